@@ -2,7 +2,7 @@
 """bench.py — the hot-path benchmark (BASELINE.json metric: depth-maps/sec at 304x228 b=24, 24 CSPN iters;
 achieved HBM GB/s vs roofline).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,6 +12,12 @@ steps, all in libcspn_hip.so) plus the fused depth-metrics reduction of the refi
 process per GPU, every rank refines its own batch (weak scaling, no collective inside the loop), one RCCL
 all-gather of the 10 metric sums at the end of the timed region.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline figures (`value`, `ms_per_step`, the schedule it
+ran).  --full adds every other measurement, each in runs of its own after the timed region: the S = 1 roofline kernel (hot
+and cache-cold), the cache-cold rotation, the sparse-depth variant, the stock-ops baseline on the same GPU, the
+forward+backward leg, a device copy and the CPU baseline.  --dump-outputs DIR writes what the last timed step returned
+as DIR/<name>.npy (inputs are seeded: two builds run with the same arguments can be compared output for output).
 """
 import argparse
 import json
@@ -32,6 +38,7 @@ if int(os.environ.get("LOCAL_RANK", "0")) == 0:
     pkg._lib.build()                                  # no-op when libcspn_hip.so is current
 
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md); ~6300 achievable
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000     # --dump-outputs: at most 64 MB in all
 
 WORKLOADS = {
     # name: (B per GPU, H, W, K, T, dtype, guidance channels)
@@ -73,6 +80,26 @@ def make_inputs(wl, B, device, seed, sparse):
     target = torch.where(torch.rand(B, 1, wl["H"], wl["W"], device=device, generator=gen) < 0.05,
                          torch.zeros_like(target), target).to(dt)
     return g, d, s, target
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each array as <out_dir>/<name>.npy, float64 kept, everything else as float32.  If the arrays
+    together would exceed DUMP_BUDGET_BYTES, each is replaced by the same share of its elements, taken at flat indices drawn
+    by a fixed seed (sorted, duplicates dropped): the same shapes give the same indices in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy() if torch.is_tensor(t) and t.dtype != torch.float64 else (
+            t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t))
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, int(a.size * DUMP_BUDGET_BYTES // total))
+            idx = np.unique(np.random.RandomState(0).randint(0, a.size, size=keep))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def load_pmc_traffic(tag, schedule="fused", launches_of_rarest=1):
@@ -435,6 +462,7 @@ def run_train(args, wl, world, rank, local_rank, device):
     cspn.register_full_backward_hook(rec("b1"))
 
     losses = []
+    last = {}                        # the last step's prediction (--dump-outputs)
 
     def step():
         pred = ddp(x)
@@ -444,6 +472,7 @@ def run_train(args, wl, world, rank, local_rank, device):
         loss.backward()
         opt.step()
         losses.append(loss.detach())
+        last["pred"] = pred.detach()
 
     def fence():
         torch.cuda.synchronize()
@@ -476,6 +505,7 @@ def run_train(args, wl, world, rank, local_rank, device):
                 static_loss = ((target - pred).abs() * valid).sum() / valid.sum()
                 static_loss.backward()
                 opt.step()
+            last["pred"] = pred.detach()
 
             def step():                                                      # noqa: F811
                 graph.replay()
@@ -549,6 +579,8 @@ def run_train(args, wl, world, rank, local_rank, device):
         res["config"]["affinity_channels"] = args.affinity_channels
         if infer is not None:
             res["inference_step"] = infer
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"prediction": last["pred"], "loss": losses[-1].double().reshape(1)})
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()
@@ -595,6 +627,12 @@ def main():
     # 181 us per pass (it no longer matters where the scheduler puts the threads: 217.3 us unbound against 220.2 bound, headline 514.1 k
     # against 514.4 k maps/s at 200 steps, profiles/r05_bench_default_bind_{off,auto}.json), and a binding the harness applies is a
     # property of the harness, not of the product
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figures, after the timed region: S = 1 roofline leg, "
+                         "cache-cold legs, sparse-depth variant, stock-ops baseline, forward+backward leg, device copy, CPU "
+                         "baseline (the --no-* options above switch single legs off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--cpu-bind", choices=("auto", "off"), default="off",
                     help="off (default): leave the affinity mask alone; auto: bind the rank's host threads to four adjacent cores of the allowed set (see bind_cpus)")
     args = ap.parse_args()
@@ -764,9 +802,10 @@ def main():
         F.set_event_log(events)
         fence()
         dbg_host = [] if os.environ.get("BENCH_DEBUG") else None
+        out = None
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            out = step()
             if dbg_host is not None:
                 dbg_host.append(time.perf_counter())
         t_loop = time.perf_counter()
@@ -789,6 +828,12 @@ def main():
     if world > 1 or force_dist:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives: the refined depth of the last step and the metric sums of the timed region
+        dumped = {"refined_depth": out}
+        if not args.no_metrics:
+            dumped["metric_sums"] = total
+        dump_outputs(args.dump_outputs, dumped)
 
     # ---- roofline of the dominant kernel (the propagation kernel), from HIP events on the launch stream
     per_fwd_us = sorted(e0.elapsed_time(e1) * 1e3 for e0, e1, _, _ in events)      # one entry per timed step
@@ -816,7 +861,7 @@ def main():
     # ---- the north-star schedule: ONE launch per propagation step (S = 1), measured in the same process.  This is the
     # HBM-bound kernel the contract's `roofline` block describes: its algorithmic bytes ARE its HBM traffic.
     per_step = None
-    if rank == 0 and not args.no_per_step_leg:
+    if rank == 0 and args.full and not args.no_per_step_leg:
         with torch.no_grad():
             if K == 3:
                 w1, _, _ = F.cspn3_prepare(g)
@@ -962,7 +1007,7 @@ def main():
     # ---- cache-cold leg: rotate over input sets whose footprint exceeds the 256 MiB Infinity
     # Cache, so that no forward finds its guidance / depth / target resident from the previous one
     cold = None
-    if rank == 0 and args.cold_sets > 1:
+    if rank == 0 and args.full and args.cold_sets > 1:
         sets = [(g, d, s, target)] + [make_inputs(wl, max(B_local, 1), device, seed=99 + i, sparse=args.sparse)
                                       for i in range(args.cold_sets - 1)]
         foot = sum(sum(t.numel() * t.element_size() for t in st if t is not None) for st in sets)
@@ -995,7 +1040,7 @@ def main():
     # passes sparse_depth — network/unet_cspn_nyu.py:362,386 — and SURVEY.md 8(d) asks for "with and without"): the scored forward on the
     # default schedule, and the S = 1 roofline kernel with the blend fused at (K^2 + 3) * sizeof(T) bytes per pixel and step
     sparse_variant = None
-    if rank == 0 and not args.sparse and not args.no_sparse_leg and B_local > 0:
+    if rank == 0 and args.full and not args.sparse and not args.no_sparse_leg and B_local > 0:
         try:
             gs, ds, ss, ts = make_inputs(wl, B_local, device, seed=1234 + rank, sparse=True)      # the same g / d / target + 500 samples
             acc_s = pkg.evaluation.new_accumulator(device)
@@ -1047,7 +1092,7 @@ def main():
 
     # ---- the reference's own GPU path as a same-box baseline: the stock-ops port on this GPU (outside the timed region)
     stock = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_stock_ops_leg and B_local > 0:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.no_stock_ops_leg and B_local > 0:
         try:
             with torch.no_grad():
                 hip_ref = (module(g, d, s) if K == 3 else module(d, g, s))
@@ -1059,7 +1104,7 @@ def main():
 
     # ---- training-shaped use of the same module (config 5's CSPN share): forward with history + hand-written backward
     train = None
-    if rank == 0 and not args.no_train_leg:
+    if rank == 0 and args.full and not args.no_train_leg:
         gt = g.detach().clone().requires_grad_(True)
         dt_ = d.detach().clone().requires_grad_(True)
         cot = torch.randn_like(d)
@@ -1098,7 +1143,7 @@ def main():
 
     # ---- what a plain device copy achieves on this GPU (fraction of achievable, next to nominal)
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         src_c = torch.empty(64 * 1024 * 1024, dtype=torch.float32, device=device)      # 256 MiB, beyond the L2
         dst_c = torch.empty_like(src_c)
         for _ in range(3):
@@ -1159,7 +1204,7 @@ def main():
             res["stock_ops_same_gpu"] = stock
         if train is not None:
             res["training_step"] = train
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 with full_affinity():
                     res["cpu_baseline"] = cpu_baseline(wl)

@@ -269,3 +269,27 @@ def test_bench_cpu_binding_narrows_and_restores_the_affinity_mask():
             assert os.sched_getaffinity(0) == set(mine)
     finally:
         os.sched_setaffinity(0, before)
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_samples_past_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 stays float64, other dtypes become float32; past the byte budget every array is cut to
+    its share of elements at seeded flat indices, the same in every call."""
+    import importlib.util
+    import os
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = torch.arange(24, dtype=torch.float16).reshape(2, 3, 4)
+    b = torch.linspace(0, 1, 10, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "whole"), {"a": a, "b": b})
+    ga, gb = np.load(str(tmp_path / "whole" / "a.npy")), np.load(str(tmp_path / "whole" / "b.npy"))
+    assert ga.dtype == np.float32 and ga.shape == (2, 3, 4) and np.array_equal(ga, a.float().numpy())
+    assert gb.dtype == np.float64 and np.array_equal(gb, b.numpy())
+    big = torch.arange(100000, dtype=torch.float32)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 40000)
+    for run in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / run), {"big": big})
+    s1, s2 = np.load(str(tmp_path / "one" / "big.npy")), np.load(str(tmp_path / "two" / "big.npy"))
+    assert s1.dtype == np.float32 and 0 < s1.nbytes <= 40000 and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) > 0) and np.isin(s1, big.numpy()).all()

@@ -1,5 +1,6 @@
 """GPU test of the bench.py contract the driver depends on: one JSON line with the agreed keys, exactly K timed
-steps, roofline + cpu_baseline objects, and the same under a torch.distributed launch (world size 1)."""
+steps, roofline + cpu_baseline objects under --full, a lean plain run whose --dump-outputs hold what the step computes, and
+the same under a torch.distributed launch (world size 1)."""
 import json
 import os
 import subprocess
@@ -26,7 +27,7 @@ def _run(cmd):
 
 
 def test_single_process_json_line():
-    d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "12", "--warmup", "2", "--prewarm-s", "0.05"])
+    d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "12", "--warmup", "2", "--prewarm-s", "0.05", "--full"])
     assert REQUIRED <= set(d)
     assert d["n_gpus"] == 1 and d["steps"] == 12 and d["warmup"] == 2 and d["higher_is_better"] is True
     assert d["unit"] == "depth-maps/s" and d["dtype"] == "f32" and d["vs_baseline"] is None
@@ -55,6 +56,37 @@ def test_single_process_json_line():
     assert so["aten_ops_per_forward"] > 24 * 10 and so["max_rel_diff_hip_vs_stock_ops"] < 1e-4
     assert d["cache_cold"]["footprint_MB"] > 256
     assert d["metrics_check"]["count"] > 0
+
+
+FULL_ONLY = ("cpu_baseline", "sparse_variant", "stock_ops_same_gpu", "training_step", "cache_cold")
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly K steps and runs none of the --full legs; --dump-outputs holds the refined depth of the last
+    timed step, bit for bit what the module returns for the bench's seeded inputs in another process, and the metric sums."""
+    import importlib.util
+    import numpy as np
+    import torch
+    out_dir = str(tmp_path / "dump")
+    d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", out_dir])
+    assert REQUIRED <= set(d) and not set(FULL_ONLY) & set(d)
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["dtype"] == "f32" and d["unit"] == "depth-maps/s"
+    assert abs(d["value"] - 24 * 7 / (d["ms_per_step"] * 7 / 1e3)) / d["value"] < 1e-6
+    assert d["default_schedule"]["launches_timed"] == 7 * d["default_schedule"]["launches_per_forward"]
+    assert sorted(os.listdir(out_dir)) == ["metric_sums.npy", "refined_depth.npy"]
+    assert sum(os.path.getsize(os.path.join(out_dir, f)) for f in os.listdir(out_dir)) <= 64 * 1000 * 1000
+    depth = np.load(os.path.join(out_dir, "refined_depth.npy"))
+    sums = np.load(os.path.join(out_dir, "metric_sums.npy"))
+    assert depth.dtype == np.float32 and depth.shape == (24, 1, 228, 304) and np.isfinite(depth).all()
+    assert sums.dtype == np.float64 and sums.shape == (10,) and sums[9] == d["metrics_check"]["count"]
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    import cspn_monodepth_amd as pkg
+    g, dd, s, _ = bench.make_inputs(bench.WORKLOADS["nyu"], 24, torch.device("cuda", 0), seed=1234, sparse=False)
+    with torch.no_grad():
+        want = pkg.CSPN_new.AffinityPropagate(24, 3)(g, dd, s)
+    assert np.array_equal(depth, want.cpu().numpy())
 
 
 def test_torchrun_world_size_one():

@@ -43,10 +43,12 @@ int resident_repair_launch(const float* g, long bs, long cs, const float* d0, co
                            int T, int blend, int n_cu, void* stream, const float* target = nullptr, double* acc = nullptr, int nslots = 0);
                            // mode 0: inference, 1: inference + fused metrics, 2: training forward, 3 / 4: reverse sweep from a tap volume / from
                                                                                  // guidance + S, 10 / 12: softmax-weight (CSPN_ours K = 3) inference / training forward
-// ... and of cspnk_forward_resident's unscored inference calls (round_every: the steps between two roundings of the state to the plane dtype)
+// ... and of cspnk_forward_resident's unscored inference calls (round_every: the steps between two roundings of the state to the plane dtype;
+// step_form: CSPN_STEP_FMA or CSPN_STEP_DOT2, the form the guarded launch ran — its arithmetic is the one re-computed)
 bool kres_repair_fits(int K, int T);
 int kres_repair_launch(const void* g, int g_dtype, int K, const void* x0, const void* sparse, void* out, int state_dtype,
-                       const unsigned* abort_word, unsigned seq, int B, int H, int W, int T, int round_every, int blend, int n_cu, void* stream);
+                       const unsigned* abort_word, unsigned seq, int B, int H, int W, int T, int round_every, int step_form, int blend, int n_cu,
+                       void* stream);
 // ... and of the K = 5 fp16 training forms: cspnk_forward_resident_history's dot-product launch and cspnk_transposed_resident
 int kres_history_repair_launch(const void* g, const void* x0, const void* sparse, void* hist, void* wk_out, const unsigned* abort_word, unsigned seq,
                                int B, int H, int W, int T, int blend, int n_cu, void* stream);

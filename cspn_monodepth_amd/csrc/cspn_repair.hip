@@ -231,9 +231,10 @@ __global__ __launch_bounds__(REP_THREADS) void cspn3_resident_repair(const RepAr
 // channels at the pixel itself (fp16 guidance: float(half) - max, 2^(d log2 e), sum in channel order, refined reciprocal, ONE rounding
 // to half; fp32 guidance: the two-piece exponential), (1-m) folded into the taps, one FMA per tap in row-major tap order from 0,
 // + m * x0, the state rounded to the plane dtype where that kernel rounds it: after every `round_every` steps (its phase length) and
-// at the end.  For the FMA step form the re-computed depth is therefore the multi-launch schedule's bits; for the dot-product form
-// (cspnk_d2: state rounded after EVERY step, two taps per v_dot2_f32_f16) round_every = 1 gives the half-precision recurrence with
-// one FMA per tap — within the fp16 tolerance of the configuration, like the host repair of that form.
+// at the end.  For the FMA step form the re-computed depth is therefore the multi-launch schedule's bits, whatever its phase length.
+// The dot-product form (cspnk_d2: state rounded after EVERY step, two taps per v_dot2_f32_f16) is re-computed with its own arithmetic
+// (D2 below).  Which of the two is re-computed is the launch site's explicit step_form argument, never inferred from round_every: an FMA
+// launch of phase length 1 (T = 1) rounds after every step as well, and must still get the FMA arithmetic.
 struct KRepArgs {
     const void* g; const void* x0; const void* sparse; void* out;
     const unsigned* abort_word; unsigned seq;
@@ -580,8 +581,10 @@ static int kres_repair_launch_t(const KRepArgs& a, int blend, size_t lds, int gr
 }
 
 int kres_repair_launch(const void* g, int g_dtype, int K, const void* x0, const void* sparse, void* out, int state_dtype,
-                       const unsigned* abort_word, unsigned seq, int B, int H, int W, int T, int round_every, int blend, int n_cu, void* stream) {
+                       const unsigned* abort_word, unsigned seq, int B, int H, int W, int T, int round_every, int step_form, int blend, int n_cu,
+                       void* stream) {
     if (!kres_repair_fits(K, T)) return fail("cspnk_forward_resident: the guard re-computes at most T * (K / 2) = 54 halo pixels (K=%d, T=%d)", K, T);
+    if (step_form != CSPN_STEP_FMA && step_form != CSPN_STEP_DOT2) return fail("cspnk_forward_resident: the guard needs the launch's step form (%d)", step_form);
     KRepArgs a{g, x0, sparse, out, abort_word, seq, B, H, W, T, round_every > 0 ? round_every : T, ceil_div(W, REP_TILE), ceil_div(H, REP_TILE)};
     const int R = REP_TILE + 2 * T * (K / 2);
     const size_t lds = (size_t)2 * R * R * sizeof(float);
@@ -591,12 +594,13 @@ int kres_repair_launch(const void* g, int g_dtype, int K, const void* x0, const 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool gh = g_dtype == CSPN_F16, sh = state_dtype == CSPN_F16;
     if (!gh && sh) return fail("cspnk_forward_resident: fp32 guidance with fp16 planes has no kernel");
+    if (step_form == CSPN_STEP_DOT2 && !(K == 5 && gh && sh)) return fail("cspnk_forward_resident: the dot-product form is K = 5 with fp16 guidance and planes");
     if (K == 3) {
         if (gh) return sh ? kres_repair_launch_t<3, __half, __half>(a, blend, lds, grid, st) : kres_repair_launch_t<3, __half, float>(a, blend, lds, grid, st);
         return kres_repair_launch_t<3, float, float>(a, blend, lds, grid, st);
     }
-    // round_every == 1 with fp16 guidance and fp16 planes is the dot-product form's launch (cspnk_d2.hip): re-computed with ITS arithmetic
-    if (gh && sh && round_every == 1) return kres_repair_launch_t<5, __half, __half, 1>(a, blend, lds, grid, st);
+    // the dot-product form's launch (cspnk_d2.hip) is re-computed with ITS arithmetic; the FMA form's at phase length 1 (T = 1) is not
+    if (step_form == CSPN_STEP_DOT2) return kres_repair_launch_t<5, __half, __half, 1>(a, blend, lds, grid, st);
     if (gh) return sh ? kres_repair_launch_t<5, __half, __half>(a, blend, lds, grid, st) : kres_repair_launch_t<5, __half, float>(a, blend, lds, grid, st);
     return kres_repair_launch_t<5, float, float>(a, blend, lds, grid, st);
 }

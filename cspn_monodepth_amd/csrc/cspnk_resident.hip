@@ -904,7 +904,8 @@ int cspnk_forward_resident(const void* guided, int g_dtype, int K, const void* x
         if (ldsb > 160 * 1024) return fail("cspnk_forward_resident: the dot-product form needs %zu bytes of LDS", ldsb);
         if (!cspn_detail::kres_d2_launch(&a, g.threads, a.nb * g.tiles_x * g.tiles_y, ldsb, blend, score, clean ? 1 : 0, npf, stream)) return 0;
         // (the dot-product form rounds the state to half after every step)
-        if (rp.guard) return cspn_detail::kres_repair_launch(guided, g_dtype, K, x0, sparse, out, state_dtype, a.status, seq, B, H, W, T, 1, blend ? 1 : 0, ncu, stream);
+        if (rp.guard) return cspn_detail::kres_repair_launch(guided, g_dtype, K, x0, sparse, out, state_dtype, a.status, seq, B, H, W, T, 1,
+                                                             CSPN_STEP_DOT2, blend ? 1 : 0, ncu, stream);
         return 1;
     }
     for (int b0 = 0; b0 < B; b0 += g.imgs_per_launch) {
@@ -925,7 +926,8 @@ int cspnk_forward_resident(const void* guided, int g_dtype, int K, const void* x
         if (!ok) return 0;
     }
     // (the FMA form rounds the state to the plane dtype at its phase boundaries)
-    if (rp.guard) return cspn_detail::kres_repair_launch(guided, g_dtype, K, x0, sparse, out, state_dtype, a.status, seq, B, H, W, T, g.S, blend ? 1 : 0, ncu, stream);
+    if (rp.guard) return cspn_detail::kres_repair_launch(guided, g_dtype, K, x0, sparse, out, state_dtype, a.status, seq, B, H, W, T, g.S,
+                                                         CSPN_STEP_FMA, blend ? 1 : 0, ncu, stream);
     return 1;
 }
 

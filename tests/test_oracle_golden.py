@@ -97,6 +97,72 @@ def test_g15_reference_half_precision_runs_keep_their_recorded_distance(tag, c_o
     assert float(z["ref_err_half"][0]) < 1e-3 and float(z["ref_err_taps16"][0]) < float(z["ref_err_half"][0])
 
 
+def _dist(o, want):
+    scale = float(np.abs(want).max())
+    return float(np.abs(np.asarray(o, np.float32) - want).max()) / scale, rmse(o, want) / scale
+
+
+@pytest.mark.parametrize("tag", ["nosp", "sp"])
+def test_g16a_stored_frames_keep_their_recorded_per_frame_distance(tag, c_oracle):
+    """Golden G16a (tests/golden/make_golden_g16.py): config 3's 24 distinct frames through the reference's two half runs, distances
+    from the fp32 oracle recorded PER FRAME.  The stored `half` outputs of one frame from each 12-frame round reproduce their recorded
+    distances from the C oracle on inputs rebuilt from the stored seed; every recorded distance is finite, positive and inside the
+    worst-case bound of a T-step half-precision recurrence (T * 2 * 2^-11)."""
+    z = load_golden("g16a_k5_t12_fp16_b24_%s" % tag)
+    B, H, W = (int(v) for v in z["shape"])
+    T = int(z["T"])
+    assert (B, H, W, T, int(z["K"])) == (24, 228, 304, 12, 5)
+    assert z["ref_err_half"].shape == z["ref_err_taps16"].shape == (B, 2)
+    for ek in ("ref_err_half", "ref_err_taps16"):
+        e = z[ek]
+        assert np.isfinite(e).all() and (e > 0).all() and (e[:, 0] < T * 2 * 2.0 ** -11).all() and (e[:, 1] <= e[:, 0]).all(), ek
+    assert len(np.unique(z["ref_err_half"][:, 0])) == B                 # 24 distinct frames, not one frame repeated
+    frames = [int(f) for f in z["frames"]]
+    assert frames[0] < 12 <= frames[1] and z["out_half_frames"].dtype == np.float16
+    gd, x, sp = orc.g16_inputs(z, c_oracle)
+    for i, f in enumerate(frames):
+        f32 = lambda a: None if a is None else a[f:f + 1].astype(np.float32)      # noqa: E731
+        want = c_oracle.pac_forward(f32(x), f32(gd), f32(sp), T)
+        emax, erms = _dist(z["out_half_frames"][i:i + 1], want)
+        assert abs(emax - float(z["ref_err_half"][f, 0])) <= 1e-6 and abs(erms - float(z["ref_err_half"][f, 1])) <= 1e-6, (f, emax, erms)
+
+
+@pytest.mark.parametrize("name", golden_names("g16b_"))
+def test_g16b_regimes_keep_their_recorded_distance(name, c_oracle):
+    """Golden G16b: the reference's two half runs in four input regimes (peaky / near-uniform / saturated softmax, KITTI depth range)
+    reproduce their recorded distances from the C oracle; the regimes are what they say (the peaky one puts taps below fp16's normal
+    range, the saturated one has its hot channel on a tenth of the pixels)."""
+    z = load_golden(name)
+    T = int(z["T"])
+    gd, x, sp = orc.g16_inputs(z, c_oracle)
+    f32 = lambda a: None if a is None else a.astype(np.float32)      # noqa: E731
+    want = c_oracle.pac_forward(f32(x), f32(gd), f32(sp), T)
+    assert z["out_half"].dtype == np.float16 and z["out_half"].shape == want.shape == z["out_taps16"].shape
+    for key, ek in (("out_taps16", "ref_err_taps16"), ("out_half", "ref_err_half")):
+        e = z[ek]
+        assert np.isfinite(e).all() and (e > 0).all() and e[0] < T * 2 * 2.0 ** -11, ek
+        emax, erms = _dist(z[key], want)
+        assert abs(emax - float(e[0])) <= 1e-6 and abs(erms - float(e[1])) <= 1e-6, (key, emax, erms, e)
+    taps = orc.pac_kernel(f32(gd))[0]
+    if "peaky" in name:
+        assert float(z["g_scale"]) == 8.0 and float(((taps > 0) & (taps < 2.0 ** -14)).mean()) > 0.1
+    if "flat" in name:
+        assert float(z["g_scale"]) == 0.05 and float(taps.max()) < 1.5 / 24
+    if "kitti" in name:
+        assert float(z["x_hi"]) == 85.0 and float(f32(x).max()) > 80.0
+    if "saturated" in name:
+        hot = int(z["hot"][0])
+        assert float(z["hot"][1]) == 30.0 and 0.08 < float((gd[:, hot] == 30.0).mean()) < 0.12
+
+
+@pytest.mark.parametrize("name", golden_names("g16c_"))
+def test_g16c_gradient_distances_are_recorded(name):
+    """Golden G16c holds statistics only: the distances of the reference's half autograd (dL/dx, dL/dguided) from the fp64 oracle,
+    (max, rmse) / max |fp64 gradient| for both runs — finite, positive, ordered and below a percent."""
+    z = load_golden(name)
+    for ek in ("ref_grad_err_taps16", "ref_grad_err_half"):
+        e = z[ek]
+        assert e.shape == (2, 2) and np.isfinite(e).all() and (e > 0).all() and (e[:, 1] <= e[:, 0]).all() and (e < 1e-2).all(), ek
 def test_metrics_golden():
     z = load_golden("g7_metrics")
     got, n = orc.evaluate_metrics(z["pred"], z["target"])

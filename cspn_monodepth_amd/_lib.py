@@ -15,7 +15,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 SO_PATH = os.environ.get("CSPN_HIP_LIB") or os.path.join(_PKG, "libcspn_hip.so")   # env override: A/B builds
 CSRC = os.path.join(_PKG, "csrc")
-SOURCES = ("cspn_propagate.hip", "cspn_resident.hip", "cspnk_resident.hip", "cspnk_d2.hip", "cspn_prepare.hip", "cspn_backward.hip", "cspn_metrics.hip", "cspn_debug.hip", "cspn_repair.hip", "pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip")   # one TU each
+SOURCES = ("cspn_propagate.hip", "cspn_resident.hip", "cspnk_resident.hip", "cspnk_d2.hip", "cspn_prepare.hip", "cspn_backward.hip", "cspn_metrics.hip", "cspn_metrics_frame.hip", "cspn_debug.hip", "cspn_repair.hip", "pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip")   # one TU each
 HEADERS = (os.path.join(CSRC, "cspn_common.hpp"), os.path.join(CSRC, "cspnk_helpers.hpp"), os.path.join(_ROOT, "include", "cspn_hip.h"))
 INCLUDE = os.path.join(_ROOT, "include")
 
@@ -30,7 +30,7 @@ EXPORTS = (
     "cspn_transpose_weights", "cspn3_resident_plan", "cspn3_resident_workspace_bytes", "cspn3_forward_resident", "cspn3_transposed_resident", "cspn3_transposed_resident_guidance",
     "cspnk_resident_plan", "cspnk_resident_workspace_bytes", "cspnk_forward_resident", "cspnk_forward_resident_history", "cspnk_transposed_resident",
     "cspn_grad_weights", "cspn3_grad_guidance", "cspn_pac_grad_guided", "cspn3_backward_tail",
-    "cspn_pac_backward_tail", "cspn_metrics_accumulate",
+    "cspn_pac_backward_tail", "cspn_metrics_accumulate", "cspn_metrics_per_frame_workspace_bytes", "cspn_metrics_per_frame", "cspn_meter_update",
     "cspn_pac_out_size", "cspn_pac_force_generic", "cspn_pac_conv2d", "cspn_pac_conv2d_grad_input", "cspn_pac_conv2d_grad_kernel", "cspn_pac_nd2col", "cspn_unpool2d", "cspn_unpool2d_backward", "cspn_debug_set_lds_poison",
 )
 
@@ -54,7 +54,7 @@ class cspn_conv_geometry(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("kh", "kw", "sh", "sw", "ph", "pw", "dh", "dw", "oph", "opw", "transposed")]
 
 
-BENCH_UNRELATED = ("pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip")       # kernels no bench.py workload launches
+BENCH_UNRELATED = ("pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_metrics_frame.hip")       # kernels no bench.py workload launches
 
 
 def _source_digest(flags, code_only=False):
@@ -178,6 +178,10 @@ def _declare(lib):
     lib.cspn3_backward_tail.argtypes = [vp, vp, vp, vp, vp, vp, cl, cl, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
     lib.cspn_pac_backward_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.cspn_metrics_accumulate.argtypes = [vp, vp, ci, cs, vp, ci, vp]
+    lib.cspn_metrics_per_frame_workspace_bytes.argtypes = [ci, cs]
+    lib.cspn_metrics_per_frame_workspace_bytes.restype = cs
+    lib.cspn_metrics_per_frame.argtypes = [vp, vp, ci, ci, cs, vp, vp, vp]
+    lib.cspn_meter_update.argtypes = [vp, ci, vp, vp]
     geom = ctypes.POINTER(cspn_conv_geometry)
     lib.cspn_pac_out_size.argtypes = [ci, ci, geom, ctypes.POINTER(ci), ctypes.POINTER(ci)]
     lib.cspn_pac_force_generic.argtypes = [ci, ctypes.POINTER(ci)]
@@ -191,7 +195,7 @@ def _declare(lib):
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("cspn_last_error", "cspn_propagate_workspace_bytes", "cspn3_resident_workspace_bytes",
-                        "cspnk_resident_workspace_bytes"):
+                        "cspnk_resident_workspace_bytes", "cspn_metrics_per_frame_workspace_bytes"):
             fn.restype = ci
     return lib
 

@@ -1,0 +1,181 @@
+"""Host model the reference's ``get_model`` returns (network/__init__.py:19-20): the topology of its
+network/unet_ours.py:251-335 — ResNet encoder on a 4-channel RGB-D input, ``MyBlock`` decoder with encoder skips, a
+1-channel coarse-depth head and a bias-free 8-channel affinity head, ``CSPN_ours.AffinityPropagate(prop_time=24)`` (the
+K x K pixel-adaptive recurrence, K = 3 for 8 channels) on top; output ``[x, guidance]``.
+
+As network/unet_cspn_nyu.py here, this file is the CALLER of the hot path: convolutions and batch-norms are stock
+``torch.nn`` ops; the two pieces of this package it uses are ``network.up_pooling.MyBlock`` (the zero-insertion un-pooling
+of every decoder block as one HIP kernel, instead of a grouped conv_transpose2d against a freshly allocated one-hot
+weight, unet_ours.py:138-150) and ``post_process.CSPN_ours.AffinityPropagate`` (the HIP recurrence, forward and backward).
+
+Attribute names are the reference's — they are the checkpoint format: ``resnet50().state_dict()`` has the reference's 417
+keys / 218 123 072 parameters (``conv3``, which the reference builds at :270 and never calls, included) and loads one of
+its checkpoints with ``strict=True``.  Modules are constructed in the reference's order, so the same ``torch.manual_seed``
+gives the same weights.  The encoder blocks are the ones of unet_cspn_nyu.py here (the reference's two files define the
+same BasicBlock / Bottleneck, unet_ours.py:59-128); the decoder blocks subclass ``MyBlock`` as unet_ours.py:160-248 do.
+The import this replaces at unet_ours.py:16 is ``from cspn_monodepth_amd.post_process import CSPN_ours as post_process``.
+"""
+import torch
+import torch.nn as nn
+
+from ..post_process import CSPN_ours as post_process
+from .unet_cspn_nyu import DECODER_SIZES_NYU, BasicBlock, Bottleneck, _conv
+from .up_pooling import MyBlock
+
+__all__ = ["ResNet", "resnet50", "resnet18", "Bottleneck", "BasicBlock", "UpProj_Block", "Gudi_UpProj_Block",
+           "Gudi_UpProj_Block_Cat", "Simple_Gudi_UpConv_Block", "Simple_Gudi_UpConv_Block_Last_Layer", "DECODER_SIZES_NYU", "decoder_sizes_for"]
+
+
+def decoder_sizes_for(height, width):
+    """The five (oheight, owidth) pairs for an input of that size: every stride-2 stage of the encoder maps n to ceil(n / 2)
+    (7x7 / 3x3 windows with padding 3 / 1), and decoder stage i un-pools back to the size of the matching encoder stage.
+    decoder_sizes_for(228, 304) == DECODER_SIZES_NYU."""
+    sizes = [(int(height), int(width))]
+    for _ in range(4):
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    return tuple(reversed(sizes))
+
+
+class Gudi_UpProj_Block(MyBlock):                              # unet_ours.py:205-223
+    """un-pool -> [5x5 conv, BN, ReLU, 3x3 conv, BN] + [5x5 conv, BN] shortcut -> ReLU."""
+
+    def __init__(self, in_channels, out_channels, oheight=0, owidth=0):
+        super(Gudi_UpProj_Block, self).__init__(oheight, owidth)
+        self.conv1, self.bn1 = _conv(in_channels, out_channels, 5), nn.BatchNorm2d(out_channels)
+        self.conv2, self.bn2 = _conv(out_channels, out_channels, 3), nn.BatchNorm2d(out_channels)
+        self.sc_conv1, self.sc_bn1 = _conv(in_channels, out_channels, 5), nn.BatchNorm2d(out_channels)
+        self.relu = nn.ReLU(inplace=False)
+
+    def forward(self, x):
+        x = self._up_pooling(x, 2)
+        out = self.bn2(self.conv2(self.relu(self.bn1(self.conv1(x)))))
+        return self.relu(out + self.sc_bn1(self.sc_conv1(x)))
+
+
+class UpProj_Block(Gudi_UpProj_Block):                           # unet_ours.py:160-178: the same block under its other name
+    pass
+
+
+class Simple_Gudi_UpConv_Block(MyBlock):                         # unet_ours.py:181-191: un-pool -> 5x5 conv, BN, ReLU
+    def __init__(self, in_channels, out_channels, oheight=0, owidth=0):
+        super(Simple_Gudi_UpConv_Block, self).__init__(oheight, owidth)
+        self.conv1, self.bn1 = _conv(in_channels, out_channels, 5), nn.BatchNorm2d(out_channels)
+        self.relu = nn.ReLU(inplace=False)
+
+    def forward(self, x):
+        return self.relu(self.bn1(self.conv1(self._up_pooling(x, 2))))
+
+
+class Simple_Gudi_UpConv_Block_Last_Layer(MyBlock):              # unet_ours.py:194-202: un-pool -> one bias-free 3x3 conv
+    def __init__(self, in_channels, out_channels, oheight=0, owidth=0):
+        super(Simple_Gudi_UpConv_Block_Last_Layer, self).__init__(oheight, owidth)
+        self.conv1 = _conv(in_channels, out_channels, 3)
+
+    def forward(self, x):
+        return self.conv1(self._up_pooling(x, 2))
+
+
+class Gudi_UpProj_Block_Cat(MyBlock):                            # unet_ours.py:226-248
+    """As Gudi_UpProj_Block, with the encoder skip concatenated after the first conv and fused by a 3x3 conv."""
+
+    def __init__(self, in_channels, out_channels, oheight=0, owidth=0):
+        super(Gudi_UpProj_Block_Cat, self).__init__(oheight, owidth)
+        self.conv1, self.bn1 = _conv(in_channels, out_channels, 5), nn.BatchNorm2d(out_channels)
+        self.conv1_1, self.bn1_1 = _conv(out_channels * 2, out_channels, 3), nn.BatchNorm2d(out_channels)
+        self.conv2, self.bn2 = _conv(out_channels, out_channels, 3), nn.BatchNorm2d(out_channels)
+        self.sc_conv1, self.sc_bn1 = _conv(in_channels, out_channels, 5), nn.BatchNorm2d(out_channels)
+        self.relu = nn.ReLU(inplace=False)
+
+    def forward(self, x, side_input):
+        x = self._up_pooling(x, 2)
+        out = torch.cat((self.relu(self.bn1(self.conv1(x))), side_input), 1)
+        out = self.bn2(self.conv2(self.relu(self.bn1_1(self.conv1_1(out)))))
+        return self.relu(out + self.sc_bn1(self.sc_conv1(x)))
+
+
+class ResNet(nn.Module):
+    """unet_ours.py:251-335.  input [B,4,H,W] (RGB + sparse depth) -> [refined depth [B,1,H,W], guidance [B,8,H,W]].
+
+    `up_proj_block` is accepted and ignored, as in the reference (:253; it builds no up_proj_layer).  decoder_sizes: the five
+    (oheight, owidth) pairs of the decoder stages; the default is the reference's hard-coded 228 x 304 pyramid (:274-279).
+    prop_time: the reference hard-codes 24 (:305).  cspn_plan: handed to the CSPN module.  `return_cspn_io = True` makes
+    forward return ([x, guidance], (blur_depth, guidance, sparse_depth)) — the tensors handed to the CSPN module."""
+
+    def __init__(self, block, layers, up_proj_block=None, decoder_sizes=DECODER_SIZES_NYU, prop_time=24, cspn_plan=None):
+        super(ResNet, self).__init__()
+        self.inplanes = 64
+        e = block.expansion
+        self.conv1_1 = nn.Conv2d(4, 64, kernel_size=7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=False)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        self.layer1 = self._make_layer(block, 64, layers[0])
+        self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
+        self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
+        self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
+        self.mid_channel = 256 * e
+        self.conv2, self.bn2 = _conv(512 * e, 512 * e, 3), nn.BatchNorm2d(512 * e)
+        self.conv3 = _conv(128, 1, 3)                                  # built and never called (:270): a checkpoint key only
+        self.post_process_layer = post_process.AffinityPropagate(prop_time=prop_time, plan=cspn_plan)
+        s = decoder_sizes
+        self.gud_up_proj_layer1 = Gudi_UpProj_Block(512 * e, 256 * e, *s[0])
+        self.gud_up_proj_layer2 = Gudi_UpProj_Block_Cat(256 * e, 128 * e, *s[1])
+        self.gud_up_proj_layer3 = Gudi_UpProj_Block_Cat(128 * e, 64 * e, *s[2])
+        self.gud_up_proj_layer4 = Gudi_UpProj_Block_Cat(64 * e, 64, *s[3])
+        self.gud_up_proj_layer5 = Simple_Gudi_UpConv_Block_Last_Layer(64, 1, *s[4])       # coarse ("blur") depth head
+        self.gud_up_proj_layer6 = Simple_Gudi_UpConv_Block_Last_Layer(64, 8, *s[4])       # affinity head: K*K - 1 = 8, K = 3
+        self.return_cspn_io = False
+
+    def _make_layer(self, block, planes, blocks, stride=1):
+        downsample = None
+        if stride != 1 or self.inplanes != planes * block.expansion:
+            downsample = nn.Sequential(_conv(self.inplanes, planes * block.expansion, 1, stride),
+                                       nn.BatchNorm2d(planes * block.expansion))
+        stack = [block(self.inplanes, planes, stride, downsample)]
+        self.inplanes = planes * block.expansion
+        stack += [block(self.inplanes, planes) for _ in range(1, blocks)]
+        return nn.Sequential(*stack)
+
+    def unused_parameters(self):
+        """Parameters the forward never touches (freeze them before wrapping in DistributedDataParallel)."""
+        return list(self.conv3.parameters())
+
+    def features(self, x):
+        """Everything below the CSPN module: (blur_depth [B,1,H,W], guidance [B,8,H,W], sparse_depth [B,1,H,W])."""
+        sparse_depth = x.narrow(1, 3, 1).clone()                       # :308
+        x = self.conv1_1(x)
+        skip4 = x                                                      # pre-BN stem output, 64 ch at H/2 (:310)
+        x = self.layer1(self.maxpool(self.relu(self.bn1(x))))
+        skip3 = x                                                      # 64e ch at H/4 (:316)
+        x = self.layer2(x)
+        skip2 = x                                                      # 128e ch at H/8 (:319)
+        x = self.bn2(self.conv2(self.layer4(self.layer3(x))))
+        x = self.gud_up_proj_layer1(x)
+        x = self.gud_up_proj_layer2(x, skip2)
+        x = self.gud_up_proj_layer3(x, skip3)
+        x = self.gud_up_proj_layer4(x, skip4)
+        return self.gud_up_proj_layer5(x), self.gud_up_proj_layer6(x), sparse_depth
+
+    def forward(self, x):
+        blur_depth, guidance, sparse_depth = self.features(x)
+        x = self.post_process_layer(blur_depth, guidance, sparse_depth=sparse_depth)      # :333
+        if self.return_cspn_io:
+            return [x, guidance], (blur_depth, guidance, sparse_depth)
+        return [x, guidance]
+
+
+def resnet50(pretrained=False, **kwargs):
+    """unet_ours.py:352-363.  `pretrained` would read pretrained/resnet50.pth there; no checkpoint ships with this package."""
+    if pretrained:
+        raise RuntimeError("no pretrained checkpoint is available here; load one with model.load_state_dict(...)")
+    return ResNet(Bottleneck, [3, 4, 6, 3], UpProj_Block, **kwargs)
+
+
+def resnet18(pretrained=False, **kwargs):
+    """unet_ours.py:338-349.  Deviation: the reference hard-codes the decoder widths of the ResNet-50 plan (2048 / 1024 / 512 /
+    256, :274-277), so its own resnet18 cannot run a forward (channel mismatch at the first decoder block); here the widths
+    follow the block expansion (512 e, 256 e, ...), the same numbers for ResNet-50 and a working model for ResNet-18.
+    Checkpoints of the reference exist for ResNet-50 only (state_dict parity: tests, golden G17)."""
+    if pretrained:
+        raise RuntimeError("no pretrained checkpoint is available here; load one with model.load_state_dict(...)")
+    return ResNet(BasicBlock, [2, 2, 2, 2], UpProj_Block, **kwargs)

@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""The reference's evaluation protocol at any batch size: N synthetic NYU-sized RGB-D frames through the model its
+`get_model` returns (cspn_monodepth_amd/network/unet_ours.py), scored PER FRAME on the device
+(evaluation.FrameAverageMeter: Result.evaluate on every frame + AverageMeter over frames, libs/metrics.py:49-127), with no
+host synchronisation per batch and one `average()` at the end.
+
+    python examples/eval_loop.py --batch 24 --frames 96                  # batched, sync-free
+    python examples/eval_loop.py --batch 24 --frames 96 --graph          # one captured replay per batch, the meter inside it
+    python examples/eval_loop.py --frames 96 --compare-host-meter        # the old way: batch 1, metric_sums + a .cpu() per frame
+
+Synthetic data (device RNG, one seed per frame, so a frame does not depend on the batch it is generated in; SURVEY.md §8d
+value distributions): `prior` = a dense depth U(0.5, 10); input = RGB U(0, 1) + sparse samples of `prior` (500 per frame);
+target = prior + N(0, sigma_i^2), sigma_i between 0.05 and 0.4 from frame to frame, clamped to >= 0.1, 3 % of its pixels invalid
+(0).  The network is UNTRAINED and emits ~0, so the scored prediction is `prior + model(x)[0]` clamped to >= 0.1: predictions
+stay in the NYU depth range and every metric term is finite.  The numbers say nothing about depth estimation — they exercise
+the protocol, and tests/test_eval_protocol.py checks them against a per-frame fp64 evaluation of the dumped tensors.
+
+Prints one JSON line: the ten averages, `count` (frames) and `seconds_per_frame` (whole loop, model included, wall clock
+between two device synchronisations — a whole-model figure dominated by the stock convolutions).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cspn_monodepth_amd import evaluation as ev                           # noqa: E402
+from cspn_monodepth_amd.graphs import GraphedForward                      # noqa: E402
+from cspn_monodepth_amd.network import unet_ours                          # noqa: E402
+
+
+def make_frames(n, H, W, seed, dev):
+    """-> x [n,4,H,W], prior [n,1,H,W], target [n,1,H,W] on the device."""
+    gen = torch.Generator(device=dev)
+    xs, priors, targets = [], [], []
+    for i in range(n):
+        gen.manual_seed(seed * 1000003 + i)
+        rnd = lambda *s: torch.rand(*s, generator=gen, device=dev)        # noqa: E731
+        prior = rnd(1, H, W) * 9.5 + 0.5
+        sparse = prior * (rnd(1, H, W) < 500.0 / (H * W))
+        sigma = 0.05 + 0.35 * ((i * 7) % 16) / 15.0
+        target = (prior + sigma * torch.randn(1, H, W, generator=gen, device=dev)).clamp_(min=0.1)
+        target = target * (rnd(1, H, W) >= 0.03)
+        xs.append(torch.cat([rnd(3, H, W), sparse], 0))
+        priors.append(prior)
+        targets.append(target)
+    return torch.stack(xs), torch.stack(priors), torch.stack(targets)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--frames", type=int, default=32)
+    ap.add_argument("--model", choices=("resnet50", "resnet18"), default="resnet50")
+    ap.add_argument("--height", type=int, default=228)
+    ap.add_argument("--width", type=int, default=304)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump", metavar="DIR", help="write pred.npy / target.npy ([frames,H,W] float32) there")
+    ap.add_argument("--graph", action="store_true", help="capture forward + meter update once per batch shape and replay it")
+    ap.add_argument("--compare-host-meter", action="store_true",
+                    help="batch 1 with metric_sums + BatchAverageMeter (a host synchronisation per frame) instead of the device meter")
+    a = ap.parse_args()
+    if a.compare_host_meter:
+        a.batch, a.graph = 1, False
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(a.seed)
+    net = getattr(unet_ours, a.model)(decoder_sizes=unet_ours.decoder_sizes_for(a.height, a.width)).to(dev).eval()
+    x, prior, target = make_frames(a.frames, a.height, a.width, a.seed, dev)
+    meter = ev.FrameAverageMeter(dev)
+    host_meter = ev.BatchAverageMeter()
+
+    def predict(xb, pb):
+        return (pb + net(xb)[0]).clamp_(min=0.1)                           # the plain forward: device-guarded, safe to score unsynchronised
+
+    def step(xb, pb, tb):
+        pred = predict(xb, pb)
+        meter.update(pred, tb)
+        return pred
+
+    nb = min(a.batch, a.frames)
+    with torch.no_grad():
+        step(x[:nb], prior[:nb], target[:nb])                              # warm-up: kernel selection of the convolutions, meter buffers
+        graphed = GraphedForward(step, x[:nb], prior[:nb], target[:nb]) if a.graph else None
+        meter.reset()
+        preds = []
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for lo in range(0, a.frames, a.batch):
+            hi = min(lo + a.batch, a.frames)
+            xb, pb, tb = x[lo:hi], prior[lo:hi], target[lo:hi]
+            if a.compare_host_meter:
+                pred = predict(xb, pb)
+                host_meter.update(ev.metric_sums(pred, tb), n=1)
+            elif graphed is not None and hi - lo == nb:
+                pred = graphed(xb, pb, tb)
+            else:                                                          # eager (and the ragged last batch of a --graph run)
+                pred = step(xb, pb, tb)
+            if a.dump:
+                preds.append(pred.clone())
+        torch.cuda.synchronize(dev)
+        dt = time.perf_counter() - t0
+    res = host_meter.average() if a.compare_host_meter else meter.average()
+    if a.dump:
+        os.makedirs(a.dump, exist_ok=True)
+        np.save(os.path.join(a.dump, "pred.npy"), torch.cat(preds)[:, 0].cpu().numpy())
+        np.save(os.path.join(a.dump, "target.npy"), target[:, 0].cpu().numpy())
+    res.update(model=a.model, batch=a.batch, graph=bool(a.graph), meter="host" if a.compare_host_meter else "device",
+               count=int(res["count"]), seconds_per_frame=dt / a.frames)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -221,6 +221,28 @@ int cspn_pac_backward_tail(const void* d0, const void* dhist, const float* g_T, 
 int cspn_metrics_accumulate(const void* pred, const void* target, int dtype, size_t n,
                             double* acc, int nslots, cspn_stream_t stream);
 
+/* The same ten masked sums PER FRAME: pred / target are [B][pixels_per_frame] (contiguous, dtype CSPN_F32 / CSPN_F16),
+ * sums[B][10] (f64) is OVERWRITTEN (no zero-initialisation contract).  `work` holds
+ * cspn_metrics_per_frame_workspace_bytes(B, pixels_per_frame) bytes (= B x the value for one frame; callable without a device).
+ * No atomics.  Determinism contract: the ten doubles of frame i are a function of that frame's pixels, the dtype and
+ * pixels_per_frame only — not of B, of the frame's position in the batch, or of the alignment of its base address (the
+ * pixel -> thread -> partial-sum mapping and the order in which partials are added are fixed per pixels_per_frame; 16-byte loads
+ * are used where a frame's base allows them and fill the same registers).  Two launches (slice partials, then their sum in
+ * an order fixed by pixels_per_frame) whatever B is. */
+size_t cspn_metrics_per_frame_workspace_bytes(int B, size_t pixels_per_frame);
+int cspn_metrics_per_frame(const void* pred, const void* target, int dtype, int B, size_t pixels_per_frame,
+                           void* work, double* sums, cspn_stream_t stream);
+
+/* The reference's single-GPU evaluation protocol on the device (libs/metrics.py:49-127: Result.evaluate per frame, then
+ * AverageMeter.update(n = 1)): for every frame of sums[B][10], in index order, with n = s9:
+ *   irmse = sqrt(s0/n), imae = s1/n, mse = s2/n, rmse = sqrt(mse), mae = s3/n, absrel = s4/n, lg10 = s5/n, delta1..3 = s6..8/n
+ * are ADDED to meter[0..9]; meter[10] += B (frames), meter[11] += sum of n (valid pixels, informational).  meter[12] (f64) is
+ * zeroed by the caller once and only added to afterwards, so consecutive batches — and replays of a captured graph —
+ * accumulate; average of metric k = meter[k] / meter[10].  A frame without a valid pixel contributes 0/0 = NaN, as the
+ * reference's mean over an empty selection does.  One workgroup, frames added sequentially: deterministic, and independent
+ * of how the frames were cut into batches. */
+int cspn_meter_update(const double* sums, int B, double* meter, cspn_stream_t stream);
+
 /* ---- general pixel-adaptive convolution (network/libs/base/pac.py) ------- *
  * The single-step, multi-channel, strided / dilated form of the op the K x K recurrence iterates.  All tensors
  * are contiguous and of one dtype (CSPN_F32 / CSPN_F16, fp32 accumulation):

@@ -1,0 +1,161 @@
+"""The reference's training criteria on the device — the drop-in for `libs.criterion`:
+
+    from cspn_monodepth_amd.criterion import get_criteria        # was: from libs.criterion import get_criteria
+
+`get_criteria(args)` offers what the reference's does (libs/criterion/__init__.py:11-30): `args.criterion` in l1 / l2 / l1_log
+-> MaskedL1Loss / MaskedMSELoss / L1_log (criteria.py:14-39, 91-107), wrapped by `args.loss_wrapper`: "dsn" -> CriterionDSN
+(loss1 + 0.4 * loss2), anything else -> Criterion_No_DSN (criteria.py:170-219).  berHuLoss, BerHu, RMSE*, L1, GradLoss and
+NormalLoss are not here: get_criteria does not offer them either, and berHu needs a dependent max pass.
+
+The reference selects the valid pixels with `diff[valid_mask]`: boolean indexing calls nonzero, a device-to-host copy on every
+step that no graph can capture.  Here a loss is three launches of include/cspn_criterion.h on the current stream — per-slice
+sums and their combination forward, one streaming kernel backward — with no atomics, no `.item()`, no nonzero and no host
+synchronisation; the loss is a 0-dim fp32 device tensor, deterministic to the bit (a function of the values, the kind and the
+element count only), and the whole step can sit inside a `torch.cuda.graph` capture.
+
+fp32 only, on purpose: the criterion is a mean, so a valid pixel's gradient is g / count — about 1e-6 for a 24 x 228 x 304
+batch, below what fp16 can hold.  A half prediction raises TypeError; cast it with `.float()` in front of the criterion (the
+cast's backward rounds the gradient once, where the caller can see it)."""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+
+KINDS = {"l1": _lib.LOSS_L1, "l2": _lib.LOSS_L2, "l1_log": _lib.LOSS_L1_LOG}
+STATE_BYTES = 32     # CSPN_CRITERION_STATE_BYTES: float loss, float 1 / count, double sum, double count, 8 reserved
+
+_FP32_ONLY = ("masked_loss: fp32 only, got %s — the gradient of a mean over ~1e6 pixels (g / count) is below the smallest fp16 "
+              "subnormal; cast the prediction with .float() first")
+
+
+def criterion_workspace(n, device):
+    """(work, state) of one forward over n elements.  Fresh from torch's caching allocator on every call — which hands back the
+    same blocks step after step without a synchronisation, also inside a graph capture — because a state belongs to ONE
+    forward until its backward has run: CriterionDSN has two forwards of the same size alive at once."""
+    nbytes = _lib.lib().cspn_criterion_workspace_bytes(int(n))
+    return (torch.empty((nbytes // 8,), dtype=torch.float64, device=device),
+            torch.empty((STATE_BYTES // 4,), dtype=torch.float32, device=device))
+
+
+class _MaskedLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, kind):
+        n = pred.numel()
+        work, state = criterion_workspace(n, pred.device)
+        with torch.cuda.device(pred.device):
+            ok = _lib.lib().cspn_criterion_forward(pred.data_ptr(), target.data_ptr(), _lib.CSPN_F32, kind, n, work.data_ptr(),
+                                                   state.data_ptr(), torch.cuda.current_stream(pred.device).cuda_stream)
+        _lib.check(ok, "cspn_criterion_forward")
+        ctx.save_for_backward(pred, target)
+        ctx.state, ctx.kind = state, kind
+        return state[0]                                  # 0-dim view of the state's first word: no copy, no launch
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable         # double backward raises
+    def backward(ctx, grad_loss):
+        pred, target = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        g = grad_loss
+        if g.dtype != torch.float32 or g.device != pred.device:
+            g = g.to(device=pred.device, dtype=torch.float32)
+        g = g.contiguous()
+        grad = torch.empty_like(pred, memory_format=torch.contiguous_format)
+        with torch.cuda.device(pred.device):
+            ok = _lib.lib().cspn_criterion_backward(pred.data_ptr(), target.data_ptr(), _lib.CSPN_F32, ctx.kind, pred.numel(),
+                                                    ctx.state.data_ptr(), g.data_ptr(), grad.data_ptr(),
+                                                    torch.cuda.current_stream(pred.device).cuda_stream)
+        _lib.check(ok, "cspn_criterion_backward")
+        return grad, None, None
+
+
+def masked_loss(pred, target, kind):
+    """mean over target > 0 of |t - p| ("l1"), (t - p)^2 ("l2") or |log t - log p| ("l1_log"): a 0-dim fp32 device tensor with
+    a gradient for `pred` only.  No valid pixel: NaN, and a zero gradient, as the reference gives."""
+    if kind not in KINDS:
+        raise NotImplementedError("masked_loss: no criterion named %r (l1, l2, l1_log)" % (kind,))
+    if pred.dtype != torch.float32:
+        raise TypeError(_FP32_ONLY % (pred.dtype,))
+    if not (pred.is_cuda and target.is_cuda):
+        raise RuntimeError("masked_loss: tensors must live on a ROCm device (no CPU implementation here)")
+    if pred.shape != target.shape or pred.device != target.device:
+        raise ValueError("pred / target must have the same shape and device, got %s and %s" % (tuple(pred.shape), tuple(target.shape)))
+    if pred.numel() < 1:
+        raise ValueError("masked_loss: empty tensors")
+    target = target.detach()
+    if target.dtype != torch.float32:
+        target = target.float()
+    return _MaskedLoss.apply(pred.contiguous(), target.contiguous(), KINDS[kind])
+
+
+def _resized(pred, target):
+    """pred at the target's spatial size: a stock bilinear resize with align_corners=True when the sizes differ."""
+    if tuple(pred.shape[-2:]) == tuple(target.shape[-2:]):
+        return pred
+    return F.interpolate(pred, size=tuple(target.shape[-2:]), mode="bilinear", align_corners=True)
+
+
+class _Masked(nn.Module):
+    """One kind of masked_loss as a module; the result is also kept in self.loss."""
+    kind = None
+
+    def forward(self, pred, target):
+        if pred.dim() != target.dim():
+            raise AssertionError("inconsistent dimensions")
+        self.loss = masked_loss(pred, target, self.kind)
+        return self.loss
+
+
+class MaskedL1Loss(_Masked):
+    kind = "l1"
+
+
+class MaskedMSELoss(_Masked):
+    kind = "l2"
+
+
+class L1_log(nn.Module):
+    """(fake, real), as the reference names them; a prediction of another size is resized to the target's first."""
+
+    def forward(self, fake, real):
+        if fake.dim() != real.dim():
+            raise AssertionError("inconsistent dimensions")
+        return masked_loss(_resized(fake, real), real, "l1_log")
+
+
+class _Wrapper(nn.Module):
+    def __init__(self, criterion=None):
+        super().__init__()
+        self.criterion = criterion
+
+    def _one(self, pred, target):
+        return self.criterion(_resized(pred, target), target)
+
+
+class Criterion_No_DSN(_Wrapper):
+    """One output: criterion(preds[0], target), preds[0] resized to the target's size when it differs (criteria.py:170-188)."""
+
+    def forward(self, preds, target):
+        return self._one(preds[0], target)
+
+
+class CriterionDSN(_Wrapper):
+    """Deep supervision: criterion(preds[0], target) + 0.4 * criterion(preds[1], target), each prediction resized to the
+    target's size when it differs (criteria.py:191-219).  The second backward receives 0.4 as its incoming gradient."""
+
+    def forward(self, preds, target):
+        return self._one(preds[0], target) + 0.4 * self._one(preds[1], target)
+
+
+key_to_criteria = {"l1": MaskedL1Loss, "l2": MaskedMSELoss, "l1_log": L1_log}
+
+
+def get_criteria(args):
+    """args.criterion: a key of key_to_criteria; anything else raises NotImplementedError (the reference prints args.arch and
+    raises it bare; here the message names the key, and args.arch is not read).  args.loss_wrapper: "dsn" in any letter case ->
+    CriterionDSN, anything else -> Criterion_No_DSN."""
+    if args.criterion not in key_to_criteria:
+        raise NotImplementedError("no available criterion method named %r (%s)" % (args.criterion, ", ".join(key_to_criteria)))
+    wrapper = CriterionDSN if args.loss_wrapper.lower() == "dsn" else Criterion_No_DSN
+    return wrapper(criterion=key_to_criteria[args.criterion]())

@@ -66,6 +66,8 @@ struct ResArgs {
     int b0, nb;              // images [b0, b0 + nb) are refined by this launch
     unsigned spin_limit;
     unsigned long long* dbg;  // developer probe: [grid][16] wall-clock stamps (100 MHz) per workgroup, or null
+    int th0, thl;            // heights of the first / last tile row (res_row_h); th is the height of the rows in between.  (Last: only the
+                             // clipped instances read them, and the kernel arguments of the others stay where their code was tuned.)
 };
 
 __device__ __forceinline__ void st4_dev(float* base, unsigned elem, float a, float b, float c, float d) {
@@ -141,6 +143,37 @@ __device__ __forceinline__ float ld1_dev(gptr p) {
 }
 
 constexpr int RES_THREADS = 512;
+constexpr int RES_THREADS_CLIPPED = 768;     // three wavefronts per SIMD, NQ = 3, clipped regions (resident_geometry_clipped)
+
+// Tile rows and region origins, shared by the kernel and the host's checks (regions_inside_image).  Tile columns are all tw wide.
+// Tile rows may be uneven: row 0 is th0 high, the last row thl, the rows in between th (the 512- / 1024-thread plans: all three are
+// the same; the clipped plans make the first and the last row taller by the halo they do not need at the image edge, so that all
+// regions are equally high).  The last row may still be cut short by the image.
+// UNEVEN = false is the same arithmetic for instances whose rows are known to be all th high (the kernel's 512- / 1024-thread
+// instances: their register allocation is tuned to the last scratch slot, and must not see the general form); the host uses the
+// general form for every plan.
+template <bool UNEVEN = true>
+__host__ __device__ __forceinline__ int res_row_y0(int ty, int th0, int th) {
+    if (!UNEVEN) return ty * th;
+    return ty <= 0 ? 0 : th0 + (ty - 1) * th;
+}
+template <bool UNEVEN = true>
+__host__ __device__ __forceinline__ int res_row_h(int ty, int tiles_y, int th0, int th, int thl) {
+    if (!UNEVEN) return th;
+    return ty == 0 ? th0 : (ty == tiles_y - 1 ? thl : th);
+}
+// Region origin: tile - halo, moved back into the image where a region of the launch's (fixed) size would stick out, but never
+// before the previous tile's start when the launch exchanges borders (the halo must come from the 8 adjacent tiles).
+__host__ __device__ __forceinline__ int res_region_x0(int tx, int tw, int hxw, int wq, int W, bool exch) {
+    const int x0 = tx * tw;
+    return max(exch ? max(0, x0 - tw) : 0, min(x0 - hxw, W - 4 * wq));
+}
+template <bool UNEVEN = true>
+__host__ __device__ __forceinline__ int res_region_y0(int ty, int th0, int th, int hyw, int wr, int H, bool exch) {
+    const int y0 = res_row_y0<UNEVEN>(ty, th0, th);
+    const int lo = exch ? (UNEVEN ? res_row_y0(ty - 1, th0, th) : max(0, y0 - th)) : 0;
+    return max(lo, min(y0 - hyw, H - wr));
+}
 // The two depth buffers of the step loop sit a COMPILE-TIME distance apart (RES_PP floats; the second one starts there
 // whatever the region size): with the step loop unrolled by two, "the other buffer" is then an immediate offset of the
 // ds_read / ds_write instead of a second set of row addresses (7 VGPRs the 256-register instances do not have), and no
@@ -189,7 +222,9 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
     const int tx = trem - ty * a.tiles_x;
     const int b = a.b0 + round * a.nb + bl;
     const int H = a.H, W = a.W;
-    const int y0 = ty * a.th, x0 = tx * a.tw;
+    constexpr bool UNEVEN = NTHREADS == RES_THREADS_CLIPPED;             // only the clipped plans have uneven tile rows
+    const int y0 = res_row_y0<UNEVEN>(ty, a.th0, a.th), x0 = tx * a.tw;
+    const int th_t = res_row_h<UNEVEN>(ty, a.tiles_y, a.th0, a.th, a.thl);      // this tile row's height
     const size_t HW = (size_t)H * W;
     const size_t plane = (size_t)a.B * HW;
     if (tid == 0) wg_bad = 0;
@@ -233,8 +268,8 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
     // (the "previous tile's start" bound belongs to the exchange: a single-phase launch stages everything from the coarse
     // depth, and its halo may be deeper than a tile — there the bound would cut the region short of y0 - hyw)
     const bool exch = a.T > a.S;
-    const int rx0 = max(exch ? max(0, x0 - a.tw) : 0, min(x0 - a.hxw, W - 4 * wq));
-    const int ry0 = max(exch ? max(0, y0 - a.th) : 0, min(y0 - a.hyw, H - wr));
+    const int rx0 = res_region_x0(tx, a.tw, a.hxw, wq, W, exch);
+    const int ry0 = res_region_y0<UNEVEN>(ty, a.th0, a.th, a.hyw, wr, H, exch);
     const int xq = rx0 + 4 * sx;
     const int yq0 = ry0 + r0;
     const bool x_in = (xq >= 0) && (xq < a.Wv);
@@ -321,7 +356,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
         const int r = r0 + i, y = yq0 + i;
         const bool ok = (r < wr) && x_in && (y >= 0) && (y < H);
         if (ok) in_img |= 1u << i;
-        if (ok && y >= y0 && y < y0 + a.th && xq >= x0 && xq < x0 + a.tw) interior |= 1u << i;
+        if (ok && y >= y0 && y < y0 + th_t && xq >= x0 && xq < x0 + a.tw) interior |= 1u << i;
         unsigned orow[3];
         bool rokv[3];
 #pragma unroll
@@ -551,7 +586,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
             int tidp = tid;                                    // opaque copy: the per-thread halo addressing below is recomputed
             asm volatile("" : "+v"(tidp));                     // every phase instead of living (spilled) across the step loop
             const int tq_in = min(a.tw, rx0 + 4 * wq - x0) >> 2;   // tile columns / rows that lie inside the region (the last
-            const int th_in = min(a.th, ry0 + wr - y0);            // tile of an image may be cut short by the image edge)
+            const int th_in = min(th_t, ry0 + wr - y0);            // tile of an image may be cut short by the image edge)
             const int nl = (x0 - rx0) >> 2;                    // quads left of the tile columns inside the region
             const int nside = wq - tq_in;                      // ... left + right
             const int nrow_t = (y0 - ry0) + R;                 // depth-region rows above the tile rows (ring row included)
@@ -818,8 +853,8 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
                 // a column band and a row band, so the union of the four bands covers all eight.  At config 2 that is 57 % of the
                 // interior quads: fewer device-scope stores to wait for before the flag, 6 MB less write traffic per forward.
 #if !CSPN_RES_PUBLISH_ALL
-                auto reg_x0 = [&](int t) { const int xx0 = t * a.tw; return max(max(0, xx0 - a.tw), min(xx0 - a.hxw, W - 4 * wq)); };
-                auto reg_y0 = [&](int t) { const int yy0 = t * a.th; return max(max(0, yy0 - a.th), min(yy0 - a.hyw, H - wr)); };
+                auto reg_x0 = [&](int t) { return res_region_x0(t, a.tw, a.hxw, wq, W, true); };
+                auto reg_y0 = [&](int t) { return res_region_y0<UNEVEN>(t, a.th0, a.th, a.hyw, wr, H, true); };
                 const int pubL = tx > 0 ? reg_x0(tx - 1) + 4 * wq + 1 : -(1 << 30);            // columns x < pubL are read by the tiles on the left
                 const int pubR = tx + 1 < a.tiles_x ? reg_x0(tx + 1) - 1 : (1 << 30);          // columns x >= pubR by the tiles on the right
                 const int pubT = ty > 0 ? reg_y0(ty - 1) + wr + 1 : -(1 << 30);                // rows y < pubT by the tiles above
@@ -949,8 +984,11 @@ struct ResGeom {
     int imgs_per_launch, launches;
     size_t lds_bytes;
     double cost;
-    int threads = RES_THREADS;      // 512, or 1024 with one quad per thread (four wavefronts per SIMD: small shards, round 5)
+    int threads = RES_THREADS;      // 512, or 1024 with one quad per thread (four wavefronts per SIMD: small shards, round 5),
+                                    // or 768 with three quads per thread on clipped regions (three wavefronts per SIMD)
+    int th0 = 0, thl = 0;           // first / last tile row (res_row_h); set_uniform_rows() for the plans whose rows are all th high
 };
+void set_uniform_rows(ResGeom* g) { g->th0 = g->thl = g->th; }
 
 int cu_count() {
     static std::atomic<int> cached[64];
@@ -985,30 +1023,95 @@ int res_row_stride(int wq, int nq, int dr) {
     return lo;
 }
 
-// Mirror of the kernel's region placement: does every region of every tile lie inside the (valid part of the) image?
+// Does every region of every tile lie inside the (valid part of the) image?  (The kernel's own region placement: res_region_x0 / _y0.)
 bool regions_inside_image(const ResGeom& g, int H, int W, int Wv, int T) {
     if (Wv != W) return false;
-    const bool exch = T > g.S;            // mirrors the kernel: see the region origin there
+    const bool exch = T > g.S;            // see the region origin in the kernel
     for (int tx = 0; tx < g.tiles_x; ++tx) {
-        const int x0 = tx * g.tw;
-        int rx0 = x0 - g.hxw; if (rx0 > W - 4 * g.wq) rx0 = W - 4 * g.wq;
-        int lo = exch ? x0 - g.tw : 0; if (lo < 0) lo = 0;
-        if (rx0 < lo) rx0 = lo;
-        if (rx0 + 4 * g.wq > W) return false;
+        const int rx0 = res_region_x0(tx, g.tw, g.hxw, g.wq, W, exch);
+        if (rx0 < 0 || rx0 + 4 * g.wq > W) return false;
     }
     for (int ty = 0; ty < g.tiles_y; ++ty) {
-        const int y0 = ty * g.th;
-        int ry0 = y0 - g.hyw; if (ry0 > H - g.wr) ry0 = H - g.wr;
-        int lo = exch ? y0 - g.th : 0; if (lo < 0) lo = 0;
-        if (ry0 < lo) ry0 = lo;
-        if (ry0 + g.wr > H) return false;
+        const int ry0 = res_region_y0(ty, g.th0, g.th, g.hyw, g.wr, H, exch);
+        if (ry0 < 0 || ry0 + g.wr > H) return false;
     }
     return true;
+}
+
+// The clipped geometry of the 768-thread instance.  The region is as large as a tile really needs: per axis the largest extent of
+// (tile +- halo) cut to the image.  A tile at an image edge needs its halo on one side only, so with two tile columns the region is
+// tw + hxw wide instead of tw + 2 hxw, and the first and the last tile ROW are made taller than the rows in between (th0 = wr - hyw
+// against th = wr - 2 hyw; the last row takes the rest of the image, at most th0), so that every row's region is wr high.  With three
+// or more columns the inner tiles keep their two-sided halo: wq is then what the 512-thread plans use.  Every thread owns a strip of
+// 3 quads: ceil(wr / 3) wq <= 768.  Fills *g for `tiles_x` x `tiles_y` tiles of width tw with a first row of th0 (tiles_y == 1: the
+// whole image); false when that is no valid clipped tiling: rows that do not cover the image, a halo reaching past the adjacent
+// tile, a region outside the image, or more than the instance / LDS holds.
+bool clipped_geometry(int H, int W, int T, int Se, int tiles_x, int tiles_y, int tw, int th0, int blend, ResGeom* g) {
+    if (tiles_x < 1 || tiles_y < 1 || tw < 4 || (tw & 3) || th0 < 1 || Se < 1) return false;
+    const int hyw = Se - 1, hxw = round_up4(Se - 1), phases = ceil_div(T, Se);
+    if (phases > 1 && (Se & 1)) return false;
+    if (tiles_x * tw < W || (tiles_x - 1) * tw >= W) return false;
+    if (phases > 1 && tiles_x > 1 && tw < 2 * hxw) return false;
+    int th = th0, thl = th0, wr = H;
+    if (tiles_y == 1) {
+        if (th0 < H) return false;
+        th = thl = th0 = H;
+    } else {
+        wr = th0 + hyw;
+        th = wr - 2 * hyw;
+        thl = H - th0 - (tiles_y - 2) * th;
+        if (th < 1 || thl < 1 || thl > th0) return false;
+        if (phases > 1 && (th0 < 2 * hyw || (tiles_y > 2 && th < 2 * hyw) || thl < hyw)) return false;
+    }
+    int wx = 0;                            // widest (tile +- halo) within the image
+    for (int tx = 0; tx < tiles_x; ++tx) {
+        const int lo = tx * tw - hxw > 0 ? tx * tw - hxw : 0, hi = (tx + 1) * tw + hxw < W ? (tx + 1) * tw + hxw : W;
+        if (hi - lo > wx) wx = hi - lo;
+    }
+    const int wq = wx / 4;
+    if (wq < 1 || ceil_div(wr, 3) * wq > RES_THREADS_CLIPPED) return false;
+    const int dr = wr + 2, ls = res_row_stride(wq, 3, dr);
+    if ((size_t)dr * ls > (size_t)RES_PP) return false;
+    const size_t ldsb = res_lds_bytes(dr, ls, 3, blend, RES_THREADS_CLIPPED);
+    if (ldsb > 160 * 1024) return false;
+    *g = ResGeom{Se, tiles_x, tiles_y, tw, th, 3, wq, wr, hxw, hyw, dr, ls, 0, 0, ldsb, 0.0};
+    g->threads = RES_THREADS_CLIPPED; g->th0 = th0; g->thl = thl;
+    return regions_inside_image(*g, H, W, W, T);          // the instance is CLEAN only
+}
+
+// The search over clipped tilings (threads = 768): same phase lengths and tile widths as resident_geometry, the smallest region
+// height that covers the image with `ty` rows.
+bool resident_geometry_clipped(int B, int H, int W, int T, int blend, int ncu, int S_user, ResGeom* best) {
+    if (W % 4 != 0 || ncu < 1 || T < 1) return false;
+    bool found = false;
+    for (int S = (S_user > 0 ? S_user : 12); S >= (S_user > 0 ? S_user : 4); S -= (S > 8 ? 4 : 2)) {
+        const int Se = S > T ? T : S;
+        const int hyw = Se - 1, phases = ceil_div(T, Se);
+        for (int tx = 1; tx <= 32; ++tx) {
+            const int tw = round_up4(ceil_div(W, tx));
+            if (tx > 1 && (tw < 16 || ceil_div(W, tw) != tx)) continue;
+            for (int ty = 1; ty <= 64 && tx * ty <= ncu; ++ty) {
+                const int wr = ty == 1 ? H : ceil_div(H + 2 * hyw * (ty - 1), ty);
+                ResGeom cand;
+                if (!clipped_geometry(H, W, T, Se, tx, ty, tw, ty == 1 ? H : wr - hyw, blend, &cand)) continue;
+                int ipl = ncu / (tx * ty);
+                if (ipl > B) ipl = B;
+                cand.imgs_per_launch = ipl; cand.launches = ceil_div(B, ipl);
+                // the 512-thread model with the quads a thread really holds (its strips are 3 quads, the region's rows rarely fill the
+                // last one) and three wavefronts per SIMD; fitted at config 2 (profiles/r07_clipped_ab.txt)
+                const double q = (double)cand.wq * cand.wr / 256.0 / 3.0;
+                cand.cost = cand.launches * (8.0 + 2.0 * q + T * (0.13 * q + 0.1) + (phases - 1) * (3.0 + 0.6 * q));
+                if (!found || cand.cost < best->cost) { found = true; *best = cand; }
+            }
+        }
+    }
+    return found;
 }
 
 // Tiling of one image for the resident kernel: every workgroup owns a tw x th tile + (S-1) halo; a launch holds
 // imgs_per_launch whole images on at most `ncu` workgroups.  Cost model: launches x (quads per thread + latency floor).
 bool resident_geometry(int B, int H, int W, int T, int blend, int ncu, int S_user, ResGeom* best, int threads = RES_THREADS) {
+    if (threads == RES_THREADS_CLIPPED) return resident_geometry_clipped(B, H, W, T, blend, ncu, S_user, best);
     if (W % 4 != 0 || ncu < 1 || T < 1) return false;
     if (threads != 1024) threads = RES_THREADS;
     const int max_nq = threads == 1024 ? 1 : RES_MAX_NQ;       // 1024 threads = 128 VGPRs: one quad's weights per thread
@@ -1044,6 +1147,7 @@ bool resident_geometry(int B, int H, int W, int T, int blend, int ncu, int S_use
                 if (ipl > B) ipl = B;
                 const int launches = ceil_div(B, ipl);
                 ResGeom cand{Se, tx, ty, tw, th, nq, wq, wr, hxw, hyw, dr, ls, ipl, launches, ldsb, 0.0};
+                set_uniform_rows(&cand);
                 // microseconds per launch, fitted on MI355X (profiles/r02_resident_vs_multilaunch.jsonl): launch + epilogue,
                 // derive (~2 us per quad of a thread), T steps (VALU-bound: 0.13 us per quad; x 1.13 with the zero-padding
                 // selects of a launch whose regions stick out of the image), and per phase boundary the publish / wait /
@@ -1054,6 +1158,7 @@ bool resident_geometry(int B, int H, int W, int T, int blend, int ncu, int S_use
                     found = true;
                     *best = ResGeom{Se, tx, ty, tw, th, nq, wq, wr, hxw, hyw, dr, ls, ipl, launches, ldsb, cost};
                     best->threads = threads;
+                    set_uniform_rows(best);
                 }
             }
         }
@@ -1082,6 +1187,13 @@ int launch_resident_1024(const ResArgs& a, int grid, size_t lds, int blend, int 
     if (mode == 0) return blend ? launch_resident_inst<1, 1, 0, CLEAN, 0, 1024>(a, grid, lds, st) : launch_resident_inst<1, 0, 0, CLEAN, 0, 1024>(a, grid, lds, st);
     if (mode == 1) return blend ? launch_resident_inst<1, 1, 1, CLEAN, 0, 1024>(a, grid, lds, st) : launch_resident_inst<1, 0, 1, CLEAN, 0, 1024>(a, grid, lds, st);
     return fail("cspn3_forward_resident: 1024-thread workgroups serve the inference forms only");
+}
+
+// 768 threads, three quads per thread, clipped regions: the inference forms only (plain / scored), CSPN_new weights, CLEAN
+int launch_resident_768(const ResArgs& a, int grid, size_t lds, int blend, int mode, hipStream_t st) {
+    if (mode == 0) return blend ? launch_resident_inst<3, 1, 0, 1, 0, RES_THREADS_CLIPPED>(a, grid, lds, st) : launch_resident_inst<3, 0, 0, 1, 0, RES_THREADS_CLIPPED>(a, grid, lds, st);
+    if (mode == 1) return blend ? launch_resident_inst<3, 1, 1, 1, 0, RES_THREADS_CLIPPED>(a, grid, lds, st) : launch_resident_inst<3, 0, 1, 1, 0, RES_THREADS_CLIPPED>(a, grid, lds, st);
+    return fail("cspn3_forward_resident: 768-thread workgroups serve the inference forms only");
 }
 
 template <int NQ, int CLEAN>
@@ -1125,10 +1237,13 @@ int cspn3_resident_plan(int B, int H, int W, int T, int blend, int n_cu, cspn_re
     if (T < 1 || !resident_geometry(B, H, W, T, blend, n_cu, out->steps_per_phase, &g, out->threads))
         return fail("cspn3_resident_plan: no resident tiling for B=%d %dx%d T=%d on %d CUs (W %% 4 == 0 needed)", B, H, W, T, n_cu);
     if (ceil_div(T, g.S) > 255) return fail("cspn3_resident_plan: T=%d in %d-step phases is more than 255 phases", T, g.S);
-    out->steps_per_phase = g.S; out->tiles_x = g.tiles_x; out->tiles_y = g.tiles_y; out->tile_w = g.tw; out->tile_h = g.th;
+    out->steps_per_phase = g.S; out->tiles_x = g.tiles_x; out->tiles_y = g.tiles_y; out->tile_w = g.tw;
+    out->tile_h = g.threads == RES_THREADS_CLIPPED ? g.th0 : g.th;       // (clipped plans: the first row; the others follow from it)
     out->quads_per_thread = g.nq; out->threads = g.threads; out->images_per_launch = g.imgs_per_launch;
     out->launches = g.launches; out->lds_bytes = (int)g.lds_bytes; out->n_cu = n_cu;
-    out->region_over_tile = (float)((double)(4 * g.wq) * g.wr / ((double)g.tw * g.th));
+    out->region_over_tile = g.threads == RES_THREADS_CLIPPED
+        ? (float)((double)(4 * g.wq) * g.wr * g.tiles_x * g.tiles_y / ((double)H * W))
+        : (float)((double)(4 * g.wq) * g.wr / ((double)g.tw * g.th));
     return 1;
 }
 
@@ -1214,7 +1329,20 @@ int resident_launch(const void* guidance, long bs, long cs, const void* d0, cons
     ResGeom g;
     cspn_resident_plan rp{};
     if (plan) rp = *plan;
-    if (rp.tiles_x > 0 && rp.tiles_y > 0 && rp.tile_w > 0 && rp.tile_h > 0 && rp.steps_per_phase > 0 && rp.images_per_launch > 0) {
+    const int Wv = (W_valid > 0 && W_valid < W) ? W_valid : W;
+    if (rp.threads == RES_THREADS_CLIPPED && (transposed || history || pac || Wv != W)) {
+        // the clipped instance serves plain / scored inference on unpadded rows: everything else takes the 512-thread plan of the
+        // same phase length (its tiling is searched for: the clipped plan's tile fields mean nothing to it)
+        rp.threads = RES_THREADS;
+        rp.tiles_x = rp.tiles_y = rp.tile_w = rp.tile_h = rp.images_per_launch = 0;
+    }
+    if (rp.threads == RES_THREADS_CLIPPED && rp.tiles_x > 0 && rp.tiles_y > 0 && rp.tile_w > 0 && rp.tile_h > 0 && rp.steps_per_phase > 0 && rp.images_per_launch > 0) {
+        // a clipped plan: tile_h is the FIRST tile row's height, the uneven rows follow from it (clipped_geometry)
+        if (!clipped_geometry(H, W, T, rp.steps_per_phase > T ? T : rp.steps_per_phase, rp.tiles_x, rp.tiles_y, rp.tile_w, rp.tile_h, blend, &g) ||
+            (long)rp.images_per_launch * g.tiles_x * g.tiles_y > ncu)
+            return fail("cspn3_forward_resident: the clipped plan does not fit this problem / device (use cspn3_resident_plan)");
+        g.imgs_per_launch = rp.images_per_launch;
+    } else if (rp.tiles_x > 0 && rp.tiles_y > 0 && rp.tile_w > 0 && rp.tile_h > 0 && rp.steps_per_phase > 0 && rp.images_per_launch > 0) {
         // a plan that came out of cspn3_resident_plan for this problem: re-derive the dependent fields and re-check the
         // limits, skip the search (it is ~6000 candidate tilings: tens of microseconds per call on the host)
         const int Se = rp.steps_per_phase > T ? T : rp.steps_per_phase;
@@ -1222,6 +1350,7 @@ int resident_launch(const void* guidance, long bs, long cs, const void* d0, cons
         g.hyw = Se - 1; g.hxw = round_up4(Se - 1);
         g.wq = (g.tw + 2 * g.hxw) / 4; g.wr = g.th + 2 * g.hyw;
         g.dr = g.wr + 2;
+        set_uniform_rows(&g);
         g.threads = rp.threads == 1024 ? 1024 : RES_THREADS;
         g.nq = g.wq > 0 && g.wq <= g.threads ? ceil_div(g.wr, g.threads / g.wq) : RES_MAX_NQ + 1;
         if (g.threads == 1024 && g.nq > 1) g.nq = RES_MAX_NQ + 1;
@@ -1256,8 +1385,8 @@ int resident_launch(const void* guidance, long bs, long cs, const void* d0, cons
     a.s_in = s_in;
     a.seq = seq;
     a.target = static_cast<const float*>(target); a.macc = acc; a.nslots = nslots;
-    a.B = B; a.H = H; a.W = W; a.Wv = (W_valid > 0 && W_valid < W) ? W_valid : W; a.T = T; a.S = g.S;
-    a.tw = g.tw; a.th = g.th; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y;
+    a.B = B; a.H = H; a.W = W; a.Wv = Wv; a.T = T; a.S = g.S;
+    a.tw = g.tw; a.th = g.th; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.th0 = g.th0; a.thl = g.thl;
     a.wq = g.wq; a.wr = g.wr; a.hxw = g.hxw; a.hyw = g.hyw; a.dr = g.dr; a.ls = g.ls;
     a.spin_limit = rp.spin_limit ? rp.spin_limit : (4u << 20);   // x (sc1 load + s_sleep) ~ seconds
     a.dbg = rp.debug_stamps;
@@ -1277,6 +1406,11 @@ int resident_launch(const void* guidance, long bs, long cs, const void* d0, cons
         a.last_chunk = (b0 + ipl * max_rounds >= B) ? 1 : 0;
         const int grid = rounds * a.nb * g.tiles_x * g.tiles_y;
         int ok = 0;
+        if (g.threads == RES_THREADS_CLIPPED) {
+            if (!clean) return fail("cspn3_forward_resident: a clipped plan whose regions leave the image");
+            if (!launch_resident_768(a, grid, g.lds_bytes, blend, mode, st)) return 0;
+            continue;
+        }
         if (g.threads == 1024) {
             ok = clean ? launch_resident_1024<1>(a, grid, g.lds_bytes, blend, mode, st) : launch_resident_1024<0>(a, grid, g.lds_bytes, blend, mode, st);
             if (!ok) return 0;

@@ -588,7 +588,8 @@ def set_resident(mode):
 
 def resident_plan(B, H, W, T, blend=0, n_cu=0, steps_per_phase=0, threads=0):
     """The tiling cspn3_forward_resident would use (dict), or None when the shape has none (W % 4 != 0, T < 1, ...).
-    threads: 0 / 512 = the 512-thread workgroups, 1024 = one quad per thread on 1024 threads (inference forms only)."""
+    threads: 0 / 512 = the 512-thread workgroups, 1024 = one quad per thread on 1024 threads (inference forms only), 768 = three
+    quads per thread on regions clipped to the image (inference forms only; `tile_h` is then the FIRST tile row's height)."""
     rp = _lib.cspn_resident_plan()
     rp.steps_per_phase = int(steps_per_phase)
     rp.threads = int(threads)
@@ -860,6 +861,33 @@ def _resident_plan_cached(B, H, W, T, blend, dev):
             _RES_PLAN_CACHE.clear()
         hit = _RES_PLAN_CACHE[key] = (rp, cp)
     return hit
+
+
+_RES_SCORED_PLAN_CACHE = {}      # (id of the default ctypes plan, B, H, W, T, blend) -> ctypes plan of the scored call
+_CLIPPED_SCORED = os.environ.get("CSPN_RESIDENT_CLIPPED", "1") != "0"      # A/B switch: "0" keeps the scored calls on the default plan
+
+
+def _scored_plan(cp, B, H, W, T, blend, dev):
+    """The plan of a scored inference call whose default plan is `cp`: the clipped 768-thread plan (three wavefronts per SIMD) where
+    it does less work per SIMD than the default — one launch either way, and a default of more than 3 quads per thread, i.e.
+    tiles whose halo the image edge makes partly unnecessary; config 2 is the measured case (profiles/r07_clipped_ab.txt).  Shards
+    and multi-launch batches (NYU B = 3, KITTI B = 1 / 8) keep `cp`."""
+    if cp is None or not _CLIPPED_SCORED or cp.launches != 1 or cp.quads_per_thread <= 3 or cp.threads != 512:
+        return cp
+    key = (id(cp), B, H, W, T, blend)
+    hit = _RES_SCORED_PLAN_CACHE.get(key)
+    if hit is None or hit[0] is not cp:
+        rp = resident_plan(B, H, W, T, blend, _resident_state(dev)["n_cu"], threads=768)
+        c2 = cp
+        if rp is not None and rp["launches"] == 1 and rp["steps_per_phase"] == cp.steps_per_phase:
+            c2 = _lib.cspn_resident_plan()
+            for name, _ in _lib.cspn_resident_plan._fields_:
+                if name != "debug_stamps":
+                    setattr(c2, name, rp[name])
+        if len(_RES_SCORED_PLAN_CACHE) > 256:
+            _RES_SCORED_PLAN_CACHE.clear()
+        hit = _RES_SCORED_PLAN_CACHE[key] = (cp, c2)
+    return hit[1]
 
 
 def resident_pays(B, H, W, T, blend, dev):
@@ -1221,7 +1249,10 @@ def forward_resident(guidance, d0, sparse, T, blend, score=None, valid_w=0, step
         rp.guard = guard
     else:
         # found once per shape: the C side skips its search
-        rp = _with_spin_limit(_resident_plan_cached(B, H, W, int(T), int(blend), dev)[1], guard=guard)
+        cp = _resident_plan_cached(B, H, W, int(T), int(blend), dev)[1]
+        if score is not None and not keep_history and not valid_w:
+            cp = _scored_plan(cp, B, H, W, int(T), int(blend), dev)
+        rp = _with_spin_limit(cp, guard=guard)
     def launch(work, seq, host_err_ptr, stream_ptr):
         return L.cspn3_forward_resident(_p(guidance), guidance.stride(0), guidance.stride(1), _p(d0), _p(sparse), _p(out),
                                         _p(hist), _p(w8), _p(S_out), _p(work), seq, host_err_ptr, B, H, W, int(valid_w),
@@ -1895,7 +1926,8 @@ def cspn3_refine_and_score(guidance, blur_depth, sparse_depth, target, acc, prop
             if key is not None and not pad and blur_depth.dim() == 4 and target.dim() == 4 and (sparse_depth is None or sparse_depth.dim() == 4):
                 if len(_SCORED_FAST) > 256:
                     _SCORED_FAST.clear()
-                _SCORED_FAST[key] = _ScoredFast(_resident_plan_cached(B, H, W, int(prop_time), int(blend), guidance.device)[1], guidance,
+                _SCORED_FAST[key] = _ScoredFast(_scored_plan(_resident_plan_cached(B, H, W, int(prop_time), int(blend), guidance.device)[1],
+                                                             B, H, W, int(prop_time), int(blend), guidance.device), guidance,
                                                 prop_time, blend, acc)
             return out.unsqueeze(1)[..., :W0]
         if (_FROM_GUIDANCE and from_guidance_supported(guidance, d0, sp, plan) and guidance.dtype == d0.dtype

@@ -300,9 +300,13 @@ typedef struct cspn_resident_plan {
     int steps_per_phase;   /* in: 0 = choose (12, 8, 6 or 4); out: the value used.  Even whenever T needs more  */
                            /* than one phase (an odd request then has no plan); any value <= T otherwise   */
     int tiles_x, tiles_y;  /* tiles per image                                                             */
-    int tile_w, tile_h;
+    int tile_w, tile_h;              /* tile_h: the tile rows' height; in a threads = 768 plan (cspn3_*) the height of the FIRST tile row: with S - 1 = the
+                                      * halo depth of the plan's phases, the rows in between are tile_h - (S - 1) high and the last row takes the rest
+                                      * of the image (at most tile_h), so that every tile's region (tile +- halo, cut to the image) is equally high */
     int quads_per_thread, threads;   /* threads, cspn3_*: in 0 / 512 = 512-thread workgroups (all forms), 1024 = one quad per thread on 1024
-                                      * threads, four wavefronts per SIMD (inference forms only; small shards, round 5); out: the value used */
+                                      * threads, four wavefronts per SIMD (inference forms only; small shards, round 5), 768 = three quads per thread on regions
+                                      * clipped to the image, three wavefronts per SIMD (plain / scored inference on unpadded rows only: every other call
+                                      * with such a plan runs the 512-thread plan of the same phase length); out: the value used */
     int images_per_launch, launches;   /* images in flight at a time; launches of that many images (the K = 5 reverse sweep: rounds of ONE launch) */
     int lds_bytes, n_cu;
     float region_over_tile; /* (tile + halo) area / tile area: the redundant-compute factor of the phases  */

@@ -5,9 +5,9 @@ Host side (Python, PyTorch-ROCm for memory/streams/autograd) over a C-ABI HIP li
 dontLoveBugs/CSPN_monodepth only; see DESIGN.md.
 """
 from . import _lib, base, criterion, evaluation, functional, graphs, network, post_process
-from .functional import (cspn3_affinity_propagate, pac_affinity_propagate, set_default_plan)
-from .post_process import CSPN_new, CSPN_ours
+from .functional import (cspn3_affinity_propagate, cspn_max8_propagate, pac_affinity_propagate, set_default_plan)
+from .post_process import CSPN, CSPN_new, CSPN_ours
 
-__all__ = ["_lib", "base", "criterion", "evaluation", "functional", "graphs", "network", "post_process", "CSPN_new", "CSPN_ours",
-           "cspn3_affinity_propagate", "pac_affinity_propagate", "set_default_plan"]
+__all__ = ["_lib", "base", "criterion", "evaluation", "functional", "graphs", "network", "post_process", "CSPN", "CSPN_new", "CSPN_ours",
+           "cspn3_affinity_propagate", "cspn_max8_propagate", "pac_affinity_propagate", "set_default_plan"]
 __version__ = "0.1.0"

@@ -2024,3 +2024,94 @@ def pac_affinity_propagate(x, guided, sparse_depth=None, prop_time=24, plan=None
     else:
         out = PACFunction.apply(x, guided, sparse_depth, int(prop_time), plan, state_dtype, vw)
     return out[..., :W] if pad else out
+
+
+# ------------------------------------------------------------------------------------------------ max-of-8 (the original CSPN.py)
+def max8_workspace(B, H, W, T, keep_history, device):
+    """`work` of one cspn_max8 call, fresh from torch's caching allocator (no synchronisation, also inside a graph capture)."""
+    nbytes = _lib.lib().cspn_max8_workspace_bytes(B, H, W, T, 1 if keep_history else 0)
+    return torch.empty((nbytes // 4,), dtype=torch.float32, device=device)
+
+
+def _max8_guidance(guidance):
+    """The guidance as the engine reads it — arbitrary batch and channel strides, rows contiguous — without a copy when it can."""
+    H, W = guidance.shape[2], guidance.shape[3]
+    if guidance.stride(3) != 1 or guidance.stride(2) != W or guidance.stride(0) < 0 or guidance.stride(1) < 0 or guidance.data_ptr() & 3:
+        guidance = guidance[:, :8].contiguous()
+    return guidance
+
+
+class Max8Function(torch.autograd.Function):
+    """network/libs/post_process/CSPN.py's recurrence: cspn_max8_forward / cspn_max8_backward (include/cspn_max8.h)."""
+
+    @staticmethod
+    def forward(ctx, guidance, blur_depth, sparse_depth, prop_time, steps_per_launch):
+        B, C, H, W = guidance.shape
+        dev = guidance.device
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        g = _max8_guidance(guidance)
+        d0 = _plane(blur_depth, B, H, W, "blur_depth")
+        sp = _plane(sparse_depth, B, H, W, "sparse_depth")
+        out = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        hist = mask = None
+        if need_grad:
+            hist = torch.empty((prop_time, B, H, W), dtype=torch.float32, device=dev)
+            mask = torch.empty((prop_time, B, H, W), dtype=torch.uint8, device=dev)
+        work = max8_workspace(B, H, W, prop_time, False, dev)
+        with _device_guard(dev):
+            ok = _lib.lib().cspn_max8_forward(_p(g), g.stride(0), g.stride(1), _p(d0), _p(sp), _p(out), _p(hist), _p(mask), _p(work),
+                                         B, H, W, prop_time, steps_per_launch, _stream(dev))
+        _lib.check(ok, "cspn_max8_forward")
+        if need_grad:
+            ctx.save_for_backward(g, d0, sp, hist, mask)
+            ctx.dims = (B, C, H, W, prop_time)
+            ctx.blur_shape = tuple(blur_depth.shape)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        g, d0, sp, hist, mask = ctx.saved_tensors
+        B, C, H, W, T = ctx.dims
+        dev = g.device
+        go = grad_out
+        if go.dtype != torch.float32:
+            go = go.float()
+        go = go.contiguous()
+        grad_g = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+        grad_b = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        work = max8_workspace(B, H, W, T, True, dev)
+        with _device_guard(dev):
+            ok = _lib.lib().cspn_max8_backward(_p(g), g.stride(0), g.stride(1), C, _p(d0), _p(sp), _p(hist), _p(mask), _p(go), _p(grad_g),
+                                          _p(grad_b), _p(work), B, H, W, T, _stream(dev))
+        _lib.check(ok, "cspn_max8_backward")
+        return (grad_g if ctx.needs_input_grad[0] else None, grad_b.view(ctx.blur_shape) if ctx.needs_input_grad[1] else None,
+                None, None, None)
+
+
+def cspn_max8_propagate(guidance, blur_depth, sparse_depth=None, prop_time=16, steps_per_launch=0):
+    """Functional form of CSPN.AffinityPropagate.forward (network/libs/post_process/CSPN.py:20-55) and, with sparse_depth=None,
+    of AffinityPropagate_prediction.forward (:132-163): eight |guidance| gates as box-normalised 3x3 filters on the depth, their
+    element-wise maximum, the sparse blend — prop_time times.  guidance [B,C>=8,H,W] (channels 0..7 read, any batch / channel
+    stride), blur_depth / sparse_depth [B,1,H,W]; fp32 only.  Gradients for guidance and blur_depth.  steps_per_launch: 0 = the
+    engine's choice, 1..16 = steps one launch advances (the result's bits do not depend on it)."""
+    dev = _require_device(guidance, blur_depth, sparse_depth)
+    if dev is None:
+        raise RuntimeError("CSPN HIP engine: tensors must live on a ROCm device")
+    if guidance.dim() != 4 or guidance.shape[1] < 8:
+        raise ValueError("guidance must be [B,C>=8,H,W], got %s" % (tuple(guidance.shape),))
+    for name, t in (("guidance", guidance), ("blur_depth", blur_depth), ("sparse_depth", sparse_depth)):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("cspn_max8_propagate: fp32 only (the reference's precision), %s is %s" % (name, t.dtype))
+    prop_time, steps_per_launch = int(prop_time), int(steps_per_launch)
+    if prop_time < 1:
+        raise ValueError("prop_time must be at least 1, got %d" % prop_time)
+    if not 0 <= steps_per_launch <= _lib.MAX8_MAX_STEPS_PER_LAUNCH:
+        raise ValueError("steps_per_launch must be 0 (the engine's choice) or 1..%d, got %d" % (_lib.MAX8_MAX_STEPS_PER_LAUNCH, steps_per_launch))
+    if guidance.numel() == 0:
+        raise ValueError("guidance must be [B,C>=8,H,W], got %s" % (tuple(guidance.shape),))
+    if sparse_depth is not None:
+        sparse_depth = sparse_depth.detach()
+    if not (torch.is_grad_enabled() and (guidance.requires_grad or blur_depth.requires_grad)):
+        return Max8Function.forward(_NoGradCtx, guidance, blur_depth, sparse_depth, prop_time, steps_per_launch)
+    return Max8Function.apply(guidance, blur_depth, sparse_depth, prop_time, steps_per_launch)

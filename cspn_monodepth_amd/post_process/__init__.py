@@ -1,5 +1,5 @@
-"""Mirror of the reference package network/libs/post_process (CSPN_new, CSPN_ours)."""
-from . import CSPN_new, CSPN_ours
+"""Mirror of the reference package network/libs/post_process (CSPN, CSPN_new, CSPN_ours)."""
+from . import CSPN, CSPN_new, CSPN_ours
 from .CSPN_new import AffinityPropagate
 
-__all__ = ["CSPN_new", "CSPN_ours", "AffinityPropagate"]
+__all__ = ["CSPN", "CSPN_new", "CSPN_ours", "AffinityPropagate"]

@@ -4,10 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
 
 #include "cspn_hip.h"
@@ -38,11 +40,24 @@ int pac_s2_grad_kernel(const void* gout, const void* in, void* gk, int dtype, in
 // cspn_repair.hip: the guard behind a plain resident inference launch (cspn_resident_plan.guard): re-computes the call's result
 // on the stream when — and only when — its launches gave up (abort word == seq)
 bool resident_repair_fits(int T);
+// The form of a 3x3 resident launch: which instance of cspn3_resident runs it (cspn_resident.hip) and which instance of the guard
+// re-computes it (cspn_repair.hip).  Both kernels take it as the template arguments MODE (resident_form_mode) and PAC (resident_form_pac:
+// the softmax weights of CSPN_ours at K = 3).
+enum class ResidentForm : int {
+    Inference,             // refined depth -> out
+    Scored,                // ... + the fused depth metrics
+    Training,              // the training forward: every step's state -> history, the weights and / or S published
+    SweepVolume,           // the backward's reverse sweep on a tap volume
+    SweepGuidance,         // ... on taps rebuilt from the raw guidance + S
+    SoftmaxInference, SoftmaxScored, SoftmaxTraining,      // the first three with softmax weights
+    Count
+};
+constexpr int resident_form_pac(ResidentForm f) { return f >= ResidentForm::SoftmaxInference ? 1 : 0; }
+constexpr int resident_form_mode(ResidentForm f) { return (int)f - (resident_form_pac(f) ? (int)ResidentForm::SoftmaxInference : 0); }
+constexpr bool resident_form_guarded(ResidentForm f) { return f != ResidentForm::SoftmaxScored; }     // the forms the guard re-computes
 int resident_repair_launch(const float* g, long bs, long cs, const float* d0, const float* sparse, float* out, float* hist, float* s_out,
-                           float* w_out, const float* s_in, int mode, const unsigned* abort_word, unsigned seq, int B, int H, int W, int Wv,
+                           float* w_out, const float* s_in, ResidentForm form, const unsigned* abort_word, unsigned seq, int B, int H, int W, int Wv,
                            int T, int blend, int n_cu, void* stream, const float* target = nullptr, double* acc = nullptr, int nslots = 0);
-                           // mode 0: inference, 1: inference + fused metrics, 2: training forward, 3 / 4: reverse sweep from a tap volume / from
-                                                                                 // guidance + S, 10 / 12: softmax-weight (CSPN_ours K = 3) inference / training forward
 // ... and of cspnk_forward_resident's unscored inference calls (round_every: the steps between two roundings of the state to the plane dtype;
 // step_form: CSPN_STEP_FMA or CSPN_STEP_DOT2, the form the guarded launch ran — its arithmetic is the one re-computed)
 bool kres_repair_fits(int K, int T);
@@ -76,6 +91,10 @@ void lds_poison(hipStream_t st);
 namespace {
 
 using cspn_detail::fail;
+using cspn_detail::ResidentForm;
+using cspn_detail::resident_form_guarded;
+using cspn_detail::resident_form_mode;
+using cspn_detail::resident_form_pac;
 
 #define HIP_OK(expr)                                                                  \
     do {                                                                              \
@@ -395,5 +414,77 @@ int grid_for(size_t n, int block) {
     return (int)g;
 }
 
+// Launches with more than 64 KiB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised once per
+// (kernel instance, device); the granted size is remembered so the hot loop does not repeat the driver call.
+template <auto Kern>
+int ensure_dynamic_lds(size_t bytes) {
+    static std::atomic<size_t> granted[64];
+    int dev = 0;
+    HIP_OK(hipGetDevice(&dev));
+    std::atomic<size_t>& slot = granted[dev & 63];
+    if (slot.load(std::memory_order_acquire) >= bytes) return 1;
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    size_t seen = slot.load(std::memory_order_relaxed);
+    while (seen < bytes && !slot.compare_exchange_weak(seen, bytes, std::memory_order_release)) {}
+    return 1;
+}
+// ... and the launch behind it (through the library's hipLaunchKernelGGL: the poisoned-LDS hook runs).  Its address is what the
+// tables of instances hold where the kernel is chosen at run time.
+template <auto Kern, typename Args>
+int launch_dynamic_lds(int grid, int threads, size_t lds_bytes, hipStream_t st, const Args& a) {
+    if (lds_bytes > 64 * 1024 && !ensure_dynamic_lds<Kern>(lds_bytes)) return 0;
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(threads), lds_bytes, st, a);
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// what the weight-resident engines (cspn_resident.hip, cspnk_resident.hip) share on the host
+// ------------------------------------------------------------------------------------------------
+// Workspace of a resident call: 2 exchange planes of B x H x W elements, then — at a fixed place, whatever the tiling — 4 status
+// words (abort, error, 2 reserved), then one phase flag per tile (a tile has at least `min_tile_pixels` pixels).
+inline size_t resident_planes_bytes(int B, int H, int W, size_t elem_size) { return ((size_t)2 * B * H * W * elem_size + 15) & ~(size_t)15; }
+inline size_t resident_workspace_bytes(int B, int H, int W, size_t elem_size, int min_tile_pixels) {
+    const size_t flags = ((size_t)B * (((size_t)H * W) / min_tile_pixels + 1) + 4) * sizeof(unsigned);
+    return resident_planes_bytes(B, H, W, elem_size) + ((flags + 15) & ~(size_t)15);
+}
+inline unsigned* resident_status_words(void* work, int B, int H, int W, size_t elem_size) {
+    return reinterpret_cast<unsigned*>(static_cast<char*>(work) + resident_planes_bytes(B, H, W, elem_size));
+}
+inline unsigned* resident_phase_flags(unsigned* status) { return status + 4; }
+
+// does the plan carry a tiling (one that came out of cspn3_resident_plan / cspnk_resident_plan: the launch then skips its search)?
+inline bool plan_has_tiling(const cspn_resident_plan& rp) {
+    return rp.tiles_x > 0 && rp.tiles_y > 0 && rp.tile_w > 0 && rp.tile_h > 0 && rp.steps_per_phase > 0 && rp.images_per_launch > 0;
+}
+inline unsigned plan_spin_limit(const cspn_resident_plan& rp) { return rp.spin_limit ? rp.spin_limit : (4u << 20); }   // x (sc1 load + s_sleep) ~ seconds
+
+// Argument rules of the resident entry points; `who` is the entry point's name.  (A null pointer counts as aligned: whether a tensor
+// may be absent is the entry point's own rule.)
+inline bool all_aligned16(std::initializer_list<const void*> ps) {
+    for (const void* p : ps)
+        if (!aligned16(p)) return false;
+    return true;
+}
+inline int check_tensors_aligned16(const char* who, std::initializer_list<const void*> ps) {
+    return all_aligned16(ps) ? 1 : fail("%s: tensors must be 16-byte aligned", who);
+}
+inline int check_blend(const char* who, int blend, const void* sparse) {
+    if (blend != CSPN_BLEND_NONE && blend != CSPN_BLEND_SPARSE) return fail("%s: blend %d", who, blend);
+    if (blend && !sparse) return fail("%s: blend needs sparse", who);
+    return 1;
+}
+inline int check_premask(const char* who, int premask, const void* sparse) {
+    return premask && !sparse ? fail("%s: premask needs sparse", who) : 1;
+}
+inline int check_scoring(const char* who, const void* target, const void* acc, int nslots) {
+    if ((target || acc) && (!target || !acc || nslots < 1 || !aligned16(target)))
+        return fail("%s: scoring needs target (16-byte aligned), acc and nslots >= 1", who);
+    return 1;
+}
+// a tile that finished phase p publishes seq + p + 1, and the next call on the workspace brings seq + 256
+inline int check_seq(const char* who, unsigned seq) {
+    return seq == 0 || seq > 0x7fffff00u ? fail("%s: seq must be in [1, 2^31 - 256]", who) : 1;
+}
 
 }  // namespace

@@ -16,7 +16,8 @@
 #include "cspn_common.hpp"
 #include "cspnk_helpers.hpp"      // the dot-product form's arithmetic (shared with cspnk_d2.hip: the same code, the same bits)
 
-#include <atomic>
+#include <array>
+#include <utility>
 
 namespace {
 
@@ -514,49 +515,36 @@ namespace cspn_detail {
 
 bool resident_repair_fits(int T) { return T >= 1 && (size_t)2 * (REP_TILE + 2 * T) * (REP_TILE + 2 * T) * sizeof(float) <= 160 * 1024; }
 
+// A few workgroups that loop over the tiles: the success path — every launch of a healthy deployment — is `grid` workgroups
+// that read one word and return, and its cost is their dispatch (rocprofv3, config 2's training step: 5.1 us with one workgroup
+// per CU and 51 KB of LDS each; n_cu / 8 of them — 32 on an MI355X — keep the failure path at tens of milliseconds)
+static int guard_grid(int n_tiles, int n_cu) {
+    const int cap = n_cu >= 64 ? n_cu / 8 : 8;
+    return n_tiles > cap ? cap : n_tiles;
+}
+
+// the guard's instance per (blend, form); null where it has none (resident_form_guarded)
+using RepLaunchFn = int (*)(int, int, size_t, hipStream_t, const RepArgs&);
+template <int BLEND, int F>
+constexpr RepLaunchFn rep_instance() {
+    constexpr ResidentForm f = static_cast<ResidentForm>(F);
+    if constexpr (resident_form_guarded(f)) return &launch_dynamic_lds<cspn3_resident_repair<BLEND, resident_form_mode(f), resident_form_pac(f)>, RepArgs>;
+    else return nullptr;
+}
+template <int BLEND, int... F>
+constexpr std::array<RepLaunchFn, sizeof...(F)> rep_instances(std::integer_sequence<int, F...>) { return {rep_instance<BLEND, F>()...}; }
+
 int resident_repair_launch(const float* g, long bs, long cs, const float* d0, const float* sparse, float* out, float* hist, float* s_out,
-                           float* w_out, const float* s_in, int mode, const unsigned* abort_word, unsigned seq, int B, int H, int W, int Wv,
+                           float* w_out, const float* s_in, ResidentForm form, const unsigned* abort_word, unsigned seq, int B, int H, int W, int Wv,
                            int T, int blend, int n_cu, void* stream, const float* target, double* acc, int nslots) {
+    constexpr auto forms = std::make_integer_sequence<int, (int)ResidentForm::Count>{};
+    static constexpr std::array<RepLaunchFn, (size_t)ResidentForm::Count> instances[2] = {rep_instances<0>(forms), rep_instances<1>(forms)};
     if (!resident_repair_fits(T)) return fail("cspn3_forward_resident: the guard re-computes at most 54 steps (T=%d)", T);
-    if (mode != 0 && mode != 1 && mode != 2 && mode != 3 && mode != 4 && mode != 10 && mode != 12) return fail("cspn3_forward_resident: the guard has no form for this launch");
+    const RepLaunchFn launch = form < ResidentForm::Count ? instances[blend ? 1 : 0][(int)form] : nullptr;
+    if (!launch) return fail("cspn3_forward_resident: the guard has no form for this launch");
     RepArgs a{g, bs, cs, d0, sparse, out, hist, s_out, w_out, s_in, target, acc, nslots > 0 ? nslots : 1, abort_word, seq, B, H, W, Wv, T, ceil_div(W, REP_TILE), ceil_div(H, REP_TILE)};
     const size_t lds = (size_t)2 * (REP_TILE + 2 * T) * (REP_TILE + 2 * T) * sizeof(float);
-    static std::atomic<size_t> granted[14][64];
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    // slots: (inference, training forward, sweep from guidance + S, sweep from a tap volume, softmax inference, softmax training forward) x blend
-    const int form = mode == 0 ? 0 : mode == 2 ? 1 : mode == 4 ? 2 : mode == 3 ? 3 : mode == 10 ? 4 : mode == 12 ? 5 : 6;
-    const int slot = 2 * form + (blend ? 1 : 0);
-    void (*kern)(RepArgs) = nullptr;
-    switch (slot) {
-        case 0: kern = cspn3_resident_repair<0, 0, 0>; break;
-        case 1: kern = cspn3_resident_repair<1, 0, 0>; break;
-        case 2: kern = cspn3_resident_repair<0, 2, 0>; break;
-        case 3: kern = cspn3_resident_repair<1, 2, 0>; break;
-        case 4: kern = cspn3_resident_repair<0, 4, 0>; break;
-        case 5: kern = cspn3_resident_repair<1, 4, 0>; break;
-        case 6: kern = cspn3_resident_repair<0, 3, 0>; break;
-        case 7: kern = cspn3_resident_repair<1, 3, 0>; break;
-        case 8: kern = cspn3_resident_repair<0, 0, 1>; break;
-        case 9: kern = cspn3_resident_repair<1, 0, 1>; break;
-        case 10: kern = cspn3_resident_repair<0, 2, 1>; break;
-        case 11: kern = cspn3_resident_repair<1, 2, 1>; break;
-        case 12: kern = cspn3_resident_repair<0, 1, 0>; break;
-        default: kern = cspn3_resident_repair<1, 1, 0>; break;
-    }
-    if (lds > 64 * 1024 && granted[slot][dev & 63].load(std::memory_order_acquire) < lds) {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        granted[slot][dev & 63].store(lds, std::memory_order_release);
-    }
-    // a few workgroups that loop over the tiles: the success path — every launch of a healthy deployment — is `grid` workgroups
-    // that read one word and return, and its cost is their dispatch (rocprofv3, config 2's training step: 5.1 us with one workgroup
-    // per CU and 51 KB of LDS each; n_cu / 8 of them — 32 on an MI355X — keep the failure path at tens of milliseconds)
-    int grid = B * a.tiles_x * a.tiles_y;
-    const int cap = n_cu >= 64 ? n_cu / 8 : 8;
-    if (grid > cap) grid = cap;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(REP_THREADS), lds, static_cast<hipStream_t>(stream), a);
-    HIP_OK(hipGetLastError());
-    return 1;
+    return launch(guard_grid(B * a.tiles_x * a.tiles_y, n_cu), REP_THREADS, lds, static_cast<hipStream_t>(stream), a);
 }
 
 
@@ -567,17 +555,8 @@ bool kres_repair_fits(int K, int T) {
 
 template <int K, typename GT, typename ST, int D2 = 0>
 static int kres_repair_launch_t(const KRepArgs& a, int blend, size_t lds, int grid, hipStream_t st) {
-    static std::atomic<size_t> granted[2][64];
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    void (*kern)(KRepArgs) = blend ? cspnk_resident_repair<K, GT, ST, 1, D2> : cspnk_resident_repair<K, GT, ST, 0, D2>;
-    if (lds > 64 * 1024 && granted[blend ? 1 : 0][dev & 63].load(std::memory_order_acquire) < lds) {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        granted[blend ? 1 : 0][dev & 63].store(lds, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(REP_THREADS), lds, st, a);
-    HIP_OK(hipGetLastError());
-    return 1;
+    return blend ? launch_dynamic_lds<cspnk_resident_repair<K, GT, ST, 1, D2>>(grid, REP_THREADS, lds, st, a)
+                 : launch_dynamic_lds<cspnk_resident_repair<K, GT, ST, 0, D2>>(grid, REP_THREADS, lds, st, a);
 }
 
 int kres_repair_launch(const void* g, int g_dtype, int K, const void* x0, const void* sparse, void* out, int state_dtype,
@@ -588,9 +567,7 @@ int kres_repair_launch(const void* g, int g_dtype, int K, const void* x0, const 
     KRepArgs a{g, x0, sparse, out, abort_word, seq, B, H, W, T, round_every > 0 ? round_every : T, ceil_div(W, REP_TILE), ceil_div(H, REP_TILE)};
     const int R = REP_TILE + 2 * T * (K / 2);
     const size_t lds = (size_t)2 * R * R * sizeof(float);
-    int grid = B * a.tiles_x * a.tiles_y;
-    const int cap = n_cu >= 64 ? n_cu / 8 : 8;
-    if (grid > cap) grid = cap;
+    const int grid = guard_grid(B * a.tiles_x * a.tiles_y, n_cu);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool gh = g_dtype == CSPN_F16, sh = state_dtype == CSPN_F16;
     if (!gh && sh) return fail("cspnk_forward_resident: fp32 guidance with fp16 planes has no kernel");
@@ -605,28 +582,16 @@ int kres_repair_launch(const void* g, int g_dtype, int K, const void* x0, const 
     return kres_repair_launch_t<5, float, float>(a, blend, lds, grid, st);
 }
 
-template <typename KernT, typename ArgsT>
-static int guarded_launch(KernT kern, std::atomic<size_t>* granted, const ArgsT& a, size_t lds, int n_tiles, int n_cu, hipStream_t st) {
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    if (lds > 64 * 1024 && granted[dev & 63].load(std::memory_order_acquire) < lds) {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        granted[dev & 63].store(lds, std::memory_order_release);
-    }
-    const int cap = n_cu >= 64 ? n_cu / 8 : 8;
-    hipLaunchKernelGGL(kern, dim3(n_tiles > cap ? cap : n_tiles), dim3(REP_THREADS), lds, st, a);
-    HIP_OK(hipGetLastError());
-    return 1;
-}
-
 int kres_history_repair_launch(const void* g, const void* x0, const void* sparse, void* hist, void* wk_out, const unsigned* abort_word, unsigned seq,
                                int B, int H, int W, int T, int blend, int n_cu, void* stream) {
     if (!kres_repair_fits(5, T)) return fail("cspnk_forward_resident_history: the guard re-computes at most 27 steps of a 5 x 5 stencil (T=%d)", T);
     KHistRepArgs a{g, x0, sparse, hist, wk_out, abort_word, seq, B, H, W, T, ceil_div(W, REP_TILE), ceil_div(H, REP_TILE)};
     const int R = REP_TILE + 4 * T;
-    static std::atomic<size_t> granted[2][64];
-    if (blend) return guarded_launch(cspnk_history_repair<5, __half, __half, 1>, granted[1], a, (size_t)2 * R * R * sizeof(float), B * a.tiles_x * a.tiles_y, n_cu, static_cast<hipStream_t>(stream));
-    return guarded_launch(cspnk_history_repair<5, __half, __half, 0>, granted[0], a, (size_t)2 * R * R * sizeof(float), B * a.tiles_x * a.tiles_y, n_cu, static_cast<hipStream_t>(stream));
+    const size_t lds = (size_t)2 * R * R * sizeof(float);
+    const int grid = guard_grid(B * a.tiles_x * a.tiles_y, n_cu);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return blend ? launch_dynamic_lds<cspnk_history_repair<5, __half, __half, 1>>(grid, REP_THREADS, lds, st, a)
+                 : launch_dynamic_lds<cspnk_history_repair<5, __half, __half, 0>>(grid, REP_THREADS, lds, st, a);
 }
 
 int kres_sweep_repair_launch(const void* wk, const void* g_T, const void* sparse, int in_dtype, float* g32_out, float* hist, const unsigned* abort_word,
@@ -635,14 +600,13 @@ int kres_sweep_repair_launch(const void* wk, const void* g_T, const void* sparse
     KSweepRepArgs a{wk, g_T, sparse, g32_out, hist, abort_word, seq, B, H, W, T, ceil_div(W, REP_TILE), ceil_div(H, REP_TILE)};
     const int R = REP_TILE + 4 * T;
     const size_t lds = (size_t)2 * R * R * sizeof(float);
-    const int n = B * a.tiles_x * a.tiles_y;
+    const int grid = guard_grid(B * a.tiles_x * a.tiles_y, n_cu);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    static std::atomic<size_t> granted[4][64];
     if (in_dtype == CSPN_F16)
-        return premask ? guarded_launch(cspnk_sweep_repair<5, __half, __half, 1>, granted[0], a, lds, n, n_cu, st)
-                       : guarded_launch(cspnk_sweep_repair<5, __half, __half, 0>, granted[1], a, lds, n, n_cu, st);
-    return premask ? guarded_launch(cspnk_sweep_repair<5, __half, float, 1>, granted[2], a, lds, n, n_cu, st)
-                   : guarded_launch(cspnk_sweep_repair<5, __half, float, 0>, granted[3], a, lds, n, n_cu, st);
+        return premask ? launch_dynamic_lds<cspnk_sweep_repair<5, __half, __half, 1>>(grid, REP_THREADS, lds, st, a)
+                       : launch_dynamic_lds<cspnk_sweep_repair<5, __half, __half, 0>>(grid, REP_THREADS, lds, st, a);
+    return premask ? launch_dynamic_lds<cspnk_sweep_repair<5, __half, float, 1>>(grid, REP_THREADS, lds, st, a)
+                   : launch_dynamic_lds<cspnk_sweep_repair<5, __half, float, 0>>(grid, REP_THREADS, lds, st, a);
 }
 
 }  // namespace cspn_detail

@@ -36,7 +36,8 @@
 //   * v_pk_fma_f32 does not help: it issues at half the rate of v_fma_f32 here (tools/probes/pk_fma_probe.hip).
 #include "cspn_common.hpp"
 
-#include <atomic>
+#include <array>
+#include <utility>
 
 namespace {
 
@@ -1108,115 +1109,110 @@ bool resident_geometry_clipped(int B, int H, int W, int T, int blend, int ncu, i
     return found;
 }
 
+// The geometry of `tiles_x` x `tiles_y` tiles of tw x th pixels with uniform rows, on 512 threads (up to RES_MAX_NQ quads per thread) or
+// 1024 (one quad per thread: 128 VGPRs hold one quad's weights): fills the dependent fields of *g (not imgs_per_launch / launches /
+// cost); false when that is no valid tiling.  The one statement of the feasibility rules: the search calls it per candidate, the
+// launch with the tiling of a plan.  (The two used to carry a copy each.  They agreed except that the plan's copy also asked for
+// tw % 4 == 0 and for tiles that cover the image — both hold for every candidate the search forms, so asking here changes neither
+// the plans the search returns nor the plans the launch accepts.)
+bool rgeom_fill(int H, int W, int T, int Se, int tiles_x, int tiles_y, int tw, int th, int threads, int blend, ResGeom* g) {
+    if (tiles_x < 1 || tiles_y < 1 || tw < 4 || (tw & 3) || th < 1 || Se < 1) return false;
+    const int hyw = Se - 1, hxw = round_up4(Se - 1), phases = ceil_div(T, Se);
+    if (phases > 1 && (Se & 1)) return false;          // every phase must start in buffer 0 (see RES_PP)
+    if (tiles_x * tw < W || tiles_y * th < H) return false;
+    // the (shifted) halo must come from adjacent tiles only
+    if (phases > 1 && ((tiles_x > 1 && tw < 2 * hxw) || (tiles_y > 1 && th < 2 * hyw))) return false;
+    const int wq = (tw + 2 * hxw) / 4, wr = th + 2 * hyw;
+    if (wq > threads) return false;
+    const int nq = ceil_div(wr, threads / wq);            // threads / wq strips per quad column
+    if (nq > (threads == 1024 ? 1 : RES_MAX_NQ)) return false;
+    const int dr = wr + 2, ls = res_row_stride(wq, nq, dr);
+    if ((size_t)dr * ls > (size_t)RES_PP) return false;                      // one depth buffer per RES_PP slot
+    const size_t ldsb = res_lds_bytes(dr, ls, nq, blend, threads);
+    if (ldsb > 160 * 1024) return false;
+    *g = ResGeom{Se, tiles_x, tiles_y, tw, th, nq, wq, wr, hxw, hyw, dr, ls, 0, 0, ldsb, 0.0};
+    g->threads = threads;
+    set_uniform_rows(g);
+    return true;
+}
+
 // Tiling of one image for the resident kernel: every workgroup owns a tw x th tile + (S-1) halo; a launch holds
 // imgs_per_launch whole images on at most `ncu` workgroups.  Cost model: launches x (quads per thread + latency floor).
 bool resident_geometry(int B, int H, int W, int T, int blend, int ncu, int S_user, ResGeom* best, int threads = RES_THREADS) {
     if (threads == RES_THREADS_CLIPPED) return resident_geometry_clipped(B, H, W, T, blend, ncu, S_user, best);
     if (W % 4 != 0 || ncu < 1 || T < 1) return false;
     if (threads != 1024) threads = RES_THREADS;
-    const int max_nq = threads == 1024 ? 1 : RES_MAX_NQ;       // 1024 threads = 128 VGPRs: one quad's weights per thread
     bool found = false;
     // phase lengths 12 / 8 / 6 / 4: twelve (one exchange at T = 24) wins on small shards whose tiles stay at two quads per
     // thread (NYU B = 6: 22.2 vs 23.9 us), eight everywhere else (tools/probes/resident_s_sweep.py)
     for (int S = (S_user > 0 ? S_user : 12); S >= (S_user > 0 ? S_user : 4); S -= (S > 8 ? 4 : 2)) {
         const int Se = S > T ? T : S;
-        const int hyw = Se - 1, hxw = round_up4(Se - 1);
         const int phases = ceil_div(T, Se);
-        if (phases > 1 && (Se & 1)) continue;          // every phase must start in buffer 0 (see RES_PP)
         for (int tx = 1; tx <= 32; ++tx) {
             const int tw = round_up4(ceil_div(W, tx));
             if (tx > 1 && (tw < 16 || ceil_div(W, tw) != tx)) continue;
-            if (phases > 1 && tx > 1 && tw < 2 * hxw) continue;                   // the (shifted) halo must come from adjacent tiles only
-            const int wq = (tw + 2 * hxw) / 4;
-            if (wq > threads) continue;
             for (int ty = 1; ty <= 64; ++ty) {
                 const int th = ceil_div(H, ty);
                 if (ty > 1 && (th < 4 || ceil_div(H, th) != ty)) continue;
-                if (phases > 1 && ty > 1 && th < 2 * hyw) continue;
                 const int tiles = tx * ty;
                 if (tiles > ncu) continue;
-                const int wr = th + 2 * hyw;
-                const int rows_per_thread_col = threads / wq;                     // strips per quad column
-                const int nq = ceil_div(wr, rows_per_thread_col);
-                if (nq > max_nq) continue;
-                const int dr = wr + 2, ls = res_row_stride(wq, nq, dr);
-                if ((size_t)dr * ls > (size_t)RES_PP) continue;                      // one depth buffer per RES_PP slot
-                const size_t ldsb = res_lds_bytes(dr, ls, nq, blend, threads);
-                if (ldsb > 160 * 1024) continue;
+                ResGeom cand;
+                if (!rgeom_fill(H, W, T, Se, tx, ty, tw, th, threads, blend, &cand)) continue;
                 int ipl = ncu / tiles;
                 if (ipl > B) ipl = B;
-                const int launches = ceil_div(B, ipl);
-                ResGeom cand{Se, tx, ty, tw, th, nq, wq, wr, hxw, hyw, dr, ls, ipl, launches, ldsb, 0.0};
-                set_uniform_rows(&cand);
+                cand.imgs_per_launch = ipl; cand.launches = ceil_div(B, ipl);
                 // microseconds per launch, fitted on MI355X (profiles/r02_resident_vs_multilaunch.jsonl): launch + epilogue,
                 // derive (~2 us per quad of a thread), T steps (VALU-bound: 0.13 us per quad; x 1.13 with the zero-padding
                 // selects of a launch whose regions stick out of the image), and per phase boundary the publish / wait /
                 // halo staging (3 us + the border bytes)
                 const double pen = regions_inside_image(cand, H, W, W, T) ? 1.0 : 1.13;
-                const double cost = launches * (8.0 + 2.0 * nq + T * (0.13 * nq + 0.1) * pen + (phases - 1) * (3.0 + 0.6 * nq));
-                if (!found || cost < best->cost) {
-                    found = true;
-                    *best = ResGeom{Se, tx, ty, tw, th, nq, wq, wr, hxw, hyw, dr, ls, ipl, launches, ldsb, cost};
-                    best->threads = threads;
-                    set_uniform_rows(best);
-                }
+                cand.cost = cand.launches * (8.0 + 2.0 * cand.nq + T * (0.13 * cand.nq + 0.1) * pen + (phases - 1) * (3.0 + 0.6 * cand.nq));
+                if (!found || cand.cost < best->cost) { found = true; *best = cand; }
             }
         }
     }
     return found;
 }
 
-template <int NQ, int BLEND, int MODE, int CLEAN, int PAC = 0, int NTH = RES_THREADS>
-int launch_resident_inst(const ResArgs& a, int grid, size_t lds_bytes, hipStream_t st) {
-    constexpr auto kern = cspn3_resident<NQ, NTH, BLEND, MODE, CLEAN, PAC>;
-    static std::atomic<size_t> granted[64];
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    if (lds_bytes > 64 * 1024 && granted[dev & 63].load(std::memory_order_acquire) < lds_bytes) {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        granted[dev & 63].store(lds_bytes, std::memory_order_release);
+// The geometry of a launch: the plan's tiling when it carries one — re-derived and re-checked by clipped_geometry / rgeom_fill, the
+// search is skipped (it is ~6000 candidate tilings: tens of microseconds per call on the host) — else the search's.
+int resident_resolve(int B, int H, int W, int T, int blend, int ncu, const cspn_resident_plan& rp, ResGeom* g) {
+    if (!plan_has_tiling(rp)) {
+        if (!resident_geometry(B, H, W, T, blend, ncu, rp.steps_per_phase, g, rp.threads))
+            return fail("cspn3_forward_resident: no resident tiling for B=%d %dx%d T=%d", B, H, W, T);
+        return 1;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NTH), lds_bytes, st, a);
-    HIP_OK(hipGetLastError());
+    const int Se = rp.steps_per_phase > T ? T : rp.steps_per_phase;
+    const bool clipped = rp.threads == RES_THREADS_CLIPPED;       // tile_h is then the FIRST tile row's height, the uneven rows follow from it
+    const bool ok = clipped ? clipped_geometry(H, W, T, Se, rp.tiles_x, rp.tiles_y, rp.tile_w, rp.tile_h, blend, g)
+                            : rgeom_fill(H, W, T, Se, rp.tiles_x, rp.tiles_y, rp.tile_w, rp.tile_h, rp.threads == 1024 ? 1024 : RES_THREADS, blend, g);
+    if (!ok || (long)rp.images_per_launch * g->tiles_x * g->tiles_y > ncu)
+        return fail("cspn3_forward_resident: the %splan does not fit this problem / device (use cspn3_resident_plan)", clipped ? "clipped " : "");
+    g->imgs_per_launch = rp.images_per_launch;
     return 1;
 }
 
-// 1024 threads, one quad per thread: the inference forms only (plain / scored), CSPN_new weights
-template <int CLEAN>
-int launch_resident_1024(const ResArgs& a, int grid, size_t lds, int blend, int mode, hipStream_t st) {
-    if (mode == 0) return blend ? launch_resident_inst<1, 1, 0, CLEAN, 0, 1024>(a, grid, lds, st) : launch_resident_inst<1, 0, 0, CLEAN, 0, 1024>(a, grid, lds, st);
-    if (mode == 1) return blend ? launch_resident_inst<1, 1, 1, CLEAN, 0, 1024>(a, grid, lds, st) : launch_resident_inst<1, 0, 1, CLEAN, 0, 1024>(a, grid, lds, st);
-    return fail("cspn3_forward_resident: 1024-thread workgroups serve the inference forms only");
+// The instances of cspn3_resident.  512 threads: every form, 1 .. RES_MAX_NQ quads per thread.  1024 threads (one quad per thread)
+// and 768 (three quads per thread on clipped regions, CLEAN only): the inference forms — plain / scored — with CSPN_new weights.
+using ResLaunchFn = int (*)(int, int, size_t, hipStream_t, const ResArgs&);
+template <int NQ, int NTH, int CLEAN, int BLEND, int F>
+constexpr ResLaunchFn res_instance() {
+    constexpr ResidentForm f = static_cast<ResidentForm>(F);
+    if constexpr (NTH == RES_THREADS || (f <= ResidentForm::Scored && (NTH == 1024 || CLEAN)))
+        return &launch_dynamic_lds<cspn3_resident<NQ, NTH, BLEND, resident_form_mode(f), CLEAN, resident_form_pac(f)>, ResArgs>;
+    else
+        return nullptr;
 }
-
-// 768 threads, three quads per thread, clipped regions: the inference forms only (plain / scored), CSPN_new weights, CLEAN
-int launch_resident_768(const ResArgs& a, int grid, size_t lds, int blend, int mode, hipStream_t st) {
-    if (mode == 0) return blend ? launch_resident_inst<3, 1, 0, 1, 0, RES_THREADS_CLIPPED>(a, grid, lds, st) : launch_resident_inst<3, 0, 0, 1, 0, RES_THREADS_CLIPPED>(a, grid, lds, st);
-    if (mode == 1) return blend ? launch_resident_inst<3, 1, 1, 1, 0, RES_THREADS_CLIPPED>(a, grid, lds, st) : launch_resident_inst<3, 0, 1, 1, 0, RES_THREADS_CLIPPED>(a, grid, lds, st);
-    return fail("cspn3_forward_resident: 768-thread workgroups serve the inference forms only");
+template <int NQ, int NTH, int CLEAN, int BLEND, int... F>
+constexpr std::array<ResLaunchFn, sizeof...(F)> res_instances(std::integer_sequence<int, F...>) { return {res_instance<NQ, NTH, CLEAN, BLEND, F>()...}; }
+// the instance for (clean, blend, form) at NQ quads per thread on NTH threads, or null
+template <int NQ, int NTH = RES_THREADS>
+ResLaunchFn res_lookup(bool clean, int blend, ResidentForm form) {
+    constexpr auto forms = std::make_integer_sequence<int, (int)ResidentForm::Count>{};
+    static constexpr std::array<ResLaunchFn, (size_t)ResidentForm::Count> table[2][2] = {
+        {res_instances<NQ, NTH, 0, 0>(forms), res_instances<NQ, NTH, 0, 1>(forms)}, {res_instances<NQ, NTH, 1, 0>(forms), res_instances<NQ, NTH, 1, 1>(forms)}};
+    return table[clean ? 1 : 0][blend ? 1 : 0][(int)form];
 }
-
-template <int NQ, int CLEAN>
-int launch_resident_c(const ResArgs& a, int grid, size_t lds, int blend, int mode, hipStream_t st) {
-    if (mode >= 4 && mode <= 6) {          // softmax-weight (PAC) forms of MODE 0 / 1 / 2
-        if (mode == 6) return blend ? launch_resident_inst<NQ, 1, 2, CLEAN, 1>(a, grid, lds, st) : launch_resident_inst<NQ, 0, 2, CLEAN, 1>(a, grid, lds, st);
-        if (blend) return mode == 5 ? launch_resident_inst<NQ, 1, 1, CLEAN, 1>(a, grid, lds, st) : launch_resident_inst<NQ, 1, 0, CLEAN, 1>(a, grid, lds, st);
-        return mode == 5 ? launch_resident_inst<NQ, 0, 1, CLEAN, 1>(a, grid, lds, st) : launch_resident_inst<NQ, 0, 0, CLEAN, 1>(a, grid, lds, st);
-    }
-    if (mode == 7) return blend ? launch_resident_inst<NQ, 1, 4, CLEAN>(a, grid, lds, st) : launch_resident_inst<NQ, 0, 4, CLEAN>(a, grid, lds, st);
-    if (mode == 3) return blend ? launch_resident_inst<NQ, 1, 3, CLEAN>(a, grid, lds, st) : launch_resident_inst<NQ, 0, 3, CLEAN>(a, grid, lds, st);
-    if (blend) {
-        if (mode == 2) return launch_resident_inst<NQ, 1, 2, CLEAN>(a, grid, lds, st);
-        return mode ? launch_resident_inst<NQ, 1, 1, CLEAN>(a, grid, lds, st) : launch_resident_inst<NQ, 1, 0, CLEAN>(a, grid, lds, st);
-    }
-    if (mode == 2) return launch_resident_inst<NQ, 0, 2, CLEAN>(a, grid, lds, st);
-    return mode ? launch_resident_inst<NQ, 0, 1, CLEAN>(a, grid, lds, st) : launch_resident_inst<NQ, 0, 0, CLEAN>(a, grid, lds, st);
-}
-template <int NQ>
-int launch_resident_nq(const ResArgs& a, int grid, size_t lds, int blend, int mode, bool clean, hipStream_t st) {
-    return clean ? launch_resident_c<NQ, 1>(a, grid, lds, blend, mode, st) : launch_resident_c<NQ, 0>(a, grid, lds, blend, mode, st);
-}
-
 
 }  // namespace
 
@@ -1248,10 +1244,7 @@ int cspn3_resident_plan(int B, int H, int W, int T, int blend, int n_cu, cspn_re
 }
 
 size_t cspn3_resident_workspace_bytes(int B, int H, int W) {
-    // 2 exchange planes, then 4 status words (abort, error, 2 reserved), then one flag per 16 pixels at most (tiles are >= 4 x 4)
-    const size_t planes = (size_t)2 * B * H * W * sizeof(float);
-    const size_t flags = ((size_t)B * (((size_t)H * W) / 16 + 1) + 4) * sizeof(unsigned);
-    return ((planes + 15) & ~(size_t)15) + ((flags + 15) & ~(size_t)15);
+    return resident_workspace_bytes(B, H, W, sizeof(float), 16);       // tiles are >= 4 x 4
 }
 
 int cspn3_forward_resident(const void* guidance, long bs, long cs, const void* d0, const void* sparse, void* out,
@@ -1267,7 +1260,7 @@ int cspn3_transposed_resident(const void* w8, const float* g_T, const float* spa
                               unsigned seq, unsigned* host_err, int B, int H, int W, int W_valid, int T, int premask,
                               const cspn_resident_plan* plan, cspn_stream_t stream) {
     if (!w8 || !g_T || !history) return fail("cspn3_transposed_resident: bad arguments");
-    if (premask && !sparse_f32) return fail("cspn3_transposed_resident: premask needs sparse");
+    if (!check_premask("cspn3_transposed_resident", premask, sparse_f32)) return 0;
     return resident_launch(w8, (long)8 * H * W, (long)H * W, g_T, premask ? sparse_f32 : nullptr, nullptr, history, nullptr, nullptr,
                            work, seq, host_err, B, H, W, W_valid, T, premask ? 1 : 0, nullptr, nullptr, 0, plan, stream,
                            /*transposed=*/true);
@@ -1278,7 +1271,7 @@ int cspn3_transposed_resident_guidance(const void* guidance, long bs, long cs, c
                                        int B, int H, int W, int W_valid, int T, int premask, const cspn_resident_plan* plan,
                                        cspn_stream_t stream) {
     if (!guidance || !S || !g_T || !history) return fail("cspn3_transposed_resident_guidance: bad arguments");
-    if (premask && !sparse_f32) return fail("cspn3_transposed_resident_guidance: premask needs sparse");
+    if (!check_premask("cspn3_transposed_resident_guidance", premask, sparse_f32)) return 0;
     if (!aligned16(S)) return fail("cspn3_transposed_resident_guidance: S must be 16-byte aligned");
     return resident_launch(guidance, bs, cs, g_T, premask ? sparse_f32 : nullptr, nullptr, history, nullptr, nullptr, work, seq,
                            host_err, B, H, W, W_valid, T, premask ? 1 : 0, nullptr, nullptr, 0, plan, stream,
@@ -1311,17 +1304,14 @@ int resident_launch(const void* guidance, long bs, long cs, const void* d0, cons
         return fail("cspn3_forward_resident: the training form (history) needs s_out (w8_out is optional: null publishes S only), 16-byte aligned, and no scoring");
     if (!history && (w8_out || s_out)) return fail("cspn3_forward_resident: w8_out / s_out are outputs of the training form (history)");
     if (transposed && !aligned16(history)) return fail("cspn3_transposed_resident: history must be 16-byte aligned");
-    if (blend != CSPN_BLEND_NONE && blend != CSPN_BLEND_SPARSE) return fail("cspn3_forward_resident: blend %d", blend);
-    if (blend && !sparse) return fail("cspn3_forward_resident: blend needs sparse");
-    if ((target || acc) && (!target || !acc || nslots < 1 || !aligned16(target)))
-        return fail("cspn3_forward_resident: scoring needs target (16-byte aligned), acc and nslots >= 1");
+    const char* const who = "cspn3_forward_resident";         // (the name every rule of the three 3x3 entry points' common part reports)
+    if (!check_blend(who, blend, sparse) || !check_scoring(who, target, acc, nslots)) return 0;
     if ((W & 3) || (cs & 3) || (bs & 3)) return fail("cspn3_forward_resident: W and the guidance strides must be multiples of 4");
     if (cs < 0 || bs < 0 || cs >= (1L << 27) || (long)H * W >= (1L << 27))
         return fail("cspn3_forward_resident: images of >= 2^27 pixels / channel strides >= 2^27 elements are not supported (32-bit offsets)");
-    if (!aligned16(guidance) || !aligned16(d0) || (out && !aligned16(out)) || !aligned16(work) || (sparse && !aligned16(sparse)))
-        return fail("cspn3_forward_resident: tensors must be 16-byte aligned");
+    if (!check_tensors_aligned16(who, {guidance, d0, out, work, sparse})) return 0;
     if (W_valid < 0 || W_valid > W) return fail("cspn3_forward_resident: W_valid=%d outside (0, W=%d]", W_valid, W);
-    if (seq == 0 || seq > 0x7fffff00u) return fail("cspn3_forward_resident: seq must be in [1, 2^31 - 256]");
+    if (!check_seq(who, seq)) return 0;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int ncu = cu_count();
@@ -1336,35 +1326,7 @@ int resident_launch(const void* guidance, long bs, long cs, const void* d0, cons
         rp.threads = RES_THREADS;
         rp.tiles_x = rp.tiles_y = rp.tile_w = rp.tile_h = rp.images_per_launch = 0;
     }
-    if (rp.threads == RES_THREADS_CLIPPED && rp.tiles_x > 0 && rp.tiles_y > 0 && rp.tile_w > 0 && rp.tile_h > 0 && rp.steps_per_phase > 0 && rp.images_per_launch > 0) {
-        // a clipped plan: tile_h is the FIRST tile row's height, the uneven rows follow from it (clipped_geometry)
-        if (!clipped_geometry(H, W, T, rp.steps_per_phase > T ? T : rp.steps_per_phase, rp.tiles_x, rp.tiles_y, rp.tile_w, rp.tile_h, blend, &g) ||
-            (long)rp.images_per_launch * g.tiles_x * g.tiles_y > ncu)
-            return fail("cspn3_forward_resident: the clipped plan does not fit this problem / device (use cspn3_resident_plan)");
-        g.imgs_per_launch = rp.images_per_launch;
-    } else if (rp.tiles_x > 0 && rp.tiles_y > 0 && rp.tile_w > 0 && rp.tile_h > 0 && rp.steps_per_phase > 0 && rp.images_per_launch > 0) {
-        // a plan that came out of cspn3_resident_plan for this problem: re-derive the dependent fields and re-check the
-        // limits, skip the search (it is ~6000 candidate tilings: tens of microseconds per call on the host)
-        const int Se = rp.steps_per_phase > T ? T : rp.steps_per_phase;
-        g.S = Se; g.tiles_x = rp.tiles_x; g.tiles_y = rp.tiles_y; g.tw = rp.tile_w; g.th = rp.tile_h;
-        g.hyw = Se - 1; g.hxw = round_up4(Se - 1);
-        g.wq = (g.tw + 2 * g.hxw) / 4; g.wr = g.th + 2 * g.hyw;
-        g.dr = g.wr + 2;
-        set_uniform_rows(&g);
-        g.threads = rp.threads == 1024 ? 1024 : RES_THREADS;
-        g.nq = g.wq > 0 && g.wq <= g.threads ? ceil_div(g.wr, g.threads / g.wq) : RES_MAX_NQ + 1;
-        if (g.threads == 1024 && g.nq > 1) g.nq = RES_MAX_NQ + 1;
-        g.ls = res_row_stride(g.wq, g.nq, g.dr);
-        g.lds_bytes = res_lds_bytes(g.dr, g.ls, g.nq, blend, g.threads);
-        g.imgs_per_launch = rp.images_per_launch;
-        const int phases = ceil_div(T, Se);
-        if ((g.tw & 3) || g.nq > RES_MAX_NQ || g.lds_bytes > 160 * 1024 || (size_t)g.dr * g.ls > (size_t)RES_PP || (phases > 1 && (Se & 1)) || g.tiles_x * g.tw < W || g.tiles_y * g.th < H ||
-            (long)g.imgs_per_launch * g.tiles_x * g.tiles_y > ncu ||
-            (phases > 1 && ((g.tiles_x > 1 && g.tw < 2 * g.hxw) || (g.tiles_y > 1 && g.th < 2 * g.hyw))))
-            return fail("cspn3_forward_resident: the plan does not fit this problem / device (use cspn3_resident_plan)");
-    } else if (!resident_geometry(B, H, W, T, blend, ncu, rp.steps_per_phase, &g, rp.threads)) {
-        return fail("cspn3_forward_resident: no resident tiling for B=%d %dx%d T=%d", B, H, W, T);
-    }
+    if (!resident_resolve(B, H, W, T, blend, ncu, rp, &g)) return 0;
     // a tile that finished phase p publishes seq + p + 1, and the next call on the workspace brings seq + 256: more than
     // 255 phases would let one call's flags satisfy the next call's waits
     if (ceil_div(T, g.S) > 255)
@@ -1372,30 +1334,46 @@ int resident_launch(const void* guidance, long bs, long cs, const void* d0, cons
     ResArgs a{};
     a.g = static_cast<const float*>(guidance); a.g_bs = bs; a.g_cs = cs;
     a.d0 = static_cast<const float*>(d0); a.sparse = static_cast<const float*>(sparse); a.out = static_cast<float*>(out);
-    const size_t planes = (((size_t)2 * B * H * W * sizeof(float)) + 15) & ~(size_t)15;
     a.xbuf = static_cast<float*>(work);
-    a.status = reinterpret_cast<unsigned*>(static_cast<char*>(work) + planes);   // fixed place, whatever the tiling
-    a.flags = a.status + 4;
+    a.status = resident_status_words(work, B, H, W, sizeof(float));
+    a.flags = resident_phase_flags(a.status);
     if ((size_t)B * g.tiles_x * g.tiles_y > (size_t)B * (((size_t)H * W) / 16 + 1))
         return fail("cspn3_forward_resident: workspace too small for %d tiles", B * g.tiles_x * g.tiles_y);
     a.host_err = host_err;
     a.hist = static_cast<float*>(history); a.w_out = static_cast<float*>(w8_out); a.s_out = s_out;
     if (pac && transposed) return fail("cspn3_forward_resident: the softmax-weight form has no transposed sweep (use cspn3_transposed_resident on the volume)");
-    const int mode = transposed ? (s_in ? 7 : 3) : (history ? 2 : (acc ? 1 : 0)) + (pac ? 4 : 0);
+    const ResidentForm plain = history ? ResidentForm::Training : acc ? ResidentForm::Scored : ResidentForm::Inference;
+    const ResidentForm form = transposed ? (s_in ? ResidentForm::SweepGuidance : ResidentForm::SweepVolume)
+                                         : pac ? static_cast<ResidentForm>((int)plain + (int)ResidentForm::SoftmaxInference) : plain;
     a.s_in = s_in;
     a.seq = seq;
     a.target = static_cast<const float*>(target); a.macc = acc; a.nslots = nslots;
     a.B = B; a.H = H; a.W = W; a.Wv = Wv; a.T = T; a.S = g.S;
     a.tw = g.tw; a.th = g.th; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.th0 = g.th0; a.thl = g.thl;
     a.wq = g.wq; a.wr = g.wr; a.hxw = g.hxw; a.hyw = g.hyw; a.dr = g.dr; a.ls = g.ls;
-    a.spin_limit = rp.spin_limit ? rp.spin_limit : (4u << 20);   // x (sc1 load + s_sleep) ~ seconds
+    a.spin_limit = plan_spin_limit(rp);
     a.dbg = rp.debug_stamps;
     const bool clean = regions_inside_image(g, H, W, a.Wv, T);
     // (refused rather than ignored: a host that asked for the guard relies on `out` being complete for GPU-side consumers)
-    // mode: 0 / 1 / 2 inference / scored / training forward, 3 / 7 reverse sweep from a tap volume / from guidance + S, 4 / 5 / 6 the softmax forms
-    if (rp.guard && ((mode != 0 && mode != 1 && mode != 2 && mode != 3 && mode != 7 && mode != 4 && mode != 6) || ((mode == 0 || mode == 1 || mode == 4) && !out) ||
-                     !cspn_detail::resident_repair_fits(T)))
+    if (rp.guard && (!resident_form_guarded(form) || (resident_form_mode(form) <= 1 && !out) || !cspn_detail::resident_repair_fits(T)))
         return fail("cspn3_forward_resident: plan->guard serves inference (plain / scored), the training forward and the reverse sweeps, T <= 54 steps");
+    ResLaunchFn launch = nullptr;
+    if (g.threads == RES_THREADS_CLIPPED) {
+        if (!clean) return fail("cspn3_forward_resident: a clipped plan whose regions leave the image");
+        launch = res_lookup<3, RES_THREADS_CLIPPED>(clean, blend, form);
+    } else if (g.threads == 1024) {
+        launch = res_lookup<1, 1024>(clean, blend, form);
+    } else {
+        switch (g.nq) {
+            case 1: launch = res_lookup<1>(clean, blend, form); break;
+            case 2: launch = res_lookup<2>(clean, blend, form); break;
+            case 3: launch = res_lookup<3>(clean, blend, form); break;
+            case 4: launch = res_lookup<4>(clean, blend, form); break;
+            case 5: launch = res_lookup<5>(clean, blend, form); break;
+            default: return fail("cspn3_forward_resident: no instance for %d quads per thread", g.nq);
+        }
+    }
+    if (!launch) return fail("cspn3_forward_resident: %d-thread workgroups serve the inference forms only", g.threads);
     // one launch per round of images_per_launch images (-DCSPN_RES_ONE_LAUNCH=1: per RES_MAX_ROUNDS rounds — measured, not faster: see there)
     const int ipl = g.imgs_per_launch < B ? g.imgs_per_launch : B;
     const int max_rounds = CSPN_RES_ONE_LAUNCH ? RES_MAX_ROUNDS : 1;
@@ -1404,32 +1382,11 @@ int resident_launch(const void* guidance, long bs, long cs, const void* d0, cons
         a.nb = (B - b0) < ipl ? (B - b0) : ipl;
         const int rounds = ceil_div(B - b0, ipl) < max_rounds ? ceil_div(B - b0, ipl) : max_rounds;
         a.last_chunk = (b0 + ipl * max_rounds >= B) ? 1 : 0;
-        const int grid = rounds * a.nb * g.tiles_x * g.tiles_y;
-        int ok = 0;
-        if (g.threads == RES_THREADS_CLIPPED) {
-            if (!clean) return fail("cspn3_forward_resident: a clipped plan whose regions leave the image");
-            if (!launch_resident_768(a, grid, g.lds_bytes, blend, mode, st)) return 0;
-            continue;
-        }
-        if (g.threads == 1024) {
-            ok = clean ? launch_resident_1024<1>(a, grid, g.lds_bytes, blend, mode, st) : launch_resident_1024<0>(a, grid, g.lds_bytes, blend, mode, st);
-            if (!ok) return 0;
-            continue;
-        }
-        switch (g.nq) {
-            case 1: ok = launch_resident_nq<1>(a, grid, g.lds_bytes, blend, mode, clean, st); break;
-            case 2: ok = launch_resident_nq<2>(a, grid, g.lds_bytes, blend, mode, clean, st); break;
-            case 3: ok = launch_resident_nq<3>(a, grid, g.lds_bytes, blend, mode, clean, st); break;
-            case 4: ok = launch_resident_nq<4>(a, grid, g.lds_bytes, blend, mode, clean, st); break;
-            case 5: ok = launch_resident_nq<5>(a, grid, g.lds_bytes, blend, mode, clean, st); break;
-            default: return fail("cspn3_forward_resident: no instance for %d quads per thread", g.nq);
-        }
-        if (!ok) return 0;
+        if (!launch(rounds * a.nb * g.tiles_x * g.tiles_y, g.threads, g.lds_bytes, st, a)) return 0;
     }
     if (rp.guard)
-        return cspn_detail::resident_repair_launch(a.g, bs, cs, a.d0, a.sparse, a.out, a.hist, a.s_out, a.w_out, a.s_in,
-                                                   mode == 7 ? 4 : mode == 4 ? 10 : mode == 6 ? 12 : mode, a.status, seq, B, H, W, a.Wv, T, blend ? 1 : 0, ncu, st,
-                                                   a.target, a.macc, a.nslots);
+        return cspn_detail::resident_repair_launch(a.g, bs, cs, a.d0, a.sparse, a.out, a.hist, a.s_out, a.w_out, a.s_in, form, a.status, seq, B, H, W,
+                                                   a.Wv, T, blend ? 1 : 0, ncu, st, a.target, a.macc, a.nslots);
     return 1;
 }
 

@@ -21,8 +21,6 @@
 // configuration, tests/test_hip_kres.py).  Exchange protocol, flags, bounded wait and NaN poisoning: those of cspnk_resident.hip.
 #include "cspnk_helpers.hpp"
 
-#include <atomic>
-
 namespace {
 
 typedef unsigned v4uu __attribute__((ext_vector_type(4)));
@@ -524,24 +522,10 @@ __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_d2(const KResArgs a) {
     count_out();
 }
 
-template <int BLEND, int MODE, int CLEAN, int NTH, int NPF>
-int d2_launch_inst(const KResArgs& a, int grid, size_t lds_bytes, hipStream_t st) {
-    constexpr auto kern = cspnk_d2<BLEND, MODE, CLEAN, NTH, NPF>;
-    static std::atomic<size_t> granted[64];
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    if (lds_bytes > 64 * 1024 && granted[dev & 63].load(std::memory_order_acquire) < lds_bytes) {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        granted[dev & 63].store(lds_bytes, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NTH), lds_bytes, st, a);
-    HIP_OK(hipGetLastError());
-    return 1;
-}
 template <int NTH, int NPF>
 int d2_launch_nth(const KResArgs& a, int grid, size_t lds, int blend, int mode, int clean, hipStream_t st) {
 #define D2_CASE(BL, MD, CL) \
-    if (blend == BL && mode == MD && clean == CL) return d2_launch_inst<BL, MD, CL, NTH, NPF>(a, grid, lds, st)
+    if (blend == BL && mode == MD && clean == CL) return launch_dynamic_lds<cspnk_d2<BL, MD, CL, NTH, NPF>>(grid, NTH, lds, st, a)
     D2_CASE(0, 0, 0); D2_CASE(0, 0, 1); D2_CASE(0, 1, 0); D2_CASE(0, 1, 1); D2_CASE(0, 2, 0); D2_CASE(0, 2, 1);
     D2_CASE(1, 0, 0); D2_CASE(1, 0, 1); D2_CASE(1, 1, 0); D2_CASE(1, 1, 1); D2_CASE(1, 2, 0); D2_CASE(1, 2, 1);
 #undef D2_CASE

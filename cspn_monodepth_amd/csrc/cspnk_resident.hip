@@ -25,8 +25,6 @@
 // launches of 12 images (20 tiles each); see DESIGN.md §4.1c for the arithmetic.
 #include "cspnk_helpers.hpp"
 
-#include <atomic>
-
 namespace {
 
 constexpr int KRES_THREADS = 512;        // default workgroup; 768 threads (3 wavefronts per SIMD, <= 168 VGPRs) serve one-oct strips
@@ -749,24 +747,56 @@ bool kres_geometry(int K, int gdt, int B, int H, int W, int T, int blend, int nc
     return found;
 }
 
-template <int K, int NO, int BLEND, int SCORE, int CLEAN, typename ST, int NTH, typename GT, int TRANS = 0>
-int klaunch_inst(const KResArgs& a, int grid, size_t lds_bytes, hipStream_t st) {
-    constexpr auto kern = cspnk_resident<K, NO, BLEND, SCORE, CLEAN, ST, NTH, GT, TRANS>;
-    static std::atomic<size_t> granted[64];
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    if (lds_bytes > 64 * 1024 && granted[dev & 63].load(std::memory_order_acquire) < lds_bytes) {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        granted[dev & 63].store(lds_bytes, std::memory_order_release);
+// The geometry of a launch: the plan's tiling when it carries one (re-derived and re-checked by kgeom_fill, the search is skipped), else the
+// search's.  `who` is the entry point's name.
+int kres_resolve(const char* who, int K, int gdt, int B, int H, int W, int T, int blend, int ncu, const cspn_resident_plan& rp, KGeom* g) {
+    if (!plan_has_tiling(rp)) {
+        if (!kres_geometry(K, gdt, B, H, W, T, blend, ncu, rp.steps_per_phase, rp.threads, g))
+            return fail("%s: no resident tiling for K=%d B=%d %dx%d T=%d", who, K, B, H, W, T);
+        return 1;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NTH), lds_bytes, st, a);
-    HIP_OK(hipGetLastError());
+    const int Se = rp.steps_per_phase > T ? T : rp.steps_per_phase;
+    if (!kgeom_fill(K, gdt, H, W, T, blend, ncu, B, Se, rp.tiles_x, rp.tiles_y, rp.tile_w, rp.tile_h, rp.threads > 0 ? rp.threads : KRES_THREADS, g) ||
+        (long)rp.images_per_launch * g->tiles_x * g->tiles_y > ncu)
+        return fail("%s: the plan does not fit this problem / device (use cspnk_resident_plan)", who);
+    g->imgs_per_launch = rp.images_per_launch;
     return 1;
 }
+
+// What the launch arguments of every entry point share: the workspace (planes of `elem_size` bytes per pixel), the call's sequence
+// number, the problem and the geometry, the plan's spin limit and debug stamps.  The tensors are the entry point's to set.
+KResArgs kres_args(const KGeom& g, const cspn_resident_plan& rp, void* work, size_t elem_size, unsigned seq, unsigned* host_err, int B, int H, int W, int T) {
+    KResArgs a{};
+    a.xbuf = work;
+    a.status = resident_status_words(work, B, H, W, elem_size);
+    a.flags = resident_phase_flags(a.status);
+    a.host_err = host_err; a.seq = seq;
+    a.B = B; a.H = H; a.W = W; a.T = T; a.S = g.S;
+    a.tw = g.tw; a.th = g.th; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y;
+    a.wo = g.wo; a.wr = g.wr; a.hxw = g.hxw; a.hyw = g.hyw; a.dr = g.dr; a.ls = g.ls;
+    a.spin_limit = plan_spin_limit(rp);
+    a.dbg = rp.debug_stamps;
+    return a;
+}
+
+// The dot-product form (cspnk_d2.hip; mode as kres_d2_launch's): ONE launch for the whole batch — a workgroup refines its tile of
+// image b, b + images_per_launch, ... back to back.
+int kres_d2_whole_batch(const char* who, KResArgs& a, const KGeom& g, int B, int H, int W, int T, int blend, int mode, void* stream) {
+    a.ls = cspn_detail::kres_d2_row_stride(g.wo);
+    a.b0 = 0;
+    a.nb = g.imgs_per_launch < B ? g.imgs_per_launch : B;
+    a.rounds = ceil_div(B, a.nb);
+    a.last_chunk = 1;
+    const int npf = cspn_detail::kres_d2_prefetch_channels(g.dr, a.ls, g.threads, a.rounds);
+    const size_t ldsb = cspn_detail::kres_d2_lds_bytes(g.dr, a.ls, g.threads, npf);
+    if (ldsb > 160 * 1024) return fail("%s: the dot-product form needs %zu bytes of LDS", who, ldsb);
+    return cspn_detail::kres_d2_launch(&a, g.threads, a.nb * g.tiles_x * g.tiles_y, ldsb, blend, mode, kregions_inside_image(g, H, W, T) ? 1 : 0, npf, stream);
+}
+
 template <int K, int NO, typename ST, int NTH, typename GT = __half>
 int klaunch_no(const KResArgs& a, int grid, size_t lds, int blend, int score, bool clean, hipStream_t st) {
 #define KRES_CASE(BL, SC, CL) \
-    if (blend == BL && score == SC && (int)clean == CL) return klaunch_inst<K, NO, BL, SC, CL, ST, NTH, GT>(a, grid, lds, st)
+    if (blend == BL && score == SC && (int)clean == CL) return launch_dynamic_lds<cspnk_resident<K, NO, BL, SC, CL, ST, NTH, GT>>(grid, NTH, lds, st, a)
     KRES_CASE(0, 0, 0); KRES_CASE(0, 0, 1); KRES_CASE(0, 1, 0); KRES_CASE(0, 1, 1);
     KRES_CASE(1, 0, 0); KRES_CASE(1, 0, 1); KRES_CASE(1, 1, 0); KRES_CASE(1, 1, 1);
 #undef KRES_CASE
@@ -828,27 +858,22 @@ int cspnk_resident_plan(int K, int g_dtype, int B, int H, int W, int T, int blen
 }
 
 size_t cspnk_resident_workspace_bytes(int B, int H, int W, int state_dtype) {
-    const size_t planes = (size_t)2 * B * H * W * esize(state_dtype);
-    const size_t flags = ((size_t)B * (((size_t)H * W) / 8 + 1) + 4) * sizeof(unsigned);       // tiles are >= 8 x 1
-    return ((planes + 15) & ~(size_t)15) + ((flags + 15) & ~(size_t)15);
+    return resident_workspace_bytes(B, H, W, esize(state_dtype), 8);       // tiles are >= 8 x 1
 }
 
 int cspnk_forward_resident(const void* guided, int g_dtype, int K, const void* x0, const void* sparse, void* out, int state_dtype,
                            void* work, unsigned seq, unsigned* host_err, int B, int H, int W, int T, int blend,
                            const void* target, double* acc, int nslots, const cspn_resident_plan* plan, cspn_stream_t stream) {
+    const char* const who = "cspnk_forward_resident";
     if (!guided || !x0 || !out || !work || B <= 0 || H <= 0 || W <= 0 || T < 1) return fail("cspnk_forward_resident: bad arguments");
     if (K != 3 && K != 5) return fail("cspnk_forward_resident: K=%d (3 or 5)", K);
     if (state_dtype != CSPN_F16 && state_dtype != CSPN_F32) return fail("cspnk_forward_resident: state dtype %d", state_dtype);
     if (g_dtype != CSPN_F16 && g_dtype != CSPN_F32) return fail("cspnk_forward_resident: guidance dtype %d", g_dtype);
     if (g_dtype == CSPN_F32 && state_dtype != CSPN_F32) return fail("cspnk_forward_resident: fp32 guidance runs with fp32 depth planes");
-    if (blend != CSPN_BLEND_NONE && blend != CSPN_BLEND_SPARSE) return fail("cspnk_forward_resident: blend %d", blend);
-    if (blend && !sparse) return fail("cspnk_forward_resident: blend needs sparse");
-    if ((target || acc) && (!target || !acc || nslots < 1)) return fail("cspnk_forward_resident: scoring needs target, acc and nslots >= 1");
+    if (!check_blend(who, blend, sparse) || !check_scoring(who, target, acc, nslots)) return 0;
     if (W & 7) return fail("cspnk_forward_resident: W must be a multiple of 8 (whole octs of guidance)");
     if ((long)(K * K - 1) * H * W >= (1L << 30)) return fail("cspnk_forward_resident: guidance images of >= 2^30 elements are not supported (32-bit offsets)");
-    if (!aligned16(guided) || !aligned16(x0) || !aligned16(out) || !aligned16(work) || (sparse && !aligned16(sparse)) || (target && !aligned16(target)))
-        return fail("cspnk_forward_resident: tensors must be 16-byte aligned");
-    if (seq == 0 || seq > 0x7fffff00u) return fail("cspnk_forward_resident: seq must be in [1, 2^31 - 256]");
+    if (!check_tensors_aligned16(who, {guided, x0, out, work, sparse}) || !check_seq(who, seq)) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int ncu = kcu_count();
     if (ncu <= 0) return fail("cspnk_forward_resident: no device");
@@ -863,46 +888,19 @@ int cspnk_forward_resident(const void* guided, int g_dtype, int K, const void* x
     }
     if (rp.guard && (acc || !cspn_detail::kres_repair_fits(K, T)))
         return fail("cspnk_forward_resident: plan->guard serves unscored calls with T * (K / 2) <= 54");
-    if (rp.tiles_x > 0 && rp.tiles_y > 0 && rp.tile_w > 0 && rp.tile_h > 0 && rp.steps_per_phase > 0 && rp.images_per_launch > 0) {
-        const int Se = rp.steps_per_phase > T ? T : rp.steps_per_phase;
-        if (!kgeom_fill(K, g_dtype, H, W, T, blend, ncu, B, Se, rp.tiles_x, rp.tiles_y, rp.tile_w, rp.tile_h, rp.threads > 0 ? rp.threads : KRES_THREADS, &g) ||
-            (long)rp.images_per_launch * g.tiles_x * g.tiles_y > ncu)
-            return fail("cspnk_forward_resident: the plan does not fit this problem / device (use cspnk_resident_plan)");
-        g.imgs_per_launch = rp.images_per_launch;
-    } else if (!kres_geometry(K, g_dtype, B, H, W, T, blend, ncu, rp.steps_per_phase, rp.threads, &g)) {
-        return fail("cspnk_forward_resident: no resident tiling for K=%d B=%d %dx%d T=%d", K, B, H, W, T);
-    }
-    KResArgs a{};
-    a.g = guided; a.x0 = x0; a.sparse = sparse; a.out = out;
-    const size_t planes = (((size_t)2 * B * H * W * esize(state_dtype)) + 15) & ~(size_t)15;
-    a.xbuf = work;
-    a.status = reinterpret_cast<unsigned*>(static_cast<char*>(work) + planes);
-    a.flags = a.status + 4;
+    if (!kres_resolve(who, K, g_dtype, B, H, W, T, blend, ncu, rp, &g)) return 0;
     if ((size_t)g.tiles_x * g.tiles_y > ((size_t)H * W) / 8 + 1) return fail("cspnk_forward_resident: workspace too small for %d tiles per image", g.tiles_x * g.tiles_y);
-    a.host_err = host_err; a.seq = seq;
+    KResArgs a = kres_args(g, rp, work, esize(state_dtype), seq, host_err, B, H, W, T);
+    a.g = guided; a.x0 = x0; a.sparse = sparse; a.out = out;
     a.target = target; a.macc = acc; a.nslots = nslots;
-    a.B = B; a.H = H; a.W = W; a.T = T; a.S = g.S;
-    a.tw = g.tw; a.th = g.th; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y;
-    a.wo = g.wo; a.wr = g.wr; a.hxw = g.hxw; a.hyw = g.hyw; a.dr = g.dr; a.ls = g.ls;
-    a.spin_limit = rp.spin_limit ? rp.spin_limit : (4u << 20);
-    a.dbg = rp.debug_stamps;
     const bool clean = kregions_inside_image(g, H, W, T);
     const int score = acc ? 1 : 0;
-    // The dot-product form (cspnk_d2.hip): K = 5, fp16 guidance, fp16 planes, one oct per thread.  One launch for the whole
-    // batch: a workgroup refines its tile of image b, b + images_per_launch, ... back to back.
+    // The dot-product form (cspnk_d2.hip): K = 5, fp16 guidance, fp16 planes, one oct per thread.
     const bool d2_able = K == 5 && g_dtype == CSPN_F16 && state_dtype == CSPN_F16 && g.no == 1;
     if (rp.step_form == CSPN_STEP_DOT2 && !d2_able)
         return fail("cspnk_forward_resident: the dot-product step form exists for K = 5 with fp16 guidance, fp16 planes and one oct per thread");
     if (d2_able && rp.step_form != CSPN_STEP_FMA) {
-        a.ls = cspn_detail::kres_d2_row_stride(g.wo);
-        a.b0 = 0;
-        a.nb = g.imgs_per_launch < B ? g.imgs_per_launch : B;
-        a.rounds = ceil_div(B, a.nb);
-        a.last_chunk = 1;
-        const int npf = cspn_detail::kres_d2_prefetch_channels(g.dr, a.ls, g.threads, a.rounds);
-        const size_t ldsb = cspn_detail::kres_d2_lds_bytes(g.dr, a.ls, g.threads, npf);
-        if (ldsb > 160 * 1024) return fail("cspnk_forward_resident: the dot-product form needs %zu bytes of LDS", ldsb);
-        if (!cspn_detail::kres_d2_launch(&a, g.threads, a.nb * g.tiles_x * g.tiles_y, ldsb, blend, score, clean ? 1 : 0, npf, stream)) return 0;
+        if (!kres_d2_whole_batch(who, a, g, B, H, W, T, blend, score, stream)) return 0;
         // (the dot-product form rounds the state to half after every step)
         if (rp.guard) return cspn_detail::kres_repair_launch(guided, g_dtype, K, x0, sparse, out, state_dtype, a.status, seq, B, H, W, T, 1,
                                                              CSPN_STEP_DOT2, blend ? 1 : 0, ncu, stream);
@@ -934,47 +932,28 @@ int cspnk_forward_resident(const void* guided, int g_dtype, int K, const void* x
 int cspnk_transposed_resident(const void* wk, int w_dtype, int K, const void* g_T, const void* sparse_f32, int in_dtype, float* g_T_f32_out,
                               float* history, void* work, unsigned seq, unsigned* host_err, int B, int H, int W, int T, int premask,
                               const cspn_resident_plan* plan, cspn_stream_t stream) {
+    const char* const who = "cspnk_transposed_resident";
     if (plan && plan->guard && !cspn_detail::kres_repair_fits(5, T)) return fail("cspnk_transposed_resident: the guard re-computes at most 27 steps (T=%d)", T);
     if (!wk || !g_T || !history || !work || B <= 0 || H <= 0 || W <= 0 || T < 1) return fail("cspnk_transposed_resident: bad arguments");
     if (K != 5 || w_dtype != CSPN_F16) return fail("cspnk_transposed_resident: K = 5 with an fp16 tap volume (K=%d, dtype %d)", K, w_dtype);
-    if (premask && !sparse_f32) return fail("cspnk_transposed_resident: premask needs sparse");
+    if (!check_premask(who, premask, sparse_f32)) return 0;
     if (in_dtype != CSPN_F32 && in_dtype != CSPN_F16) return fail("cspnk_transposed_resident: bad in_dtype %d", in_dtype);
     if (g_T_f32_out && (in_dtype != CSPN_F16 || !aligned16(g_T_f32_out)))
         return fail("cspnk_transposed_resident: g_T_f32_out goes with fp16 inputs (16-byte aligned)");
     if (W & 7) return fail("cspnk_transposed_resident: W must be a multiple of 8");
     if ((long)24 * H * W >= (1L << 30)) return fail("cspnk_transposed_resident: tap volumes of >= 2^30 elements per image are not supported");
-    if (!aligned16(wk) || !aligned16(g_T) || !aligned16(history) || !aligned16(work) || (sparse_f32 && !aligned16(sparse_f32)))
-        return fail("cspnk_transposed_resident: tensors must be 16-byte aligned");
-    if (seq == 0 || seq > 0x7fffff00u) return fail("cspnk_transposed_resident: seq must be in [1, 2^31 - 256]");
+    if (!check_tensors_aligned16(who, {wk, g_T, history, work, sparse_f32}) || !check_seq(who, seq)) return 0;
     const int ncu = kcu_count();
     if (ncu <= 0) return fail("cspnk_transposed_resident: no device");
     const int blend = premask ? 1 : 0;
     cspn_resident_plan rp{};
     if (plan) rp = *plan;
     KGeom g;
-    if (rp.tiles_x > 0 && rp.tiles_y > 0 && rp.tile_w > 0 && rp.tile_h > 0 && rp.steps_per_phase > 0 && rp.images_per_launch > 0) {
-        const int Se = rp.steps_per_phase > T ? T : rp.steps_per_phase;
-        if (!kgeom_fill(K, CSPN_F16, H, W, T, blend, ncu, B, Se, rp.tiles_x, rp.tiles_y, rp.tile_w, rp.tile_h, rp.threads > 0 ? rp.threads : KRES_THREADS, &g) ||
-            (long)rp.images_per_launch * g.tiles_x * g.tiles_y > ncu)
-            return fail("cspnk_transposed_resident: the plan does not fit this problem / device (use cspnk_resident_plan)");
-        g.imgs_per_launch = rp.images_per_launch;
-    } else if (!kres_geometry(K, CSPN_F16, B, H, W, T, blend, ncu, rp.steps_per_phase, rp.threads, &g)) {
-        return fail("cspnk_transposed_resident: no resident tiling for K=%d B=%d %dx%d T=%d", K, B, H, W, T);
-    }
+    if (!kres_resolve(who, K, CSPN_F16, B, H, W, T, blend, ncu, rp, &g)) return 0;
     if (g.no != 1) return fail("cspnk_transposed_resident: needs a one-oct-per-thread tiling");
-    KResArgs a{};
+    KResArgs a = kres_args(g, rp, work, esize(CSPN_F32), seq, host_err, B, H, W, T);
     a.g = wk; a.x0 = g_T; a.sparse = premask ? sparse_f32 : nullptr; a.out = g_T_f32_out; a.hist = history;
     const int tr = in_dtype == CSPN_F16 ? 2 : 1;
-    const size_t planes = (((size_t)2 * B * H * W * esize(CSPN_F32)) + 15) & ~(size_t)15;
-    a.xbuf = work;
-    a.status = reinterpret_cast<unsigned*>(static_cast<char*>(work) + planes);
-    a.flags = a.status + 4;
-    a.host_err = host_err; a.seq = seq;
-    a.B = B; a.H = H; a.W = W; a.T = T; a.S = g.S;
-    a.tw = g.tw; a.th = g.th; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y;
-    a.wo = g.wo; a.wr = g.wr; a.hxw = g.hxw; a.hyw = g.hyw; a.dr = g.dr; a.ls = g.ls;
-    a.spin_limit = rp.spin_limit ? rp.spin_limit : (4u << 20);
-    a.dbg = rp.debug_stamps;
     const bool clean = kregions_inside_image(g, H, W, T);
     hipStream_t st = static_cast<hipStream_t>(stream);
     // ONE launch for the whole batch (KRES_T_MAX_ROUNDS rounds of images_per_launch images at most per launch: the bounded neighbour wait
@@ -990,8 +969,8 @@ int cspnk_transposed_resident(const void* wk, int w_dtype, int K, const void* g_
         int ok = 0;
 #define KT_CASE(BL, CL, NTHR) \
         if (!ok && blend == BL && (int)clean == CL && g.threads == NTHR) \
-            ok = tr == 2 ? klaunch_inst<5, 1, BL, 0, CL, float, NTHR, __half, 2>(a, grid, g.lds_bytes, st) \
-                         : klaunch_inst<5, 1, BL, 0, CL, float, NTHR, __half, 1>(a, grid, g.lds_bytes, st)
+            ok = tr == 2 ? launch_dynamic_lds<cspnk_resident<5, 1, BL, 0, CL, float, NTHR, __half, 2>>(grid, NTHR, g.lds_bytes, st, a) \
+                         : launch_dynamic_lds<cspnk_resident<5, 1, BL, 0, CL, float, NTHR, __half, 1>>(grid, NTHR, g.lds_bytes, st, a)
         KT_CASE(0, 0, 768); KT_CASE(0, 1, 768); KT_CASE(1, 0, 768); KT_CASE(1, 1, 768);
         KT_CASE(0, 0, 512); KT_CASE(0, 1, 512); KT_CASE(1, 0, 512); KT_CASE(1, 1, 512);
 #undef KT_CASE
@@ -1012,49 +991,21 @@ int cspnk_forward_resident_history(const void* guided, int g_dtype, int K, const
     if (K == 5 && g_dtype == CSPN_F16) {
         // BASELINE config 3's training forward: the dot-product kernel (cspnk_d2.hip) with fp16 planes — x0 / sparse / history are
         // fp16, every step's state goes to its history plane, wk_out receives the fp16 tap volume (pair-interleaved layout)
-        if (blend != CSPN_BLEND_NONE && blend != CSPN_BLEND_SPARSE) return fail("cspnk_forward_resident_history: blend %d", blend);
-        if (blend && !sparse) return fail("cspnk_forward_resident_history: blend needs sparse");
+        const char* const who = "cspnk_forward_resident_history";
+        if (!check_blend(who, blend, sparse)) return 0;
         if (W & 7) return fail("cspnk_forward_resident_history: W must be a multiple of 8");
         if ((long)24 * H * W >= (1L << 30)) return fail("cspnk_forward_resident_history: guidance images of >= 2^30 elements are not supported");
-        if (!aligned16(guided) || !aligned16(x0) || !aligned16(history) || !aligned16(wk_out) || !aligned16(work) || (sparse && !aligned16(sparse)))
-            return fail("cspnk_forward_resident_history: tensors must be 16-byte aligned");
-        if (seq == 0 || seq > 0x7fffff00u) return fail("cspnk_forward_resident_history: seq must be in [1, 2^31 - 256]");
+        if (!check_tensors_aligned16(who, {guided, x0, history, wk_out, work, sparse}) || !check_seq(who, seq)) return 0;
         const int ncu = kcu_count();
         if (ncu <= 0) return fail("cspnk_forward_resident_history: no device");
         cspn_resident_plan rp{};
         if (plan) rp = *plan;
         KGeom g;
-        if (rp.tiles_x > 0 && rp.tiles_y > 0 && rp.tile_w > 0 && rp.tile_h > 0 && rp.steps_per_phase > 0 && rp.images_per_launch > 0) {
-            const int Se = rp.steps_per_phase > T ? T : rp.steps_per_phase;
-            if (!kgeom_fill(K, g_dtype, H, W, T, blend, ncu, B, Se, rp.tiles_x, rp.tiles_y, rp.tile_w, rp.tile_h, rp.threads > 0 ? rp.threads : KRES_THREADS, &g) ||
-                (long)rp.images_per_launch * g.tiles_x * g.tiles_y > ncu)
-                return fail("cspnk_forward_resident_history: the plan does not fit this problem / device (use cspnk_resident_plan)");
-            g.imgs_per_launch = rp.images_per_launch;
-        } else if (!kres_geometry(K, g_dtype, B, H, W, T, blend, ncu, rp.steps_per_phase, rp.threads, &g)) {
-            return fail("cspnk_forward_resident_history: no resident tiling for K=%d B=%d %dx%d T=%d", K, B, H, W, T);
-        }
+        if (!kres_resolve(who, K, g_dtype, B, H, W, T, blend, ncu, rp, &g)) return 0;
         if (g.no != 1) return fail("cspnk_forward_resident_history: the K = 5 training form needs a one-oct-per-thread tiling");
-        KResArgs a{};
+        KResArgs a = kres_args(g, rp, work, esize(CSPN_F16), seq, host_err, B, H, W, T);
         a.g = guided; a.x0 = x0; a.sparse = sparse; a.out = nullptr; a.hist = history; a.wk_out = wk_out;
-        const size_t planes = (((size_t)2 * B * H * W * esize(CSPN_F16)) + 15) & ~(size_t)15;
-        a.xbuf = work;
-        a.status = reinterpret_cast<unsigned*>(static_cast<char*>(work) + planes);
-        a.flags = a.status + 4;
-        a.host_err = host_err; a.seq = seq;
-        a.B = B; a.H = H; a.W = W; a.T = T; a.S = g.S;
-        a.tw = g.tw; a.th = g.th; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y;
-        a.wo = g.wo; a.wr = g.wr; a.hxw = g.hxw; a.hyw = g.hyw; a.dr = g.dr;
-        a.ls = cspn_detail::kres_d2_row_stride(g.wo);
-        a.spin_limit = rp.spin_limit ? rp.spin_limit : (4u << 20);
-        a.dbg = rp.debug_stamps;
-        a.b0 = 0;
-        a.nb = g.imgs_per_launch < B ? g.imgs_per_launch : B;
-        a.rounds = ceil_div(B, a.nb);
-        a.last_chunk = 1;
-        const int npf = cspn_detail::kres_d2_prefetch_channels(g.dr, a.ls, g.threads, a.rounds);
-        const size_t ldsb = cspn_detail::kres_d2_lds_bytes(g.dr, a.ls, g.threads, npf);
-        if (ldsb > 160 * 1024) return fail("cspnk_forward_resident_history: %zu bytes of LDS", ldsb);
-        if (!cspn_detail::kres_d2_launch(&a, g.threads, a.nb * g.tiles_x * g.tiles_y, ldsb, blend, 2, kregions_inside_image(g, H, W, T) ? 1 : 0, npf, stream)) return 0;
+        if (!kres_d2_whole_batch(who, a, g, B, H, W, T, blend, 2, stream)) return 0;
         // the guard: a forward that gave up gets its T planes and its tap volume re-computed on the stream (cspn_repair.hip)
         if (rp.guard) return cspn_detail::kres_history_repair_launch(guided, x0, blend ? sparse : nullptr, history, wk_out, a.status, seq, B, H, W, T, blend ? 1 : 0, ncu, stream);
         return 1;

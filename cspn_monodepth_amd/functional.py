@@ -586,13 +586,28 @@ def set_resident(mode):
     _RESIDENT_MODE = mode
 
 
+def _plan_copy(cp=None, **fields):
+    """A new ctypes plan: a copy of `cp` (None: all zero) with `fields` set."""
+    c2 = _lib.cspn_resident_plan()
+    if cp is not None:
+        ctypes.memmove(ctypes.byref(c2), ctypes.byref(cp), ctypes.sizeof(c2))
+    for name, value in fields.items():
+        setattr(c2, name, value)
+    return c2
+
+
+def _ctypes_plan(plan_dict):
+    """The ctypes plan of a plan dict (resident_plan / kres_plan); None stays None.  debug_stamps is a per-call probe, not part of a plan."""
+    if plan_dict is None:
+        return None
+    return _plan_copy(**{name: plan_dict[name] for name, _ in _lib.cspn_resident_plan._fields_ if name != "debug_stamps"})
+
+
 def resident_plan(B, H, W, T, blend=0, n_cu=0, steps_per_phase=0, threads=0):
     """The tiling cspn3_forward_resident would use (dict), or None when the shape has none (W % 4 != 0, T < 1, ...).
     threads: 0 / 512 = the 512-thread workgroups, 1024 = one quad per thread on 1024 threads (inference forms only), 768 = three
     quads per thread on regions clipped to the image (inference forms only; `tile_h` is then the FIRST tile row's height)."""
-    rp = _lib.cspn_resident_plan()
-    rp.steps_per_phase = int(steps_per_phase)
-    rp.threads = int(threads)
+    rp = _plan_copy(steps_per_phase=int(steps_per_phase), threads=int(threads))
     ok = _lib.lib().cspn3_resident_plan(int(B), int(H), int(W), int(T), int(blend), int(n_cu), ctypes.byref(rp))
     if not ok:
         return None
@@ -851,15 +866,9 @@ def _resident_plan_cached(B, H, W, T, blend, dev):
             rp = resident_plan(B, H, W, T, blend, n_cu)
         else:
             rp = None if _device_is_oversubscribed() else resident_pays(B, H, W, T, blend, dev)
-        cp = None
-        if rp is not None:
-            cp = _lib.cspn_resident_plan()
-            for name, _ in _lib.cspn_resident_plan._fields_:
-                if name != "debug_stamps":
-                    setattr(cp, name, rp[name])
         if len(_RES_PLAN_CACHE) > 1024:
             _RES_PLAN_CACHE.clear()
-        hit = _RES_PLAN_CACHE[key] = (rp, cp)
+        hit = _RES_PLAN_CACHE[key] = (rp, _ctypes_plan(rp))
     return hit
 
 
@@ -880,10 +889,7 @@ def _scored_plan(cp, B, H, W, T, blend, dev):
         rp = resident_plan(B, H, W, T, blend, _resident_state(dev)["n_cu"], threads=768)
         c2 = cp
         if rp is not None and rp["launches"] == 1 and rp["steps_per_phase"] == cp.steps_per_phase:
-            c2 = _lib.cspn_resident_plan()
-            for name, _ in _lib.cspn_resident_plan._fields_:
-                if name != "debug_stamps":
-                    setattr(c2, name, rp[name])
+            c2 = _ctypes_plan(rp)
         if len(_RES_SCORED_PLAN_CACHE) > 256:
             _RES_SCORED_PLAN_CACHE.clear()
         hit = _RES_SCORED_PLAN_CACHE[key] = (cp, c2)
@@ -1114,17 +1120,11 @@ def _with_spin_limit(cp, step_form=0, guard=0):
     if guard and not _RESIDENT_SPIN_LIMIT and not step_form:      # the common case: one guarded copy per cached plan
         c2 = getattr(cp, "_guarded", None)
         if c2 is None:
-            c2 = _lib.cspn_resident_plan()
-            ctypes.memmove(ctypes.byref(c2), ctypes.byref(cp), ctypes.sizeof(c2))
-            c2.guard = 1
-            cp._guarded = c2
+            c2 = cp._guarded = _plan_copy(cp, guard=1)
         return c2
-    c2 = _lib.cspn_resident_plan()
-    ctypes.memmove(ctypes.byref(c2), ctypes.byref(cp), ctypes.sizeof(c2))
+    c2 = _plan_copy(cp, step_form=int(step_form), guard=int(guard))
     if _RESIDENT_SPIN_LIMIT:
         c2.spin_limit = int(_RESIDENT_SPIN_LIMIT)
-    c2.step_form = int(step_form)
-    c2.guard = int(guard)
     return c2
 
 
@@ -1197,10 +1197,7 @@ def pac_transposed_resident(wk, g_T, sparse, T, debug_stamps=None):
     guard = int(bool(_RESIDENT_GUARD) and 2 * int(T) <= _GUARD_MAX_T)
     rp = _with_spin_limit(_kres_plan_cached(5, B, H, W, int(T), premask, dev, 0, CSPN_F16)[1], guard=guard)
     if debug_stamps is not None and rp is not None:     # developer probe: in-kernel time stamps of round 0's workgroups [images_per_launch x tiles][16]
-        c2 = _lib.cspn_resident_plan()
-        ctypes.memmove(ctypes.byref(c2), ctypes.byref(rp), ctypes.sizeof(c2))
-        c2.debug_stamps = debug_stamps.data_ptr()
-        rp = c2
+        rp = _plan_copy(rp, debug_stamps=debug_stamps.data_ptr())
 
     def launch(work, seq, host_err_ptr, stream_ptr):
         return L.cspnk_transposed_resident(_p(wk), CSPN_F16, 5, _p(g_T), _p(sparse), _dt(g_T), _p(g32) if half_in else None, _p(ghist),
@@ -1241,12 +1238,8 @@ def forward_resident(guidance, d0, sparse, T, blend, score=None, valid_w=0, step
     if _plan is not None and not _RESIDENT_SPIN_LIMIT:
         rp = _plan                                     # the caller's cached (guarded) plan: CSPN3Function's fast path
     elif steps_per_phase or spin_limit or debug_stamps is not None or threads:
-        rp = _lib.cspn_resident_plan()
-        rp.steps_per_phase = int(steps_per_phase)
-        rp.threads = int(threads)
-        rp.spin_limit = int(spin_limit)
-        rp.debug_stamps = None if debug_stamps is None else debug_stamps.data_ptr()
-        rp.guard = guard
+        rp = _plan_copy(steps_per_phase=int(steps_per_phase), threads=int(threads), spin_limit=int(spin_limit),
+                        debug_stamps=None if debug_stamps is None else debug_stamps.data_ptr(), guard=guard)
     else:
         # found once per shape: the C side skips its search
         cp = _resident_plan_cached(B, H, W, int(T), int(blend), dev)[1]
@@ -1288,9 +1281,7 @@ def forward_resident(guidance, d0, sparse, T, blend, score=None, valid_w=0, step
 def kres_plan(K, B, H, W, T, blend=0, n_cu=0, steps_per_phase=0, threads=0, g_dtype=CSPN_F16):
     """The tiling cspnk_forward_resident would use (dict; `quads_per_thread` holds the OCTS per thread), or None.
     g_dtype: CSPN_F16 (packed taps) or CSPN_F32 (fp32 taps: fewer octs fit a thread)."""
-    rp = _lib.cspn_resident_plan()
-    rp.steps_per_phase = int(steps_per_phase)
-    rp.threads = int(threads)
+    rp = _plan_copy(steps_per_phase=int(steps_per_phase), threads=int(threads))
     ok = _lib.lib().cspnk_resident_plan(int(K), int(g_dtype), int(B), int(H), int(W), int(T), int(blend), int(n_cu), ctypes.byref(rp))
     if not ok:
         return None
@@ -1307,15 +1298,9 @@ def _kres_plan_cached(K, B, H, W, T, blend, dev, steps_per_phase=0, g_dtype=CSPN
         rp = None
         if _RESIDENT_MODE == "on" or not _device_is_oversubscribed():
             rp = kres_plan(K, B, H, W, T, blend, _resident_state(dev)["n_cu"], steps_per_phase, 0, g_dtype)
-        cp = None
-        if rp is not None:
-            cp = _lib.cspn_resident_plan()
-            for name, _ in _lib.cspn_resident_plan._fields_:
-                if name != "debug_stamps":
-                    setattr(cp, name, rp[name])
         if len(_KRES_PLAN_CACHE) > 1024:
             _KRES_PLAN_CACHE.clear()
-        hit = _KRES_PLAN_CACHE[key] = (rp, cp)
+        hit = _KRES_PLAN_CACHE[key] = (rp, _ctypes_plan(rp))
     return hit
 
 
@@ -1373,13 +1358,8 @@ def pac_forward_resident(guided, x0, sparse, T, score=None, steps_per_phase=0, s
         guard = int(bool(_RESIDENT_GUARD) and score is None and int(T) * (K // 2) <= _GUARD_MAX_T)
     guard = int(guard)
     if steps_per_phase or spin_limit or debug_stamps is not None or threads:
-        rp = _lib.cspn_resident_plan()
-        rp.steps_per_phase = int(steps_per_phase)
-        rp.threads = int(threads)
-        rp.spin_limit = int(spin_limit)
-        rp.debug_stamps = None if debug_stamps is None else debug_stamps.data_ptr()
-        rp.step_form = form
-        rp.guard = guard
+        rp = _plan_copy(steps_per_phase=int(steps_per_phase), threads=int(threads), spin_limit=int(spin_limit),
+                        debug_stamps=None if debug_stamps is None else debug_stamps.data_ptr(), step_form=form, guard=guard)
     else:
         rp = _with_spin_limit(_kres_plan_cached(K, B, H, W, int(T), int(blend), dev, 0, _dt(guided))[1], form, guard)
 

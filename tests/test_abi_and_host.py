@@ -183,6 +183,173 @@ def test_production_shapes_keep_their_resident_instances():
         assert tuple(p[k] for k in keys) == (4, 2, 10, 152, 23, 1, 12, 2) and p["threads"] == 768, p
 
 
+_PLAN_TABLE = os.path.join(ROOT, "tests", "golden", "g20_resident_plans.json")
+_PLAN_FIELDS = tuple(name for name, _ in _lib.cspn_resident_plan._fields_)
+_PLAN_SHAPES = ((7, 12), (37, 8), (60, 64), (61, 76), (100, 148), (228, 304), (352, 1216), (64, 30), (40, 152))
+
+
+def _resident_plan_cases():
+    """The arguments of the recorded plan calls: the full grid over batch, shape, steps, blend, CU count, requested phase length
+    and workgroup size (and K / guidance dtype for the K x K engine), thinned to every 23rd / 71st point — strides that share no
+    factor with an axis length, so every value of every axis and every pair of neighbouring axes' values still occurs."""
+    import itertools
+    Bs, Ts, cus, spps = (1, 2, 3, 5, 8, 24, 48), (1, 3, 7, 12, 24, 60), (64, 256), (0, 2, 5, 6, 8, 12)
+    grid3 = itertools.product(Bs, _PLAN_SHAPES, Ts, (0, 1), cus, spps, (0, 512, 768, 1024))
+    gridk = itertools.product((3, 5), (_lib.CSPN_F16, _lib.CSPN_F32), Bs, _PLAN_SHAPES, Ts, (0, 1), cus, spps, (0, 512, 768))
+    cases = [("cspn3", B, H, W, T, bl, cu, spp, th) for B, (H, W), T, bl, cu, spp, th in itertools.islice(grid3, 0, None, 23)]
+    cases += [("cspnk", K, gdt, B, H, W, T, bl, cu, spp, th) for K, gdt, B, (H, W), T, bl, cu, spp, th in itertools.islice(gridk, 0, None, 71)]
+    # the production shapes and the requests the thinning is most likely to miss: each workgroup size at the BASELINE configs
+    for B, H, W in ((24, 228, 304), (3, 228, 304), (1, 352, 1216), (8, 352, 1216)):
+        cases += [("cspn3", B, H, W, 24, bl, 256, 0, th) for bl in (0, 1) for th in (0, 512, 768, 1024)]
+        cases += [("cspnk", K, gdt, B, H, W, 12, bl, 256, 0, th) for K in (3, 5) for gdt in (_lib.CSPN_F16, _lib.CSPN_F32)
+                  for bl in (0, 1) for th in (0, 512, 768)]
+    return list(dict.fromkeys(cases))
+
+
+def _resident_plan_of(case):
+    from cspn_monodepth_amd import functional as F
+    if case[0] == "cspn3":
+        _, B, H, W, T, bl, cu, spp, th = case
+        p = F.resident_plan(B, H, W, T, bl, cu, steps_per_phase=spp, threads=th)
+    else:
+        _, K, gdt, B, H, W, T, bl, cu, spp, th = case
+        p = F.kres_plan(K, B, H, W, T, bl, cu, steps_per_phase=spp, threads=th, g_dtype=gdt)
+    return None if p is None else [p[name] for name in _PLAN_FIELDS]
+
+
+def make_resident_plan_table():
+    """Writes tests/golden/g20_resident_plans.json from the library in the tree.  Run once, at the commit whose plans are the
+    reference (`python -c "import test_abi_and_host as t; t.make_resident_plan_table()"` from tests/)."""
+    import json
+    rows = [list(case) + [_resident_plan_of(case)] for case in _resident_plan_cases()]
+    with open(_PLAN_TABLE, "w") as fh:
+        fh.write(json.dumps({"fields": list(_PLAN_FIELDS), "rows": rows}, separators=(",", ":")).replace("],[", "],\n["))
+        fh.write("\n")
+
+
+def test_resident_plans_match_the_recorded_table():
+    """cspn3_resident_plan / cspnk_resident_plan (pure host code with n_cu > 0) return, field for field, the plans recorded in
+    tests/golden/g20_resident_plans.json — or no plan where none was recorded — over a grid that reaches every branch of both
+    searches: one- and multi-launch batches, one and several phases, odd requests, the 512 / 768 (clipped) / 1024-thread 3x3
+    instances, both K, both guidance dtypes, widths that are no multiple of 4 / 8.  The table was written by
+    make_resident_plan_table() before the geometry code was restructured."""
+    import json
+    import numpy as np
+    table = json.load(open(_PLAN_TABLE))
+    assert tuple(table["fields"]) == _PLAN_FIELDS
+    rows = {tuple(r[:-1]): r[-1] for r in table["rows"]}
+    cases = _resident_plan_cases()
+    assert set(rows) == set(cases) and len(rows) == len(table["rows"])
+    fi = _PLAN_FIELDS.index("region_over_tile")
+    n_plans = 0
+    for case in cases:
+        want, got = rows[case], _resident_plan_of(case)
+        assert (want is None) == (got is None), (case, want, got)
+        if want is None:
+            continue
+        n_plans += 1
+        assert np.float32(got[fi]) == np.float32(want[fi]), (case, got[fi], want[fi])
+        assert got[:fi] + got[fi + 1:] == want[:fi] + want[fi + 1:], (case, dict(zip(_PLAN_FIELDS, got)), dict(zip(_PLAN_FIELDS, want)))
+    assert n_plans > len(cases) // 4                     # the grid is not mostly refusals
+
+
+def test_resident_entry_points_reject_bad_arguments_without_a_gpu():
+    """Every validation rule of the six weight-resident entry points that precedes the device query: the call returns 0 and
+    cspn_last_error() names the entry point and the rule.  The pointers (value 16, or 8 for a misaligned one) are never
+    dereferenced.  The rules that the three 3x3 entries share are checked by their common launcher, whose messages carry the
+    name cspn3_forward_resident.  Where there is no device, one fully valid call per entry point shows that validation lets it
+    through: it fails at the device query ("no device").  (With a device that call would launch on the made-up pointers, so it
+    is only made without one.)"""
+    L = _lib.lib()
+    F16, F32 = _lib.CSPN_F16, _lib.CSPN_F32
+    p, odd = 16, 8
+    B, H, W, T = 2, 8, 16, 4
+    no_device = not torch.cuda.is_available()
+
+    def run(entry, order, valid, rules, prefix=None):
+        fn = getattr(L, entry)
+        for change, rule, *who in rules:
+            args = dict(valid, **change)
+            assert fn(*[args[k] for k in order]) == 0, (entry, change)
+            msg = L.cspn_last_error().decode()
+            assert rule in msg and msg.startswith((who[0] if who else prefix or entry) + ":"), (entry, change, msg)
+        if no_device:
+            assert fn(*[valid[k] for k in order]) == 0
+            msg = L.cspn_last_error().decode()
+            assert "no device" in msg and msg.startswith((prefix or entry) + ":"), (entry, msg)
+
+    shape = dict(B=B, H=H, W=W, T=T)
+    seqs = [(dict(seq=0), "seq must be in [1, 2^31 - 256]"), (dict(seq=0x7fffff01), "seq must be in [1, 2^31 - 256]")]
+    q = "cspn3_forward_resident"                                     # the launcher the three 3x3 entries share
+
+    order = "g bs cs d0 sparse out hist w8 s_out work seq host_err B H W Wv T blend target acc nslots plan stream".split()
+    valid = dict(shape, g=p, bs=8 * H * W, cs=H * W, d0=p, sparse=None, out=p, hist=None, w8=None, s_out=None, work=p, seq=256, host_err=None,
+                 Wv=0, blend=0, target=None, acc=None, nslots=0, plan=None, stream=None)
+    run("cspn3_forward_resident", order, valid, [
+        (dict(g=None), "bad arguments"), (dict(B=0), "bad arguments"), (dict(H=-1), "bad arguments"), (dict(T=0), "bad arguments"),
+        (dict(out=None), "bad arguments"), (dict(blend=2), "blend 2"), (dict(blend=1), "blend needs sparse"),
+        (dict(target=p), "scoring needs target"), (dict(acc=p, nslots=1), "scoring needs target"),
+        (dict(target=p, acc=p, nslots=0), "scoring needs target"), (dict(d0=odd), "16-byte aligned"), (dict(work=odd), "16-byte aligned"),
+        (dict(sparse=odd, blend=1), "16-byte aligned"), (dict(target=odd, acc=p, nslots=1), "16-byte aligned"),
+        (dict(W=30, cs=H * 30, bs=8 * H * 30), "multiples of 4"), (dict(cs=H * W + 2), "multiples of 4"),
+        (dict(s_out=p), "outputs of the training form"), (dict(hist=p, out=None), "the training form (history) needs s_out"),
+        (dict(hist=odd, s_out=p, out=None), "16-byte aligned"), (dict(Wv=W + 1), "W_valid")] + seqs)
+
+    order = "w8 g_T sparse hist work seq host_err B H W Wv T premask plan stream".split()
+    valid = dict(shape, w8=p, g_T=p, sparse=None, hist=p, work=p, seq=256, host_err=None, Wv=0, premask=0, plan=None, stream=None)
+    run("cspn3_transposed_resident", order, valid, [
+        (dict(w8=None), "bad arguments", "cspn3_transposed_resident"), (dict(hist=None), "bad arguments", "cspn3_transposed_resident"),
+        (dict(B=0), "bad arguments"), (dict(work=None), "bad arguments"),
+        (dict(premask=1), "premask needs sparse", "cspn3_transposed_resident"),
+        (dict(hist=odd), "history must be 16-byte aligned", "cspn3_transposed_resident"),
+        (dict(g_T=odd), "16-byte aligned"), (dict(sparse=odd, premask=1), "16-byte aligned"), (dict(W=30), "multiples of 4")] + seqs, prefix=q)
+
+    order = "g bs cs S g_T sparse hist work seq host_err B H W Wv T premask plan stream".split()
+    valid = dict(shape, g=p, bs=8 * H * W, cs=H * W, S=p, g_T=p, sparse=None, hist=p, work=p, seq=256, host_err=None, Wv=0, premask=0,
+                 plan=None, stream=None)
+    e = "cspn3_transposed_resident_guidance"
+    run(e, order, valid, [
+        (dict(g=None), "bad arguments", e), (dict(S=None), "bad arguments", e), (dict(H=0), "bad arguments"),
+        (dict(premask=1), "premask needs sparse", e), (dict(S=odd), "S must be 16-byte aligned", e),
+        (dict(hist=odd), "history must be 16-byte aligned", "cspn3_transposed_resident"), (dict(g=odd), "16-byte aligned"),
+        (dict(W=30, cs=H * 30, bs=8 * H * 30), "multiples of 4"), (dict(bs=8 * H * W + 1), "multiples of 4")] + seqs, prefix=q)
+
+    order = "g g_dtype K x0 sparse out sdt work seq host_err B H W T blend target acc nslots plan stream".split()
+    valid = dict(shape, g=p, g_dtype=F16, K=5, x0=p, sparse=None, out=p, sdt=F16, work=p, seq=256, host_err=None, blend=0, target=None, acc=None,
+                 nslots=0, plan=None, stream=None)
+    run("cspnk_forward_resident", order, valid, [
+        (dict(g=None), "bad arguments"), (dict(out=None), "bad arguments"), (dict(B=0), "bad arguments"), (dict(T=0), "bad arguments"),
+        (dict(K=4), "K=4 (3 or 5)"), (dict(K=7), "K=7 (3 or 5)"), (dict(sdt=2), "state dtype 2"), (dict(g_dtype=2), "guidance dtype 2"),
+        (dict(g_dtype=F32), "fp32 guidance runs with fp32 depth planes"), (dict(blend=2), "blend 2"), (dict(blend=1), "blend needs sparse"),
+        (dict(target=p), "scoring needs target"), (dict(acc=p, nslots=1), "scoring needs target"), (dict(W=12), "multiple of 8"),
+        (dict(x0=odd), "16-byte aligned"), (dict(target=odd, acc=p, nslots=1), "16-byte aligned"), (dict(sparse=odd, blend=1), "16-byte aligned")] + seqs)
+    if no_device:                                   # K = 3 with fp32 guidance runs on the quad kernel: its launcher answers
+        args = dict(valid, K=3, g_dtype=F32, sdt=F32)
+        assert L.cspnk_forward_resident(*[args[k] for k in order]) == 0 and L.cspn_last_error().decode().endswith("no device")
+
+    order = "wk w_dtype K g_T sparse in_dtype g32 hist work seq host_err B H W T premask plan stream".split()
+    valid = dict(shape, wk=p, w_dtype=F16, K=5, g_T=p, sparse=None, in_dtype=F32, g32=None, hist=p, work=p, seq=256, host_err=None, premask=0,
+                 plan=None, stream=None)
+    run("cspnk_transposed_resident", order, valid, [
+        (dict(wk=None), "bad arguments"), (dict(hist=None), "bad arguments"), (dict(W=0), "bad arguments"),
+        (dict(K=3), "K = 5 with an fp16 tap volume"), (dict(w_dtype=F32), "K = 5 with an fp16 tap volume"),
+        (dict(premask=1), "premask needs sparse"), (dict(in_dtype=2), "bad in_dtype 2"),
+        (dict(g32=p), "g_T_f32_out goes with fp16 inputs"), (dict(g32=odd, in_dtype=F16), "g_T_f32_out goes with fp16 inputs"),
+        (dict(W=12), "multiple of 8"), (dict(g_T=odd), "16-byte aligned"), (dict(hist=odd), "16-byte aligned")] + seqs)
+
+    order = "g g_dtype K x0 sparse hist wk_out work seq host_err B H W T blend plan stream".split()
+    valid = dict(shape, g=p, g_dtype=F16, K=5, x0=p, sparse=None, hist=p, wk_out=p, work=p, seq=256, host_err=None, blend=0, plan=None, stream=None)
+    run("cspnk_forward_resident_history", order, valid, [
+        (dict(g=None), "bad arguments"), (dict(wk_out=None), "bad arguments"), (dict(B=-2), "bad arguments"),
+        (dict(K=4), "the training form exists for K = 3 with fp32 guidance and for K = 5 with fp16"),
+        (dict(g_dtype=F32), "the training form exists for K = 3 with fp32 guidance and for K = 5 with fp16"),
+        (dict(blend=2), "blend 2"), (dict(blend=1), "blend needs sparse"), (dict(W=12), "multiple of 8"),
+        (dict(hist=odd), "16-byte aligned"), (dict(wk_out=odd), "16-byte aligned")] + seqs)
+    if no_device:
+        args = dict(valid, K=3, g_dtype=F32)
+        assert L.cspnk_forward_resident_history(*[args[k] for k in order]) == 0 and L.cspn_last_error().decode().endswith("no device")
+
+
 def test_journal_entries_demote_to_weak_references():
     """Host logic of the resident launches' journal (no GPU needed): an old entry holds its tensors weakly — through the tensor
     that owns the storage, so that a view made inside the package can be rebuilt — and reports a dropped output as "nothing to

@@ -18,9 +18,9 @@ CSRC = os.path.join(_PKG, "csrc")
 SOURCES = ("cspn_propagate.hip", "cspn_resident.hip", "cspnk_resident.hip", "cspnk_d2.hip", "cspn_prepare.hip", "cspn_backward.hip", "cspn_metrics.hip", "cspn_metrics_frame.hip", "cspn_debug.hip", "cspn_repair.hip", "pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_criterion.hip", "cspn_max8.hip")   # one TU each
 HEADERS = (os.path.join(CSRC, "cspn_common.hpp"), os.path.join(CSRC, "cspnk_helpers.hpp"), os.path.join(_ROOT, "include", "cspn_hip.h"))
 INCLUDE = os.path.join(_ROOT, "include")
-# include/cspn_criterion.h, include/cspn_max8.h: part of the build's staleness hash, NOT of code_digest() — no benchmarked kernel sees it, and a
-# digest that moved would mark the HBM traffic recorded under profiles/ as stale (bench.py `traffic_stale`)
-BUILD_HEADERS = HEADERS + (os.path.join(INCLUDE, "cspn_criterion.h"), os.path.join(INCLUDE, "cspn_max8.h"))
+# include/cspn_criterion.h, include/cspn_max8.h, csrc/pac_launch.hpp: part of the build's staleness hash, NOT of code_digest() — no benchmarked
+# kernel sees it, and a digest that moved would mark the HBM traffic recorded under profiles/ as stale (bench.py `traffic_stale`)
+BUILD_HEADERS = HEADERS + (os.path.join(INCLUDE, "cspn_criterion.h"), os.path.join(INCLUDE, "cspn_max8.h"), os.path.join(CSRC, "pac_launch.hpp"))
 
 CSPN_F32, CSPN_F16 = 0, 1
 ABI_VERSION = 10         # CSPN_ABI_VERSION of include/cspn_hip.h this host code was written against

@@ -7,6 +7,7 @@
 // channels are walked CC at a time against the same kernel registers.  The K x K recurrence of CSPN_ours
 // (C = 1, stride 1, "same" padding, T steps) does NOT come through here — cspn_propagate keeps it in LDS.
 #include "cspn_common.hpp"
+#include "pac_launch.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -24,15 +25,9 @@ std::atomic<int>& force_generic_flag() {
     return flag;
 }
 
-// workgroups the any-geometry launches aim for (channel chunks / tap groups are split until there are that many): measured on
-// the C = 32 dilated row — 512 / 1024 / 2048 workgroups: forward 57 / 47 / 54 us; dL/dkernel with 1 / 2 tap groups: 58 / 88 us
 #ifndef CSPN_PAC_NT
 #define CSPN_PAC_NT 0          // developer A/B: 1 = non-temporal stores of the tiled kernels' results
 #endif
-#ifndef CSPN_PAC_WANT_WGS
-#define CSPN_PAC_WANT_WGS 1024
-#endif
-constexpr size_t ANY_WANT_WGS = CSPN_PAC_WANT_WGS, ANY_WANT_WGS_GK = 256;
 
 struct ConvArgs {
     int B, C, CK, H, W, Ho, Wo, WQ;      // WQ = ceil(Wo / 4) output quads per row
@@ -1252,21 +1247,18 @@ int make_args(const char* who, int dtype, int B, int C, int CK, int H, int W, co
     return 1;
 }
 
-// spread channels over blockIdx.y until the launch has enough workgroups to fill 256 CUs a few times over
-int channel_chunk(int C, size_t spatial_blocks) {
-    const size_t want = 2048;
-    if (spatial_blocks >= want || C <= CC) return C;
-    size_t nchunk = (want + spatial_blocks - 1) / spatial_blocks;
-    const size_t maxchunk = (size_t)ceil_div(C, CC);
-    if (nchunk > maxchunk) nchunk = maxchunk;
-    int per = ceil_div(C, (int)nchunk);
-    per = ceil_div(per, CC) * CC;
-    return per;
+// Generic one-quad kernels: spread channels over blockIdx.y until the launch has enough workgroups.  NOT split_channels alone:
+// a launch that stays whole (enough workgroups already, or a single batch of CC channels) keeps cchunk = C where the split rule
+// would round C up to CC.
+int generic_chunk(int C, size_t have) {
+    return (have >= GENERIC_WANT_WGS || C <= CC) ? C : split_channels(C, have, GENERIC_WANT_WGS, CC);
 }
 
 bool aligned_for(const void* p, int dtype) {
     return (reinterpret_cast<uintptr_t>(p) & (dtype == CSPN_F16 ? 7 : 15)) == 0;
 }
+bool aligned16(const void* p0, const void* p1) { return ((reinterpret_cast<uintptr_t>(p0) | reinterpret_cast<uintptr_t>(p1)) & 15) == 0; }
+template <typename T> constexpr int dtype_of = std::is_same<T, __half>::value ? CSPN_F16 : CSPN_F32;
 
 // stride 2 x 2, dilation 1, K in {3, 5}, padding K / 2, whole octets, 16-byte aligned bases: the register / DPP kernels of
 // pac_conv2d_s2.hip (no LDS staging, no tile quantisation)
@@ -1288,71 +1280,65 @@ bool tiled_geometry(const ConvArgs& a) {
     return a.kh == a.kw && (a.kh == 3 || a.kh == 5 || a.kh == 7) && a.sh == 1 && a.sw == 1 && a.dh == 1 && a.dw == 1;
 }
 
-// Launch of pac_conv2d_tiled for the forward (transposed = false) or the input gradient (true).
-template <typename T, int K, bool TRANSPOSED>
-int launch_tiled(const T* src, const T* kern, T* dst, const ConvArgs& a, int dst_vec, hipStream_t st) {
+// What the square-window tiled kernels derive from the geometry: forward-shaped (patches from the input, tile on the output
+// plane) or transposed (patches from grad_out, tile on the input plane).  tiles_x and cchunk (and the 1-D grid's lin_*) are the caller's.
+TiledArgs tiled_args(const ConvArgs& a, bool transposed, int K) {
     TiledArgs t{};
     t.B = a.B; t.C = a.C; t.CK = a.CK;
     t.k_h = a.Ho; t.k_w = a.Wo;
-    if (TRANSPOSED) {
+    if (transposed) {
         t.src_h = a.Ho; t.src_w = a.Wo; t.dst_h = a.H; t.dst_w = a.W;
         t.org_y = a.ph - (K - 1); t.org_x = a.pw - (K - 1);
     } else {
         t.src_h = a.H; t.src_w = a.W; t.dst_h = a.Ho; t.dst_w = a.Wo;
         t.org_y = -a.ph; t.org_x = -a.pw;
     }
-    t.k_vec = a.vec; t.dst_vec = dst_vec;
+    t.k_vec = t.dst_vec = a.vec;
+    return t;
+}
+
+// Launch of pac_conv2d_tiled for the forward (transposed = false) or the input gradient (true).
+template <typename T, int K, bool TRANSPOSED>
+int launch_tiled(const T* src, const T* kern, T* dst, const ConvArgs& a, int dst_vec, hipStream_t st) {
+    TiledArgs t = tiled_args(a, TRANSPOSED, K);
+    t.dst_vec = dst_vec;                                 // the input gradient lies on the input plane: its own alignment
+    const bool shared = a.CK == 1;
+    const dim3 block(256);
     if constexpr (std::is_same<T, __half>::value && !TRANSPOSED && K <= 5) {
         // fp16 forward with whole 16-byte octs everywhere: the eight-pixel kernel (2x the bytes per load instruction)
-        if (a.vec && dst_vec && t.dst_w % 8 == 0 && ((reinterpret_cast<uintptr_t>(kern) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+        if (a.vec && dst_vec && t.dst_w % 8 == 0 && aligned16(kern, dst)) {
             t.tiles_x = ceil_div(t.dst_w, TILE_W8);
             const int tiles8 = t.tiles_x * ceil_div(t.dst_h, TILE_H);
-            const size_t want8 = 1024, have8 = (size_t)tiles8 * a.B;
-            int nchunk8 = (int)std::min<size_t>((want8 + have8 - 1) / have8, (size_t)a.C);
-            if (a.CK != 1) nchunk8 = (int)std::min<size_t>((4 * want8 + have8 - 1) / have8, (size_t)a.C);
-            t.cchunk = ceil_div(a.C, std::max(nchunk8, 1));
+            t.cchunk = split_channels(a.C, (size_t)tiles8 * a.B, shared ? H8_WANT_WGS : PERCH_WANT_FACTOR * H8_WANT_WGS, 1);
             t.lin_tiles = tiles8; t.lin_chunks = ceil_div(a.C, t.cchunk);
-            const dim3 grid8 = lin_grid(tiles8, t.lin_chunks, a.B), block8(256);
-            if (a.CK == 1 && t.cchunk > 1) CSPN_PRE(st), pac_conv2d_tiled_h8<K, true><<<grid8, block8, 0, st>>>(src, kern, dst, t);
-            else CSPN_PRE(st), pac_conv2d_tiled_h8<K, false><<<grid8, block8, 0, st>>>(src, kern, dst, t);
-            HIP_OK(hipGetLastError());
-            return 1;
+            return with_bools([&](auto hoist) {
+                return launch(pac_conv2d_tiled_h8<K, hoist.value>, lin_grid(tiles8, t.lin_chunks, a.B), block, 0, st, src, kern, dst, t);
+            }, shared && t.cchunk > 1);
         }
     }
     t.tiles_x = ceil_div(t.dst_w, TILE_W);
     const int tiles = t.tiles_x * ceil_div(t.dst_h, TILE_H);
-    // every channel chunk re-reads the kernel planes, so only split as far as filling the chip needs (~4 x 256 groups)
-    const size_t want = ANY_WANT_WGS, have = (size_t)tiles * a.B;
-    int nchunk = (int)std::min<size_t>((want + have - 1) / have, (size_t)a.C);
-    if (a.CK != 1) nchunk = (int)std::min<size_t>((4 * want + have - 1) / have, (size_t)a.C);   // nothing is re-read
-    t.cchunk = ceil_div(a.C, std::max(nchunk, 1));
-    t.lin_tiles = tiles; t.lin_chunks = ceil_div(a.C, t.cchunk);
-    const dim3 grid = lin_grid(tiles, t.lin_chunks, a.B), block(256);
-    constexpr bool CAN_HOIST = K <= 5;                   // the whole window in registers
-    const bool hoist = CAN_HOIST && a.CK == 1;
+    const size_t have = (size_t)tiles * a.B;
+    t.lin_tiles = tiles;
     if constexpr (K > 5) {
         // a shared 7 x 7 kernel streams its 49 taps once per channel batch: batches of eight channels (101 KB of LDS, one
-        // workgroup per CU) halve that stream
-        if (a.CK == 1 && a.C >= 8) {
-            int nchunk8 = (int)std::min<size_t>((want + have - 1) / have, (size_t)ceil_div(a.C, 8));
-            t.cchunk = ceil_div(ceil_div(a.C, std::max(nchunk8, 1)), 8) * 8;
+        // workgroup per CU) halve that stream; a chunk that is a single batch needs no second LDS buffer
+        if (shared && a.C >= 8) {
+            t.cchunk = split_channels(a.C, have, ANY_WANT_WGS, 8);
             t.lin_chunks = ceil_div(a.C, t.cchunk);
-            const dim3 grid8 = lin_grid(tiles, t.lin_chunks, a.B);
-            if (t.cchunk <= 8) CSPN_PRE(st), pac_conv2d_tiled<T, K, false, 8, TRANSPOSED, 1><<<grid8, block, 0, st>>>(src, kern, dst, t);
-            else CSPN_PRE(st), pac_conv2d_tiled<T, K, false, 8, TRANSPOSED><<<grid8, block, 0, st>>>(src, kern, dst, t);
-            HIP_OK(hipGetLastError());
-            return 1;
+            return with_bools([&](auto single) {
+                return launch(pac_conv2d_tiled<T, K, false, 8, TRANSPOSED, single.value ? 1 : 2>, lin_grid(tiles, t.lin_chunks, a.B), block, 0,
+                              st, src, kern, dst, t);
+            }, t.cchunk <= 8);
         }
     }
-    if (t.cchunk == 1) {
-        if (hoist) CSPN_PRE(st), pac_conv2d_tiled<T, K, CAN_HOIST, 1, TRANSPOSED><<<grid, block, 0, st>>>(src, kern, dst, t);
-        else CSPN_PRE(st), pac_conv2d_tiled<T, K, false, 1, TRANSPOSED><<<grid, block, 0, st>>>(src, kern, dst, t);
-    } else {
-        if (hoist) CSPN_PRE(st), pac_conv2d_tiled<T, K, CAN_HOIST, CC, TRANSPOSED><<<grid, block, 0, st>>>(src, kern, dst, t);
-        else CSPN_PRE(st), pac_conv2d_tiled<T, K, false, CC, TRANSPOSED><<<grid, block, 0, st>>>(src, kern, dst, t);
-    }
-    HIP_OK(hipGetLastError());
-    return 1;
+    t.cchunk = split_channels(a.C, have, shared ? ANY_WANT_WGS : PERCH_WANT_FACTOR * ANY_WANT_WGS, 1);
+    t.lin_chunks = ceil_div(a.C, t.cchunk);
+    // K <= 5: the whole window of a shared kernel stays in registers (HOIST); single-channel chunks take the CB = 1 instance
+    return with_bools([&](auto hoist, auto one) {
+        return launch(pac_conv2d_tiled<T, K, (K <= 5) && hoist.value, one.value ? 1 : CC, TRANSPOSED>, lin_grid(tiles, t.lin_chunks, a.B), block, 0,
+                      st, src, kern, dst, t);
+    }, shared, t.cchunk == 1);
 }
 
 template <typename T, bool TRANSPOSED>
@@ -1362,246 +1348,170 @@ int launch_tiled_k(const T* src, const T* kern, T* dst, const ConvArgs& a, int d
                      : launch_tiled<T, 7, TRANSPOSED>(src, kern, dst, a, dst_vec, st);
 }
 
+// LDS patch of the any-geometry kernels: the source extent a 64 x 16 tile touches, and how many channels of it (cb <= CC) fit
+// 64 KiB — cb = 0: not even one, the caller stays on the generic kernel.  Transposed (dL/dinput): the grad_out patch the tile
+// gathers from has the extents of the forward's input patch at unit stride.  The only transposed caller already requires unit
+// stride, so today the flag changes no value: it records that the transposed kernel never applies a stride to its patch.
+struct AnyPatch {
+    int RW, RH, cb;
+    size_t lds_bytes;
+};
+AnyPatch any_patch(const ConvArgs& a, bool transposed) {
+    const long sh = transposed ? 1 : a.sh, sw = transposed ? 1 : a.sw;
+    const long RW = ((TILE_W - 1) * sw + (long)(a.kw - 1) * a.dw + 1 + 3) & ~3L;
+    const long RH = (TILE_H - 1) * sh + (long)(a.kh - 1) * a.dh + 1;
+    const long psz = RW * RH;
+    const int cb = std::min((int)std::min<long>(CC, (64 * 1024 / 4) / std::max(psz, 1L)), a.C);
+    return {(int)RW, (int)RH, cb, (size_t)cb * psz * sizeof(float)};
+}
+
+// Launch of pac_conv2d_fwd_tiled_any for the forward (tile on the output plane) or the input gradient (TRANSPOSED: on the input plane).
+template <typename T, bool TRANSPOSED>
+int launch_tiled_any(const T* src, const T* kern, T* dst, ConvArgs a, const AnyPatch& p, hipStream_t st) {
+    const int tiles_x = ceil_div(TRANSPOSED ? a.W : a.Wo, TILE_W), tiles = tiles_x * ceil_div(TRANSPOSED ? a.H : a.Ho, TILE_H);
+    a.cchunk = split_channels(a.C, (size_t)tiles * a.B, ANY_WANT_WGS, p.cb);
+    a.lin_tiles = tiles; a.lin_chunks = ceil_div(a.C, a.cchunk);
+    // the hoisted instance (<= 9 taps in registers) exists for shared kernels only
+    return with_bools([&](auto shared, auto few) {
+        return launch(pac_conv2d_fwd_tiled_any<T, shared.value, TRANSPOSED, shared.value && few.value>, lin_grid(tiles, a.lin_chunks, a.B),
+                      dim3(256), p.lds_bytes, st, src, kern, dst, a, tiles_x, p.RW, p.RH, p.cb);
+    }, a.CK == 1, a.kh * a.kw <= 9);
+}
+
 template <typename T>
 int conv_forward_typed(const void* in, const void* kern, void* out, ConvArgs a, hipStream_t st) {
-    if (s2_fast(a, in, kern, out))
-        return cspn_detail::pac_s2_forward(in, kern, out, std::is_same<T, __half>::value ? CSPN_F16 : CSPN_F32, a.kh, s2_args(a), st);
-    if (tiled_geometry(a) && !a.force_scalar) {
-        const T* i = static_cast<const T*>(in);
-        const T* k = static_cast<const T*>(kern);
-        T* o = static_cast<T*>(out);
-        return launch_tiled_k<T, false>(i, k, o, a, a.vec, st);
-    }
     const T* i = static_cast<const T*>(in);
     const T* k = static_cast<const T*>(kern);
     T* o = static_cast<T*>(out);
-    const bool shared = a.CK == 1;
+    if (s2_fast(a, in, kern, out)) return cspn_detail::pac_s2_forward(in, kern, out, dtype_of<T>, a.kh, s2_args(a), st);
+    if (tiled_geometry(a) && !a.force_scalar) return launch_tiled_k<T, false>(i, k, o, a, a.vec, st);
     if (!a.force_scalar && (size_t)a.H * a.W < ((size_t)1 << 31)) {
         // every other geometry (stride, dilation, non-square or even windows): LDS-tiled when the input patch of a 64 x 16
         // output tile fits 64 KiB for at least one channel.  (Strided windows used to stay on the scalar kernel — their
         // patches are stride^2 larger per output and the tiled form measured 87 vs 77 us at stride 2; that was the old
         // staging loop, four loads in flight per wavefront: with stage_patch_any it is 42 vs 76 us.)
-        const long RWl = ((long)(TILE_W - 1) * a.sw + (long)(a.kw - 1) * a.dw + 1 + 3) & ~3L;
-        const long RHl = (long)(TILE_H - 1) * a.sh + (long)(a.kh - 1) * a.dh + 1;
-        const long psz = RWl * RHl;
-        int cb = (int)std::min<long>(CC, (64 * 1024 / 4) / std::max(psz, 1L));
-        cb = std::min(cb, a.C);
-        if (cb >= 1) {
-            const int tiles_x = ceil_div(a.Wo, TILE_W), tiles = tiles_x * ceil_div(a.Ho, TILE_H);
-            const size_t want = ANY_WANT_WGS, have = (size_t)tiles * a.B;
-            int nchunk = (int)std::min<size_t>((want + have - 1) / have, (size_t)ceil_div(a.C, cb));
-            a.cchunk = ceil_div(ceil_div(a.C, std::max(nchunk, 1)), cb) * cb;
-            a.lin_tiles = tiles; a.lin_chunks = ceil_div(a.C, a.cchunk);
-            const dim3 grid = lin_grid(tiles, a.lin_chunks, a.B), block(256);
-            const size_t lds = (size_t)cb * psz * sizeof(float);
-            if (shared && a.kh * a.kw <= 9) CSPN_PRE(st), pac_conv2d_fwd_tiled_any<T, true, false, true><<<grid, block, lds, st>>>(i, k, o, a, tiles_x, (int)RWl, (int)RHl, cb);
-            else if (shared) CSPN_PRE(st), pac_conv2d_fwd_tiled_any<T, true, false, false><<<grid, block, lds, st>>>(i, k, o, a, tiles_x, (int)RWl, (int)RHl, cb);
-            else CSPN_PRE(st), pac_conv2d_fwd_tiled_any<T, false, false, false><<<grid, block, lds, st>>>(i, k, o, a, tiles_x, (int)RWl, (int)RHl, cb);
-            HIP_OK(hipGetLastError());
-            return 1;
-        }
+        const AnyPatch p = any_patch(a, false);
+        if (p.cb >= 1) return launch_tiled_any<T, false>(i, k, o, a, p, st);
     }
     const int gx = ceil_div(a.Ho * a.WQ, 256);
-    a.cchunk = channel_chunk(a.C, (size_t)gx * a.B);
-    const dim3 grid(gx, ceil_div(a.C, a.cchunk), a.B), block(256);
-    if (a.vec && shared) CSPN_PRE(st), pac_conv2d_fwd<T, true, true><<<grid, block, 0, st>>>(i, k, o, a);
-    else if (a.vec) CSPN_PRE(st), pac_conv2d_fwd<T, true, false><<<grid, block, 0, st>>>(i, k, o, a);
-    else if (shared) CSPN_PRE(st), pac_conv2d_fwd<T, false, true><<<grid, block, 0, st>>>(i, k, o, a);
-    else CSPN_PRE(st), pac_conv2d_fwd<T, false, false><<<grid, block, 0, st>>>(i, k, o, a);
-    HIP_OK(hipGetLastError());
-    return 1;
+    a.cchunk = generic_chunk(a.C, (size_t)gx * a.B);
+    return with_bools([&](auto vec, auto shared) {
+        return launch(pac_conv2d_fwd<T, vec.value, shared.value>, dim3(gx, ceil_div(a.C, a.cchunk), a.B), dim3(256), 0, st, i, k, o, a);
+    }, a.vec != 0, a.CK == 1);
 }
 
 template <typename T, int K>
-int conv_gk_tiled(const T* g, const T* in, T* gk, ConvArgs a, hipStream_t st) {
+int conv_gk_tiled(const T* g, const T* in, T* gk, const ConvArgs& a, hipStream_t st) {
     const int tiles_x = ceil_div(a.Wo, TILE_W), tiles = tiles_x * ceil_div(a.Ho, TILE_H);
+    const size_t have = (size_t)tiles * a.B;
+    const bool shared = a.CK == 1;
+    const dim3 block(256);
+    TiledArgs t = tiled_args(a, false, K);
     if constexpr (std::is_same<T, __half>::value && K <= 5) {
         // fp16, no sum over channels (CK == C), whole 16-byte octs: the eight-pixel outer-product kernel
-        if (a.CK == a.C && a.vec && a.Wo % 8 == 0 &&
-            ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(gk)) & 15) == 0) {
-            TiledArgs t{};
-            t.B = a.B; t.C = a.C; t.CK = a.CK;
-            t.src_h = a.H; t.src_w = a.W; t.dst_h = a.Ho; t.dst_w = a.Wo; t.k_h = a.Ho; t.k_w = a.Wo;
-            t.org_y = -a.ph; t.org_x = -a.pw;
-            t.k_vec = t.dst_vec = a.vec;
+        if (a.CK == a.C && a.vec && a.Wo % 8 == 0 && aligned16(g, gk)) {
             t.tiles_x = ceil_div(a.Wo, TILE_W8);
             const int tiles8 = t.tiles_x * ceil_div(a.Ho, TILE_H);
-            const int nchunk = (int)std::min<size_t>((4096 + (size_t)tiles8 * a.B - 1) / ((size_t)tiles8 * a.B), (size_t)a.C);
-            t.cchunk = ceil_div(a.C, std::max(nchunk, 1));
-            const dim3 grid8(tiles8, ceil_div(a.C, t.cchunk), a.B), block8(256);
-            CSPN_PRE(st), pac_conv2d_gk_h8<K><<<grid8, block8, 0, st>>>(g, in, gk, t);
-            HIP_OK(hipGetLastError());
-            return 1;
+            t.cchunk = split_channels(a.C, (size_t)tiles8 * a.B, GK_WANT_WGS, 1);
+            return launch(pac_conv2d_gk_h8<K>, dim3(tiles8, ceil_div(a.C, t.cchunk), a.B), block, 0, st, g, in, gk, t);
         }
     }
+    t.tiles_x = tiles_x;
     if constexpr (K <= 5) {
         // whole-window kernel; a shared kernel pins all channels to one workgroup, so it needs enough tiles to fill the
         // chip — small launches keep the tap-row split below (K x the workgroups)
-        if (a.CK != 1 || (size_t)tiles * a.B >= 256) {
-            TiledArgs t{};
-            t.B = a.B; t.C = a.C; t.CK = a.CK;
-            t.src_h = a.H; t.src_w = a.W; t.dst_h = a.Ho; t.dst_w = a.Wo; t.k_h = a.Ho; t.k_w = a.Wo;
-            t.org_y = -a.ph; t.org_x = -a.pw;
-            t.k_vec = t.dst_vec = a.vec;
-            t.tiles_x = tiles_x;
-            int nchunk = 1;
-            if (a.CK != 1) nchunk = (int)std::min<size_t>((4096 + (size_t)tiles * a.B - 1) / ((size_t)tiles * a.B), (size_t)a.C);
-            t.cchunk = ceil_div(a.C, nchunk);
-            const dim3 grid(tiles, ceil_div(a.C, t.cchunk), a.B), block(256);
-            if (a.CK == 1) {
-                if (a.C == 1) CSPN_PRE(st), pac_conv2d_gk_window<T, K, true, 1><<<grid, block, 0, st>>>(g, in, gk, t);
-                else CSPN_PRE(st), pac_conv2d_gk_window<T, K, true, CC><<<grid, block, 0, st>>>(g, in, gk, t);
-            } else {
-                if (t.cchunk == 1) CSPN_PRE(st), pac_conv2d_gk_window<T, K, false, 1><<<grid, block, 0, st>>>(g, in, gk, t);
-                else CSPN_PRE(st), pac_conv2d_gk_window<T, K, false, CC><<<grid, block, 0, st>>>(g, in, gk, t);
-            }
-            HIP_OK(hipGetLastError());
-            return 1;
+        if (!shared || have >= 256) {
+            t.cchunk = shared ? a.C : split_channels(a.C, have, GK_WANT_WGS, 1);
+            return with_bools([&](auto sh, auto one) {
+                return launch(pac_conv2d_gk_window<T, K, sh.value, one.value ? 1 : CC>, dim3(tiles, ceil_div(a.C, t.cchunk), a.B), block, 0, st,
+                              g, in, gk, t);
+            }, shared, t.cchunk == 1);
         }
     }
     if constexpr (K == 7) {
         // shared 7 x 7: the tap-row split below reads grad_out and the input seven times; with enough tiles the whole window
         // (49 accumulator quads) stays in the registers of one workgroup instead
-        if (a.CK == 1 && (size_t)tiles * a.B >= 256) {
-            TiledArgs t{};
-            t.B = a.B; t.C = a.C; t.CK = a.CK;
-            t.src_h = a.H; t.src_w = a.W; t.dst_h = a.Ho; t.dst_w = a.Wo; t.k_h = a.Ho; t.k_w = a.Wo;
-            t.org_y = -a.ph; t.org_x = -a.pw;
-            t.k_vec = t.dst_vec = a.vec;
-            t.tiles_x = tiles_x;
+        if (shared && have >= 256) {
             t.cchunk = a.C;
-            const dim3 gridw(tiles, 1, a.B), blockw(256);
             // one channel per batch: 247 VGPRs, two wavefronts per SIMD (two channels: 256 + spills to AGPRs, one wavefront —
             // 67.8 vs 52.3 us; the tap-row split: 125.9 us)
-            CSPN_PRE(st), pac_conv2d_gk_window<T, K, true, 1><<<gridw, blockw, 0, st>>>(g, in, gk, t);
-            HIP_OK(hipGetLastError());
-            return 1;
+            return launch(pac_conv2d_gk_window<T, K, true, 1>, dim3(tiles, 1, a.B), block, 0, st, g, in, gk, t);
         }
     }
-    const dim3 grid(tiles, K, a.B), block(256);
-    if (a.CK == 1) CSPN_PRE(st), pac_conv2d_gk_tiled<T, K, true><<<grid, block, 0, st>>>(g, in, gk, a, tiles_x);
-    else CSPN_PRE(st), pac_conv2d_gk_tiled<T, K, false><<<grid, block, 0, st>>>(g, in, gk, a, tiles_x);
-    HIP_OK(hipGetLastError());
-    return 1;
+    return with_bools([&](auto sh) {
+        return launch(pac_conv2d_gk_tiled<T, K, sh.value>, dim3(tiles, K, a.B), block, 0, st, g, in, gk, a, tiles_x);
+    }, shared);
 }
 
 template <typename T>
 int conv_gk_typed(const void* gout, const void* in, void* gk, ConvArgs a, hipStream_t st) {
-    if (s2_fast(a, gout, in, gk))
-        return cspn_detail::pac_s2_grad_kernel(gout, in, gk, std::is_same<T, __half>::value ? CSPN_F16 : CSPN_F32, a.kh, s2_args(a), st);
-    if (tiled_geometry(a) && !a.force_scalar) {
-        const T* g = static_cast<const T*>(gout);
-        const T* i = static_cast<const T*>(in);
-        T* o = static_cast<T*>(gk);
+    const T* g = static_cast<const T*>(gout);
+    const T* i = static_cast<const T*>(in);
+    T* o = static_cast<T*>(gk);
+    if (s2_fast(a, gout, in, gk)) return cspn_detail::pac_s2_grad_kernel(gout, in, gk, dtype_of<T>, a.kh, s2_args(a), st);
+    if (tiled_geometry(a) && !a.force_scalar)
         return a.kh == 3 ? conv_gk_tiled<T, 3>(g, i, o, a, st)
              : a.kh == 5 ? conv_gk_tiled<T, 5>(g, i, o, a, st) : conv_gk_tiled<T, 7>(g, i, o, a, st);
-    }
+    const dim3 block(256);
     if (!a.force_scalar && a.sh == 1 && a.sw == 1 && (size_t)a.H * a.W < ((size_t)1 << 31) &&
         (size_t)a.Ho * a.Wo < ((size_t)1 << 31)) {
         // other unit-stride windows: input patch in LDS, all taps (per-channel kernel) or a group of <= 9 taps (shared kernel:
         // the sum over channels stays in registers) per workgroup.  (The kernel takes strides too, but a strided window's
         // patch is stride^2 larger per output: 85 vs 70 us for the scalar kernel at stride 2.)
         constexpr int NTM = 9;
-        const long RWl = ((long)(TILE_W - 1) * a.sw + (long)(a.kw - 1) * a.dw + 1 + 3) & ~3L;
-        const long RHl = (long)(TILE_H - 1) * a.sh + (long)(a.kh - 1) * a.dh + 1;
-        const long psz = RWl * RHl;
-        int cb = (int)std::min<long>(CC, (64 * 1024 / 4) / std::max(psz, 1L));
-        cb = std::min(cb, a.C);
-        if (cb >= 1) {
+        const AnyPatch p = any_patch(a, false);
+        if (p.cb >= 1) {
             const int tiles_x = ceil_div(a.Wo, TILE_W), tiles = tiles_x * ceil_div(a.Ho, TILE_H);
             const int ntap = a.kh * a.kw;
             const size_t have = (size_t)tiles * a.B;
-            const size_t lds = (size_t)cb * psz * sizeof(float);
-            const T* g = static_cast<const T*>(gout);
-            const T* i = static_cast<const T*>(in);
-            T* o = static_cast<T*>(gk);
             if (a.CK == 1) {
-                // enough workgroups to fill the chip: split the taps into more groups when there are few tiles
-                const int want_groups = (int)std::min<size_t>((size_t)ntap, (ANY_WANT_WGS_GK + have - 1) / have);
+                // enough workgroups to fill the chip: split the taps into more groups when there are few tiles.  (Not the channel
+                // rule: a group is capped at the NTM accumulators of the kernel, not rounded up to a batch.)
+                const int want_groups = (int)std::min<size_t>((size_t)ntap, (GK_ANY_TAPGROUP_WANT_WGS + have - 1) / have);
                 const int tpg = std::max(1, std::min(NTM, ceil_div(ntap, std::max(want_groups, 1))));
-                const dim3 grid(tiles, ceil_div(ntap, tpg), a.B), block(256);
-                CSPN_PRE(st), pac_conv2d_gk_any<T, true, NTM><<<grid, block, lds, st>>>(g, i, o, a, tiles_x, (int)RWl, (int)RHl, cb, tpg);
-            } else {
-                int nchunk = (int)std::min<size_t>((1024 + have - 1) / have, (size_t)ceil_div(a.C, cb));
-                a.cchunk = ceil_div(ceil_div(a.C, std::max(nchunk, 1)), cb) * cb;
-                const dim3 grid(tiles, ceil_div(a.C, a.cchunk), a.B), block(256);
-                CSPN_PRE(st), pac_conv2d_gk_any<T, false, NTM><<<grid, block, lds, st>>>(g, i, o, a, tiles_x, (int)RWl, (int)RHl, cb, 0);
+                return launch(pac_conv2d_gk_any<T, true, NTM>, dim3(tiles, ceil_div(ntap, tpg), a.B), block, p.lds_bytes, st, g, i, o, a,
+                              tiles_x, p.RW, p.RH, p.cb, tpg);
             }
-            HIP_OK(hipGetLastError());
-            return 1;
+            a.cchunk = split_channels(a.C, have, GK_ANY_WANT_WGS, p.cb);
+            return launch(pac_conv2d_gk_any<T, false, NTM>, dim3(tiles, ceil_div(a.C, a.cchunk), a.B), block, p.lds_bytes, st, g, i, o, a,
+                          tiles_x, p.RW, p.RH, p.cb, 0);
         }
     }
-    const dim3 grid(ceil_div(a.Ho * a.WQ, 256), a.kh * a.kw, a.B), block(256);
-    const T* g = static_cast<const T*>(gout);
-    const T* i = static_cast<const T*>(in);
-    T* o = static_cast<T*>(gk);
-    const bool shared = a.CK == 1;
-    if (a.vec && shared) CSPN_PRE(st), pac_conv2d_gk<T, true, true><<<grid, block, 0, st>>>(g, i, o, a);
-    else if (a.vec) CSPN_PRE(st), pac_conv2d_gk<T, true, false><<<grid, block, 0, st>>>(g, i, o, a);
-    else if (shared) CSPN_PRE(st), pac_conv2d_gk<T, false, true><<<grid, block, 0, st>>>(g, i, o, a);
-    else CSPN_PRE(st), pac_conv2d_gk<T, false, false><<<grid, block, 0, st>>>(g, i, o, a);
-    HIP_OK(hipGetLastError());
-    return 1;
+    return with_bools([&](auto vec, auto shared) {
+        return launch(pac_conv2d_gk<T, vec.value, shared.value>, dim3(ceil_div(a.Ho * a.WQ, 256), a.kh * a.kw, a.B), block, 0, st, g, i, o, a);
+    }, a.vec != 0, a.CK == 1);
 }
 
 template <typename T>
 int conv_gi_typed(const void* gout, const void* kern, void* gin, ConvArgs a, int in_vec, hipStream_t st) {
-    if (s2_fast(a, gout, kern, gin))
-        return cspn_detail::pac_s2_grad_input(gout, kern, gin, std::is_same<T, __half>::value ? CSPN_F16 : CSPN_F32, a.kh, s2_args(a), st);
-    if (tiled_geometry(a) && !a.force_scalar && (size_t)a.Ho * a.Wo < ((size_t)1 << 31))
-        return launch_tiled_k<T, true>(static_cast<const T*>(gout), static_cast<const T*>(kern), static_cast<T*>(gin), a,
-                                       in_vec, st);
-    if (!a.force_scalar && a.sh == 1 && a.sw == 1 && (size_t)a.H * a.W < ((size_t)1 << 31) &&
-        (size_t)a.Ho * a.Wo < ((size_t)1 << 31)) {
-        // other unit-stride windows (dilated, non-square, even): the any-geometry tiled kernel, transposed — the tile lies
-        // on the input plane, the grad_out patch it gathers from has the extents of the forward's input patch
-        const long RWl = ((long)(TILE_W - 1) + (long)(a.kw - 1) * a.dw + 1 + 3) & ~3L;
-        const long RHl = (long)(TILE_H - 1) + (long)(a.kh - 1) * a.dh + 1;
-        const long psz = RWl * RHl;
-        int cb = (int)std::min<long>(CC, (64 * 1024 / 4) / std::max(psz, 1L));
-        cb = std::min(cb, a.C);
-        if (cb >= 1) {
-            const int tiles_x = ceil_div(a.W, TILE_W), tiles = tiles_x * ceil_div(a.H, TILE_H);
-            const size_t want = ANY_WANT_WGS, have = (size_t)tiles * a.B;
-            int nchunk = (int)std::min<size_t>((want + have - 1) / have, (size_t)ceil_div(a.C, cb));
-            a.cchunk = ceil_div(ceil_div(a.C, std::max(nchunk, 1)), cb) * cb;
-            a.lin_tiles = tiles; a.lin_chunks = ceil_div(a.C, a.cchunk);
-            const dim3 grid = lin_grid(tiles, a.lin_chunks, a.B), block(256);
-            const size_t lds = (size_t)cb * psz * sizeof(float);
-            const T* g = static_cast<const T*>(gout);
-            const T* k = static_cast<const T*>(kern);
-            T* o = static_cast<T*>(gin);
-            if (a.CK == 1 && a.kh * a.kw <= 9) CSPN_PRE(st), pac_conv2d_fwd_tiled_any<T, true, true, true><<<grid, block, lds, st>>>(g, k, o, a, tiles_x, (int)RWl, (int)RHl, cb);
-            else if (a.CK == 1) CSPN_PRE(st), pac_conv2d_fwd_tiled_any<T, true, true, false><<<grid, block, lds, st>>>(g, k, o, a, tiles_x, (int)RWl, (int)RHl, cb);
-            else CSPN_PRE(st), pac_conv2d_fwd_tiled_any<T, false, true, false><<<grid, block, lds, st>>>(g, k, o, a, tiles_x, (int)RWl, (int)RHl, cb);
-            HIP_OK(hipGetLastError());
-            return 1;
-        }
-    }
-    const int in_wq = ceil_div(a.W, 4);
-    const int gx = ceil_div(a.H * in_wq, 256);
-    a.cchunk = channel_chunk(a.C, (size_t)gx * a.B);
-    const dim3 grid(gx, ceil_div(a.C, a.cchunk), a.B), block(256);
     const T* g = static_cast<const T*>(gout);
     const T* k = static_cast<const T*>(kern);
     T* o = static_cast<T*>(gin);
-    const bool shared = a.CK == 1, unit = a.sh == 1 && a.sw == 1;
-    if (shared && unit) CSPN_PRE(st), pac_conv2d_gi<T, true, true><<<grid, block, 0, st>>>(g, k, o, a, in_wq, in_vec);
-    else if (shared) CSPN_PRE(st), pac_conv2d_gi<T, true, false><<<grid, block, 0, st>>>(g, k, o, a, in_wq, in_vec);
-    else if (unit) CSPN_PRE(st), pac_conv2d_gi<T, false, true><<<grid, block, 0, st>>>(g, k, o, a, in_wq, in_vec);
-    else CSPN_PRE(st), pac_conv2d_gi<T, false, false><<<grid, block, 0, st>>>(g, k, o, a, in_wq, in_vec);
-    HIP_OK(hipGetLastError());
-    return 1;
+    if (s2_fast(a, gout, kern, gin)) return cspn_detail::pac_s2_grad_input(gout, kern, gin, dtype_of<T>, a.kh, s2_args(a), st);
+    if (tiled_geometry(a) && !a.force_scalar && (size_t)a.Ho * a.Wo < ((size_t)1 << 31))
+        return launch_tiled_k<T, true>(g, k, o, a, in_vec, st);
+    if (!a.force_scalar && a.sh == 1 && a.sw == 1 && (size_t)a.H * a.W < ((size_t)1 << 31) &&
+        (size_t)a.Ho * a.Wo < ((size_t)1 << 31)) {
+        // other unit-stride windows (dilated, non-square, even): the any-geometry tiled kernel, transposed
+        const AnyPatch p = any_patch(a, true);
+        if (p.cb >= 1) return launch_tiled_any<T, true>(g, k, o, a, p, st);
+    }
+    const int in_wq = ceil_div(a.W, 4);
+    const int gx = ceil_div(a.H * in_wq, 256);
+    a.cchunk = generic_chunk(a.C, (size_t)gx * a.B);
+    return with_bools([&](auto shared, auto unit) {
+        return launch(pac_conv2d_gi<T, shared.value, unit.value>, dim3(gx, ceil_div(a.C, a.cchunk), a.B), dim3(256), 0, st, g, k, o, a, in_wq,
+                      in_vec);
+    }, a.CK == 1, a.sh == 1 && a.sw == 1);
 }
 
 template <typename T>
-int nd2col_typed(const void* in, void* cols, ConvArgs a, hipStream_t st) {
+int nd2col_typed(const void* in, void* cols, const ConvArgs& a, hipStream_t st) {
     if ((long)a.B * a.C > 65535) return fail("cspn_pac_nd2col: B*C=%ld exceeds the grid limit 65535", (long)a.B * a.C);
-    const dim3 grid(ceil_div(a.Ho * a.WQ, 256), a.kh * a.kw, a.B * a.C), block(256);
-    if (a.vec) CSPN_PRE(st), pac_nd2col_kernel<T, true><<<grid, block, 0, st>>>(static_cast<const T*>(in), static_cast<T*>(cols), a);
-    else CSPN_PRE(st), pac_nd2col_kernel<T, false><<<grid, block, 0, st>>>(static_cast<const T*>(in), static_cast<T*>(cols), a);
-    HIP_OK(hipGetLastError());
-    return 1;
+    return with_bools([&](auto vec) {
+        return launch(pac_nd2col_kernel<T, vec.value>, dim3(ceil_div(a.Ho * a.WQ, 256), a.kh * a.kw, a.B * a.C), dim3(256), 0, st,
+                      static_cast<const T*>(in), static_cast<T*>(cols), a);
+    }, a.vec != 0);
 }
 
 }  // namespace

@@ -22,6 +22,7 @@
 // Accumulation is fp32 for both storage types.  A zero of the padding still multiplies the kernel value in the forward
 // (0 * inf = NaN, as F.unfold * kernel does); in dL/dinput a window position outside grad_out contributes no term at all.
 #include "cspn_common.hpp"
+#include "pac_launch.hpp"
 
 #include <algorithm>
 
@@ -446,53 +447,29 @@ __global__ __launch_bounds__(256) void pac_s2_gi(const T* __restrict__ gout, con
 }
 
 // ------------------------------------------------------------------------------------------------ host
-#ifndef CSPN_S2_WANT
-#define CSPN_S2_WANT 1024      // workgroups a chunked launch aims for (channel chunks are split until there are that many)
-#endif
-// 1-D grid of the chunked launches: the spatial blocks of all images padded to a multiple of 8, times the chunks (see chunked_id)
-inline dim3 chunked_grid(PacS2Args& a, int gx) {
-    a.gx = gx;
+// 1-D grid of the chunked launches: the spatial blocks of all images padded to a multiple of 8, times the chunks (see chunked_id).
+// Channel chunks are split until there are S2_WANT_WGS workgroups.  NOT split_channels alone: a launch that has enough spatial
+// blocks already keeps cchunk = C where the split rule would round C up to the batch CB.
+inline dim3 chunked_grid(PacS2Args& a, int CB) {
+    a.gx = ceil_div(a.Ho * a.WQ, 256);
+    const size_t have = (size_t)a.gx * a.B;
+    a.cchunk = have >= S2_WANT_WGS ? a.C : split_channels(a.C, have, S2_WANT_WGS, CB);
     a.nchunk = ceil_div(a.C, a.cchunk);
-    return dim3((unsigned)(ceil_div(gx * a.B, 8) * 8 * a.nchunk));
+    return dim3((unsigned)(ceil_div(a.gx * a.B, 8) * 8 * a.nchunk));
 }
 
-inline int chunk_for(int C, size_t spatial_blocks, int CB, size_t want) {
-    if (spatial_blocks >= want) return C;
-    size_t nchunk = (want + spatial_blocks - 1) / spatial_blocks;
-    const size_t maxchunk = (size_t)ceil_div(C, CB);
-    nchunk = std::min(nchunk, maxchunk);
-    const int per = ceil_div(C, (int)nchunk);
-    return ceil_div(per, CB) * CB;
-}
-
-template <typename T, int K>
-int forward_k(const void* in_, const void* kern_, void* out_, PacS2Args a, hipStream_t st) {
-    const T* in = static_cast<const T*>(in_);
+// forward (src = input) or dL/dinput (src = grad_out): the same launch around two kernels
+template <typename T, int K, bool GRAD_INPUT>
+int chunked_k(const void* src_, const void* kern_, void* dst_, PacS2Args a, hipStream_t st) {
+    const T* src = static_cast<const T*>(src_);
     const T* kern = static_cast<const T*>(kern_);
-    T* out = static_cast<T*>(out_);
+    T* dst = static_cast<T*>(dst_);
     constexpr int CB = K == 3 ? 2 : 1;
-    const int gx = ceil_div(a.Ho * a.WQ, 256);
-    a.cchunk = chunk_for(a.C, (size_t)gx * a.B, CB, CSPN_S2_WANT);
-    const dim3 grid = chunked_grid(a, gx), block(256);
-    if (a.CK == 1) CSPN_PRE(st), pac_s2_fwd<T, K, true, CB><<<grid, block, 0, st>>>(in, kern, out, a);
-    else CSPN_PRE(st), pac_s2_fwd<T, K, false, CB><<<grid, block, 0, st>>>(in, kern, out, a);
-    HIP_OK(hipGetLastError());
-    return 1;
-}
-
-template <typename T, int K>
-int grad_input_k(const void* gout_, const void* kern_, void* gin_, PacS2Args a, hipStream_t st) {
-    const T* gout = static_cast<const T*>(gout_);
-    const T* kern = static_cast<const T*>(kern_);
-    T* gin = static_cast<T*>(gin_);
-    constexpr int CB = K == 3 ? 2 : 1;
-    const int gx = ceil_div(a.Ho * a.WQ, 256);
-    a.cchunk = chunk_for(a.C, (size_t)gx * a.B, CB, CSPN_S2_WANT);
-    const dim3 grid = chunked_grid(a, gx), block(256);
-    if (a.CK == 1) CSPN_PRE(st), pac_s2_gi<T, K, true, CB><<<grid, block, 0, st>>>(gout, kern, gin, a);
-    else CSPN_PRE(st), pac_s2_gi<T, K, false, CB><<<grid, block, 0, st>>>(gout, kern, gin, a);
-    HIP_OK(hipGetLastError());
-    return 1;
+    const dim3 grid = chunked_grid(a, CB);
+    return with_bools([&](auto shared) {
+        if constexpr (GRAD_INPUT) return launch(pac_s2_gi<T, K, shared.value, CB>, grid, dim3(256), 0, st, src, kern, dst, a);
+        else return launch(pac_s2_fwd<T, K, shared.value, CB>, grid, dim3(256), 0, st, src, kern, dst, a);
+    }, a.CK == 1);
 }
 
 template <typename T, int K>
@@ -500,20 +477,24 @@ int grad_kernel_k(const void* gout_, const void* in_, void* gk_, PacS2Args a, hi
     const T* gout = static_cast<const T*>(gout_);
     const T* in = static_cast<const T*>(in_);
     T* gk = static_cast<T*>(gk_);
-    if (a.CK == 1) {
-        constexpr int NW = K == 3 ? 4 : 2, CB = K == 3 ? 2 : 1;
-        const dim3 grid(ceil_div(a.Ho * a.WQ, 64), 1, a.B), block(64 * NW);
-        if (a.C == 1) CSPN_PRE(st), pac_s2_gk_shared<T, K, 1, 1><<<grid, dim3(64), 0, st>>>(gout, in, gk, a);
-        else CSPN_PRE(st), pac_s2_gk_shared<T, K, NW, CB><<<grid, block, 0, st>>>(gout, in, gk, a);
-    } else {
-        constexpr int CB = K == 3 ? 2 : 1;
-        const int gx = ceil_div(a.Ho * a.WQ, 256);
-        a.cchunk = chunk_for(a.C, (size_t)gx * a.B, CB, CSPN_S2_WANT);
-        const dim3 grid = chunked_grid(a, gx), block(256);
-        CSPN_PRE(st), pac_s2_gk_perch<T, K, CB><<<grid, block, 0, st>>>(gout, in, gk, a);
+    constexpr int NW = K == 3 ? 4 : 2, CB = K == 3 ? 2 : 1;
+    if (a.CK != 1) {
+        const dim3 grid = chunked_grid(a, CB);           // sets a.cchunk, a.nchunk, a.gx: before `a` is passed on
+        return launch(pac_s2_gk_perch<T, K, CB>, grid, dim3(256), 0, st, gout, in, gk, a);
     }
-    HIP_OK(hipGetLastError());
-    return 1;
+    const dim3 grid(ceil_div(a.Ho * a.WQ, 64), 1, a.B);
+    if (a.C == 1) return launch(pac_s2_gk_shared<T, K, 1, 1>, grid, dim3(64), 0, st, gout, in, gk, a);
+    return launch(pac_s2_gk_shared<T, K, NW, CB>, grid, dim3(64 * NW), 0, st, gout, in, gk, a);
+}
+
+// f(type tag, K): the storage type and the window size as compile-time values
+template <typename T> struct type_tag { using type = T; };
+template <typename F>
+int with_dtype_k(int dtype, int K, F&& f) {
+    using K3 = std::integral_constant<int, 3>;
+    using K5 = std::integral_constant<int, 5>;
+    if (dtype == CSPN_F16) return K == 3 ? f(type_tag<__half>{}, K3{}) : f(type_tag<__half>{}, K5{});
+    return K == 3 ? f(type_tag<float>{}, K3{}) : f(type_tag<float>{}, K5{});
 }
 
 }  // namespace
@@ -526,21 +507,19 @@ bool pac_s2_geometry(int kh, int kw, int sh, int sw, int ph, int pw, int dh, int
 }
 
 int pac_s2_forward(const void* in, const void* kern, void* out, int dtype, int K, const PacS2Args& a, void* stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == CSPN_F16) return K == 3 ? forward_k<__half, 3>(in, kern, out, a, st) : forward_k<__half, 5>(in, kern, out, a, st);
-    return K == 3 ? forward_k<float, 3>(in, kern, out, a, st) : forward_k<float, 5>(in, kern, out, a, st);
+    return with_dtype_k(dtype, K, [&](auto t, auto k) {
+        return chunked_k<typename decltype(t)::type, k.value, false>(in, kern, out, a, static_cast<hipStream_t>(stream));
+    });
 }
 int pac_s2_grad_input(const void* gout, const void* kern, void* gin, int dtype, int K, const PacS2Args& a, void* stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == CSPN_F16)
-        return K == 3 ? grad_input_k<__half, 3>(gout, kern, gin, a, st) : grad_input_k<__half, 5>(gout, kern, gin, a, st);
-    return K == 3 ? grad_input_k<float, 3>(gout, kern, gin, a, st) : grad_input_k<float, 5>(gout, kern, gin, a, st);
+    return with_dtype_k(dtype, K, [&](auto t, auto k) {
+        return chunked_k<typename decltype(t)::type, k.value, true>(gout, kern, gin, a, static_cast<hipStream_t>(stream));
+    });
 }
 int pac_s2_grad_kernel(const void* gout, const void* in, void* gk, int dtype, int K, const PacS2Args& a, void* stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == CSPN_F16)
-        return K == 3 ? grad_kernel_k<__half, 3>(gout, in, gk, a, st) : grad_kernel_k<__half, 5>(gout, in, gk, a, st);
-    return K == 3 ? grad_kernel_k<float, 3>(gout, in, gk, a, st) : grad_kernel_k<float, 5>(gout, in, gk, a, st);
+    return with_dtype_k(dtype, K, [&](auto t, auto k) {
+        return grad_kernel_k<typename decltype(t)::type, k.value>(gout, in, gk, a, static_cast<hipStream_t>(stream));
+    });
 }
 
 }  // namespace cspn_detail

@@ -490,3 +490,65 @@ def test_fp16_eight_pixel_kernel_several_channels_per_workgroup(K):
         b, c, y, xx = (int(rng.integers(0, n)) for n in (B, C, Ho, Wo))
         want = float((xp[b, c, y:y + K, xx:xx + K] * kern[b, c, :, :, y, xx].double()).sum())
         assert abs(float(outs[0][b, c, y, xx]) - want) <= 2e-3 * max(1.0, abs(want)), (b, c, y, xx)
+
+
+# One case per kernel instantiation that a sweep over dtype x kernel sharing x window x alignment x channels x frame size
+# launches and no test above does (found by comparing kernel traces of that sweep and of this file).  Shapes are the smallest
+# that select the instantiation: a few 64 x 16 tiles, and only as many channels and images as the selection rule needs.
+#   dtype, B, C, CK, H, W, k, s, p, d
+INSTANTIATION_CASES = [
+    # square windows, shared kernel, several channels per workgroup (288 workgroups before the split): the hoisted four-channel
+    # forward / transposed kernels, the eight-pixel fp16 forward with hoisted taps, the whole-window dL/dkernel
+    ("f32", 32, 12, 1, 33, 136, 3, 1, 1, 1), ("f32", 32, 12, 1, 33, 136, 5, 1, 2, 1),
+    ("f16", 32, 12, 1, 33, 136, 3, 1, 1, 1), ("f16", 32, 12, 1, 33, 136, 5, 1, 2, 1),
+    # ... fp16 at a width that is no multiple of 8: the quad kernel instead of the eight-pixel one
+    ("f16", 32, 12, 1, 33, 132, 3, 1, 1, 1), ("f16", 32, 12, 1, 33, 132, 5, 1, 2, 1),
+    # a single channel on >= 256 tiles: the one-channel whole-window dL/dkernel (fp16: not the eight-pixel outer product)
+    ("f32", 32, 1, 1, 33, 136, 3, 1, 1, 1), ("f32", 32, 1, 1, 33, 136, 5, 1, 2, 1),
+    ("f16", 32, 1, 1, 33, 132, 3, 1, 1, 1), ("f16", 32, 1, 1, 33, 132, 5, 1, 2, 1),
+    # per-channel kernel, two channels per workgroup (4 ragged tiles x 32 images, 40 channels in 32 chunks)
+    ("f32", 32, 40, 40, 17, 65, 3, 1, 1, 1), ("f16", 32, 40, 40, 17, 65, 3, 1, 1, 1),
+    # per-channel kernel, one channel per workgroup, fp16 quad kernels
+    ("f16", 2, 3, 3, 33, 132, 3, 1, 1, 1), ("f16", 2, 3, 3, 33, 132, 5, 1, 2, 1),
+    # 7 x 7: the tap-row dL/dkernel (few tiles), per-channel fp32 and shared fp16
+    ("f32", 2, 3, 3, 33, 136, 7, 1, 3, 1),
+    # shared 7 x 7, eight-channel batches, one LDS buffer (a chunk is one batch) — forward and transposed
+    ("f16", 2, 8, 1, 33, 136, 7, 1, 3, 1),
+    # ... on >= 256 tiles: the whole-window dL/dkernel
+    ("f16", 32, 8, 1, 33, 136, 7, 1, 3, 1),
+    # ... two LDS buffers (cchunk > 8: 128 workgroups before the split, 72 channels in 8 chunks of 9 -> 16)
+    ("f16", 8, 72, 1, 64, 256, 7, 1, 3, 1),
+    ("f32", 8, 72, 1, 64, 256, 7, 1, 3, 1),
+    # any-geometry kernels (dilated window), fp16, per-channel kernel
+    ("f16", 2, 3, 3, 33, 136, 3, 1, 2, 2),
+    # stride-2 register kernels: fp16 per-channel 3 x 3; one-channel and shared dL/dkernel
+    ("f16", 2, 3, 3, 34, 136, 3, 2, 1, 1), ("f16", 2, 1, 1, 34, 136, 3, 2, 1, 1), ("f16", 2, 3, 1, 34, 136, 5, 2, 2, 1),
+    ("f32", 2, 1, 1, 34, 136, 5, 2, 2, 1),
+]
+
+
+@pytest.mark.parametrize("dt,B,C,CK,H,W,k,s,p,d", INSTANTIATION_CASES)
+def test_tiled_equals_generic_per_instantiation(dt, B, C, CK, H, W, k, s, p, d):
+    """The same call with cspn_pac_force_generic off and on.  fp32: random normal inputs, TOL.  fp16: inputs on a grid
+    (integers in [-2, 2], taps in {-0.5, 0, 0.5}) on which every product and every sum of <= 49 taps or <= 72 channels is
+    exact in fp32 and in fp16 (|sum| <= 288 in steps of 0.5), so the order of accumulation, which differs between the
+    kernels, cannot move a half: what differs then is an index or a launch parameter."""
+    rng = np.random.default_rng(4100 + B + C + H + W)
+    kk, ss, pp, dd = (v if isinstance(v, tuple) else (v, v) for v in (k, s, p, d))
+    Ho, Wo = porc.out_size((H, W), kk, ss, pp, dd)
+    if dt == "f16":
+        x = rng.integers(-2, 3, (B, C, H, W)).astype(np.float32)
+        kern = rng.integers(-1, 2, (B, CK, kk[0], kk[1], Ho, Wo)).astype(np.float32) * 0.5
+        cot = rng.integers(-2, 3, (B, C, Ho, Wo)).astype(np.float32)
+    else:
+        x = rng.standard_normal((B, C, H, W)).astype(np.float32)
+        kern = (rng.standard_normal((B, CK, kk[0], kk[1], Ho, Wo)) * 0.3).astype(np.float32)
+        cot = rng.standard_normal((B, C, Ho, Wo)).astype(np.float32)
+    tdt = torch.float16 if dt == "f16" else torch.float32
+    with force_generic(0):
+        got = run_all(x, kern, cot, kk, ss, pp, dd, tdt)
+    with force_generic(1):
+        ref = run_all(x, kern, cot, kk, ss, pp, dd, tdt)
+    errs = [nmax(g_, r_) for g_, r_ in zip(got, ref)]
+    print("tiled vs generic (out, grad_input, grad_kernel):", errs)
+    assert max(errs) <= TOL, (errs, dt, B, C, CK, H, W, k, s, p, d)

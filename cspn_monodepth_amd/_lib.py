@@ -15,18 +15,23 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 SO_PATH = os.environ.get("CSPN_HIP_LIB") or os.path.join(_PKG, "libcspn_hip.so")   # env override: A/B builds
 CSRC = os.path.join(_PKG, "csrc")
-SOURCES = ("cspn_propagate.hip", "cspn_resident.hip", "cspnk_resident.hip", "cspnk_d2.hip", "cspn_prepare.hip", "cspn_backward.hip", "cspn_metrics.hip", "cspn_metrics_frame.hip", "cspn_debug.hip", "cspn_repair.hip", "pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_criterion.hip", "cspn_max8.hip")   # one TU each
+SOURCES = ("cspn_propagate.hip", "cspn_resident.hip", "cspnk_resident.hip", "cspnk_d2.hip", "cspn_prepare.hip", "cspn_backward.hip", "cspn_metrics.hip", "cspn_metrics_frame.hip", "cspn_debug.hip", "cspn_repair.hip", "pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_criterion.hip", "cspn_max8.hip", "cspn_abn.hip")   # one TU each
 HEADERS = (os.path.join(CSRC, "cspn_common.hpp"), os.path.join(CSRC, "cspnk_helpers.hpp"), os.path.join(_ROOT, "include", "cspn_hip.h"))
 INCLUDE = os.path.join(_ROOT, "include")
-# include/cspn_criterion.h, include/cspn_max8.h, csrc/pac_launch.hpp: part of the build's staleness hash, NOT of code_digest() — no benchmarked
+# include/cspn_criterion.h, include/cspn_max8.h, include/cspn_abn.h, csrc/pac_launch.hpp: part of the build's staleness hash, NOT of code_digest() — no benchmarked
 # kernel sees it, and a digest that moved would mark the HBM traffic recorded under profiles/ as stale (bench.py `traffic_stale`)
-BUILD_HEADERS = HEADERS + (os.path.join(INCLUDE, "cspn_criterion.h"), os.path.join(INCLUDE, "cspn_max8.h"), os.path.join(CSRC, "pac_launch.hpp"))
+BUILD_HEADERS = HEADERS + (os.path.join(INCLUDE, "cspn_criterion.h"), os.path.join(INCLUDE, "cspn_max8.h"), os.path.join(INCLUDE, "cspn_abn.h"),
+                           os.path.join(CSRC, "pac_launch.hpp"))
 
 CSPN_F32, CSPN_F16 = 0, 1
 ABI_VERSION = 10         # CSPN_ABI_VERSION of include/cspn_hip.h this host code was written against
 CRITERION_ABI_VERSION = 1   # CSPN_CRITERION_ABI_VERSION of include/cspn_criterion.h
 MAX8_ABI_VERSION = 1        # CSPN_MAX8_ABI_VERSION of include/cspn_max8.h
 MAX8_MAX_STEPS_PER_LAUNCH = 16
+ABN_ABI_VERSION = 1         # CSPN_ABN_ABI_VERSION of include/cspn_abn.h
+ABN_ACT_LEAKY_RELU, ABN_ACT_ELU, ABN_ACT_NONE = 0, 1, 2
+ABN_SMALL, ABN_SPLIT = 0, 1                                 # cspn_abn_plan_t.regime
+ABN_FULL, ABN_STATS_ONLY, ABN_APPLY_ONLY = 0, 1, 2          # the `phase` of a training-mode cspn_abn_forward
 LOSS_L1, LOSS_L2, LOSS_L1_LOG = 0, 1, 2
 BLEND_NONE, BLEND_SPARSE, BLEND_PREMASK = 0, 1, 2
 
@@ -44,6 +49,9 @@ EXPORTS = (
 CRITERION_EXPORTS = ("cspn_criterion_abi_version", "cspn_criterion_workspace_bytes", "cspn_criterion_forward", "cspn_criterion_backward")
 # every symbol include/cspn_max8.h declares
 MAX8_EXPORTS = ("cspn_max8_abi_version", "cspn_max8_workspace_bytes", "cspn_max8_forward", "cspn_max8_backward")
+# every symbol include/cspn_abn.h declares
+ABN_EXPORTS = ("cspn_abn_abi_version", "cspn_abn_plan", "cspn_abn_workspace_bytes", "cspn_abn_forward", "cspn_abn_backward_reduce",
+               "cspn_abn_backward")
 
 
 class cspn_plan(ctypes.Structure):
@@ -65,7 +73,13 @@ class cspn_conv_geometry(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("kh", "kw", "sh", "sw", "ph", "pw", "dh", "dw", "oph", "opw", "transposed")]
 
 
-BENCH_UNRELATED = ("pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_metrics_frame.hip", "cspn_criterion.hip", "cspn_max8.hip")       # kernels no bench.py workload launches
+class cspn_abn_plan(ctypes.Structure):           # cspn_abn_plan_t (include/cspn_abn.h)
+    _fields_ = [(n, ctypes.c_int) for n in ("regime", "channels_per_workgroup", "workgroups_per_channel", "threads")] + \
+               [("elements_per_workgroup", ctypes.c_size_t), ("small_limit", ctypes.c_size_t)]
+
+
+BENCH_UNRELATED = ("pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_metrics_frame.hip", "cspn_criterion.hip", "cspn_max8.hip",
+                   "cspn_abn.hip")       # kernels no bench.py workload launches
 
 
 def _source_digest(flags, code_only=False):
@@ -217,6 +231,18 @@ def _declare(lib):
     lib.cspn_max8_forward.restype = ci
     lib.cspn_max8_backward.argtypes = [vp, cl, cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.cspn_max8_backward.restype = ci
+    cf = ctypes.c_float
+    lib.cspn_abn_abi_version.restype = ci
+    lib.cspn_abn_plan.argtypes = [ci, ci, ci, ctypes.POINTER(cspn_abn_plan)]
+    lib.cspn_abn_plan.restype = ci
+    lib.cspn_abn_workspace_bytes.argtypes = [ci, ci, ci]
+    lib.cspn_abn_workspace_bytes.restype = cs
+    lib.cspn_abn_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, ci, cf, vp, vp]
+    lib.cspn_abn_forward.restype = ci
+    lib.cspn_abn_backward_reduce.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, ci, cf, vp, vp]
+    lib.cspn_abn_backward_reduce.restype = ci
+    lib.cspn_abn_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, cf, vp, vp]
+    lib.cspn_abn_backward.restype = ci
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("cspn_last_error", "cspn_propagate_workspace_bytes", "cspn3_resident_workspace_bytes",
@@ -242,6 +268,8 @@ def lib():
                     raise RuntimeError("cspn_monodepth_amd: criterion ABI version mismatch")
                 if _lib.cspn_max8_abi_version() != MAX8_ABI_VERSION:
                     raise RuntimeError("cspn_monodepth_amd: max8 ABI version mismatch")
+                if _lib.cspn_abn_abi_version() != ABN_ABI_VERSION:
+                    raise RuntimeError("cspn_monodepth_amd: abn ABI version mismatch")
                 poison = os.environ.get("CSPN_DEBUG_LDS_POISON", "")      # debugging aid (include/cspn_hip.h): "nan" or a hex word
                 if poison and poison != "0":
                     _lib.cspn_debug_set_lds_poison(1, 0x7fc00000 if poison in ("1", "nan") else int(poison, 16), None)

@@ -11,7 +11,8 @@ DistributedDataParallel over RCCL when launched with torchrun:
 encoder, guided up-projection decoder on the HIP un-pooling kernel, both heads — 218 M parameters in use); the default
 `--model tiny` is a five-conv network with the same tensor contract at the CSPN boundary (guidance [B,12,H,W], coarse
 [B,1,H,W], sparse = input[:,3:4]) for quick smoke runs.  `bench.py --workload train` is the measured version of the
-resnet50 step.  Synthetic data (no dataset on the box).
+resnet50 step.  Synthetic data (no dataset on the box).  The normalisation layers are nn.SyncBatchNorm here;
+`cspn_monodepth_amd.network.convert_batchnorm(model, sync=True)` instead gives the reference's own In-Place ABN layers.
 """
 import argparse
 import os

@@ -7,12 +7,17 @@ host synchronisation per batch and one `average()` at the end.
     python examples/eval_loop.py --batch 24 --frames 96                  # batched, sync-free
     python examples/eval_loop.py --batch 24 --frames 96 --graph          # one captured replay per batch, the meter inside it
     python examples/eval_loop.py --frames 96 --compare-host-meter        # the old way: batch 1, metric_sums + a .cpu() per frame
+    python examples/eval_loop.py --batch 24 --frames 96 --graph --sparsifier device   # the reference's sampler inside the replay
 
 Synthetic data (device RNG, one seed per frame, so a frame does not depend on the batch it is generated in; SURVEY.md §8d
 value distributions): `prior` = a dense depth U(0.5, 10); input = RGB U(0, 1) + sparse samples of `prior` (500 per frame);
 target = prior + N(0, sigma_i^2), sigma_i between 0.05 and 0.4 from frame to frame, clamped to >= 0.1, 3 % of its pixels invalid
 (0).  The network is UNTRAINED and emits ~0, so the scored prediction is `prior + model(x)[0]` clamped to >= 0.1: predictions
-stay in the NYU depth range and every metric term is finite.  The numbers say nothing about depth estimation — they exercise
+stay in the NYU depth range and every metric term is finite.  --sparsifier stock (the default) keeps a pixel of `prior` with
+probability 500 / (H W) with stock ops while the frames are made; --sparsifier device draws the sample inside the step (and inside
+the captured replay) with the reference's own rule — dataloaders.nyu_dataloader.dense_to_sparse.UniformSampling(500): probability
+500 / n_keep, n_keep counted per frame — and assembles the 4-channel input in the same launch (create_rgbd); a frame's sample
+depends on (--seed, frame index) only, not on the batch size.  The numbers say nothing about depth estimation — they exercise
 the protocol, and tests/test_eval_protocol.py checks them against a per-frame fp64 evaluation of the dumped tensors.
 
 Prints one JSON line: the ten averages, `count` (frames) and `seconds_per_frame` (whole loop, model included, wall clock
@@ -29,23 +34,26 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cspn_monodepth_amd import evaluation as ev                           # noqa: E402
+from cspn_monodepth_amd.dataloaders.nyu_dataloader.dense_to_sparse import UniformSampling, create_rgbd      # noqa: E402
 from cspn_monodepth_amd.graphs import GraphedForward                      # noqa: E402
 from cspn_monodepth_amd.network import unet_ours                          # noqa: E402
 
 
-def make_frames(n, H, W, seed, dev):
-    """-> x [n,4,H,W], prior [n,1,H,W], target [n,1,H,W] on the device."""
+def make_frames(n, H, W, seed, dev, sparsifier="stock"):
+    """-> x [n,4,H,W], prior [n,1,H,W], target [n,1,H,W] on the device; sparsifier "device": x is the RGB planes alone [n,3,H,W],
+    and the step samples `prior` itself."""
     gen = torch.Generator(device=dev)
     xs, priors, targets = [], [], []
     for i in range(n):
         gen.manual_seed(seed * 1000003 + i)
         rnd = lambda *s: torch.rand(*s, generator=gen, device=dev)        # noqa: E731
         prior = rnd(1, H, W) * 9.5 + 0.5
-        sparse = prior * (rnd(1, H, W) < 500.0 / (H * W))
+        if sparsifier == "stock":
+            sparse = prior * (rnd(1, H, W) < 500.0 / (H * W))
         sigma = 0.05 + 0.35 * ((i * 7) % 16) / 15.0
         target = (prior + sigma * torch.randn(1, H, W, generator=gen, device=dev)).clamp_(min=0.1)
         target = target * (rnd(1, H, W) >= 0.03)
-        xs.append(torch.cat([rnd(3, H, W), sparse], 0))
+        xs.append(torch.cat([rnd(3, H, W), sparse], 0) if sparsifier == "stock" else rnd(3, H, W))
         priors.append(prior)
         targets.append(target)
     return torch.stack(xs), torch.stack(priors), torch.stack(targets)
@@ -63,42 +71,50 @@ def main():
     ap.add_argument("--graph", action="store_true", help="capture forward + meter update once per batch shape and replay it")
     ap.add_argument("--compare-host-meter", action="store_true",
                     help="batch 1 with metric_sums + BatchAverageMeter (a host synchronisation per frame) instead of the device meter")
+    ap.add_argument("--sparsifier", choices=("stock", "device"), default="stock",
+                    help="stock: sparse samples made with the frames by stock ops, probability 500 / (H W); device: the reference's "
+                         "UniformSampling(500) + create_rgbd on the device inside every step (include/cspn_sparsify.h)")
     a = ap.parse_args()
     if a.compare_host_meter:
         a.batch, a.graph = 1, False
     dev = torch.device("cuda", 0)
     torch.manual_seed(a.seed)
     net = getattr(unet_ours, a.model)(decoder_sizes=unet_ours.decoder_sizes_for(a.height, a.width)).to(dev).eval()
-    x, prior, target = make_frames(a.frames, a.height, a.width, a.seed, dev)
+    x, prior, target = make_frames(a.frames, a.height, a.width, a.seed, dev, a.sparsifier)
+    uar = UniformSampling(500)
+    # --sparsifier device: one more input per batch, the frame indices (the Philox frame ids), copied into the replay like the rest
+    ids = (torch.arange(a.frames, dtype=torch.int64, device=dev),) if a.sparsifier == "device" else ()
     meter = ev.FrameAverageMeter(dev)
     host_meter = ev.BatchAverageMeter()
 
     def predict(xb, pb):
         return (pb + net(xb)[0]).clamp_(min=0.1)                           # the plain forward: device-guarded, safe to score unsynchronised
 
-    def step(xb, pb, tb):
+    def step(xb, pb, tb, *ib):
+        if ib:
+            xb = create_rgbd(uar, xb, pb, frame_ids=ib[0], seed=a.seed)[0]
         pred = predict(xb, pb)
         meter.update(pred, tb)
         return pred
 
     nb = min(a.batch, a.frames)
     with torch.no_grad():
-        step(x[:nb], prior[:nb], target[:nb])                              # warm-up: kernel selection of the convolutions, meter buffers
-        graphed = GraphedForward(step, x[:nb], prior[:nb], target[:nb]) if a.graph else None
+        step(x[:nb], prior[:nb], target[:nb], *(i[:nb] for i in ids))      # warm-up: kernel selection of the convolutions, meter buffers
+        graphed = GraphedForward(step, x[:nb], prior[:nb], target[:nb], *(i[:nb] for i in ids)) if a.graph else None
         meter.reset()
         preds = []
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         for lo in range(0, a.frames, a.batch):
             hi = min(lo + a.batch, a.frames)
-            xb, pb, tb = x[lo:hi], prior[lo:hi], target[lo:hi]
+            xb, pb, tb, ib = x[lo:hi], prior[lo:hi], target[lo:hi], tuple(i[lo:hi] for i in ids)
             if a.compare_host_meter:
-                pred = predict(xb, pb)
+                pred = predict(create_rgbd(uar, xb, pb, frame_ids=ib[0], seed=a.seed)[0] if ib else xb, pb)
                 host_meter.update(ev.metric_sums(pred, tb), n=1)
             elif graphed is not None and hi - lo == nb:
-                pred = graphed(xb, pb, tb)
+                pred = graphed(xb, pb, tb, *ib)
             else:                                                          # eager (and the ragged last batch of a --graph run)
-                pred = step(xb, pb, tb)
+                pred = step(xb, pb, tb, *ib)
             if a.dump:
                 preds.append(pred.clone())
         torch.cuda.synchronize(dev)
@@ -108,6 +124,8 @@ def main():
         os.makedirs(a.dump, exist_ok=True)
         np.save(os.path.join(a.dump, "pred.npy"), torch.cat(preds)[:, 0].cpu().numpy())
         np.save(os.path.join(a.dump, "target.npy"), target[:, 0].cpu().numpy())
+    if a.sparsifier == "device":
+        res.update(sparsifier="device")
     res.update(model=a.model, batch=a.batch, graph=bool(a.graph), meter="host" if a.compare_host_meter else "device",
                count=int(res["count"]), seconds_per_frame=dt / a.frames)
     print(json.dumps(res))

@@ -1,0 +1,594 @@
+"""The sparse-depth sampler and the RGB-D assembly (cspn_monodepth_amd/dataloaders/nyu_dataloader/dense_to_sparse.py,
+include/cspn_sparsify.h) against golden G21: the reference's UniformSampling.dense_to_sparse and create_sparse_depth / create_rgbd per
+frame on the CPU (tests/golden/make_golden_g21.py), which equal the numpy restatement of tests/sparsify_cases.py bit for bit.
+
+An output is a copy of an input or a zero, so EVERY comparison here is bit equality: no tolerance appears anywhere.
+
+  * CPU: the fixtures against the restatement, the header / library / loader contract, the host-side argument checks of the C ABI and
+    of the module, SimulatedStereo, the numpy Philox against published known answers, the seed of the statistical test;
+  * GPU: every G21 case through the C ABI and through the module with fp64 u, with fp32 u where the stored u fits, and with every
+    plane one element off 16-byte alignment (guard elements either side); generated mode against the numpy Philox; what a frame id
+    promises; the sample count at 228 x 304; a captured loop; the sparse view in front of CSPN_new.AffinityPropagate.
+
+Sizes not covered here: H * W at and past 2^31 (pixel indices in the kernels are size_t, the Philox counter takes the low 32 bits,
+and the entry point refuses H * W >= 2^32); one such fp32 frame with its fp64 uniforms is 26 GB."""
+import ctypes
+import functools
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import cspn_monodepth_amd as pkg
+import sparsify_cases as sc
+from conftest import ROOT, golden_names, lds_poison, load_golden
+from cspn_monodepth_amd import _lib
+from cspn_monodepth_amd.dataloaders.nyu_dataloader import dense_to_sparse as d2s
+
+DEV = "cuda:0"
+NAMES = ["g21_sparsify_" + n for n in sc.CASES]
+FULL_HW = (228, 304)
+FULL_SEED = 2024            # test_seed_of_the_count_test_keeps_the_restatement_inside: chosen on the CPU, from the restatement alone
+
+
+@functools.lru_cache(maxsize=None)
+def golden(name):
+    return load_golden(name)                 # shared among the tests: nobody writes into it
+
+
+def sparsifier_of(z):
+    return d2s.UniformSampling(int(z["num_samples"]), float(z["max_depth"]))
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def host(t):
+    return t.detach().cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------ CPU
+def test_fixture_set_is_complete():
+    assert golden_names("g21_sparsify_") == sorted(NAMES)
+    assert os.path.exists(os.path.join(ROOT, "tests", "golden", "golden_g21_manifest.json"))
+    for name in NAMES:
+        assert os.path.getsize(os.path.join(ROOT, "tests", "golden", name + ".npz")) <= sc.MAX_FILE_BYTES
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_restatement_equals_the_reference_bit_for_bit(name):
+    z, case = golden(name), sc.CASES[name[len("g21_sparsify_"):]]
+    assert z["depth"].dtype == np.float32 and z["u"].dtype == np.float64 and z["mask"].dtype == bool and z["sparse"].dtype == np.float32
+    assert tuple(z["depth"].shape) == (case["shape"][0], 1) + tuple(case["shape"][1:])
+    assert sc.same_bits(z["depth"], sc.make_depth(case))                       # the stored seed gives the stored inputs
+    mask, sparse = sc.restate(z["depth"], z["u"], int(z["num_samples"]), float(z["max_depth"]))
+    assert np.array_equal(mask, z["mask"]) and sc.same_bits(sparse, z["sparse"])
+    assert sc.fp32_exact(z["u"]) == (case["u"] == "f32")
+    if case["rgb"]:
+        assert sc.same_bits(z["rgb"], sc.make_rgb(case))
+        assert z["rgbd"].dtype == np.float32 and sc.same_bits(z["rgbd"], sc.restate_rgbd(z["rgb"], sparse))
+        assert z["rgb"].dtype == (np.uint8 if case["rgb"] == "u8" else np.float32)
+    else:
+        assert "rgbd" not in z
+
+
+def test_fixtures_hold_what_they_are_there_for():
+    z = golden("g21_sparsify_boundary_quarter")
+    assert z["mask"].reshape(-1).tolist() == [False, True, False, True, False, False]          # u == prob is not sampled
+    assert (z["u"] == 0.25).sum() == 2 and (z["u"] == np.nextafter(0.25, 0.0)).sum() == 2
+    z = golden("g21_sparsify_empty_middle_3x5x7")
+    assert [int(z["mask"][b].sum()) > 0 for b in range(3)] == [True, False, True] and not (z["depth"][1] > 0).any()
+    z = golden("g21_sparsify_max_depth_2x6x9")
+    md = np.float32(float(z["max_depth"]))
+    assert float(md) > float(z["max_depth"]) and (z["depth"].reshape(2, -1)[:, 1] == md).all()     # kept by fp32, cut by an fp64 comparison
+    keep, _ = sc.restate(z["depth"], np.zeros_like(z["u"]), 10 ** 9, float(z["max_depth"]))
+    assert keep.reshape(2, -1)[:, 1].all() and not keep.reshape(2, -1)[:, 4].any() and ((z["depth"] > 0) & ~keep).sum() > 2
+    z = golden("g21_sparsify_hostile_2x5x7")
+    assert np.isnan(z["depth"]).any() and np.isinf(z["depth"]).any() and (np.signbit(z["depth"]) & (z["depth"] == 0)).any()
+    assert not np.isnan(z["sparse"]).any() and not np.signbit(z["sparse"]).any()
+    z = golden("g21_sparsify_frame_57x76")
+    assert np.unique(z["rgb"]).size == 256 and int(z["num_samples"]) == 500
+    for name, n in sc.SPANS_SLICES.items():
+        hw = int(np.prod(sc.CASES[name]["shape"][1:]))
+        assert sc.slices(hw) == n == _lib.lib().cspn_sparsify_slices(hw) and n > 1
+    z = golden("g21_sparsify_all_sampled_2x4x6")
+    assert np.array_equal(z["mask"], z["depth"] > 0)
+    assert not golden("g21_sparsify_none_sampled_2x4x6")["mask"].any()
+
+
+def test_header_declares_four_symbols_and_the_library_exports_them():
+    src = open(os.path.join(ROOT, "include", "cspn_sparsify.h")).read()
+    assert re.search(r"^#define CSPN_SPARSIFY_ABI_VERSION 1$", src, flags=re.M)
+    assert re.search(r"CSPN_UNIFORM_PHILOX = 0, CSPN_UNIFORM_F32 = 1, CSPN_UNIFORM_F64 = 2", src)
+    assert re.search(r"CSPN_RGB_NONE = 0, CSPN_RGB_F32 = 1, CSPN_RGB_U8 = 2", src)
+    assert re.search(r"CSPN_SPARSIFY_UAR = 0, CSPN_SPARSIFY_DENSE = 1", src)
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    declared = sorted(set(re.findall(r"\b(cspn\w*)\s*\(", src)))
+    assert declared == sorted(_lib.SPARSIFY_EXPORTS) == sorted(
+        ["cspn_sparsify_abi_version", "cspn_sparsify_slices", "cspn_sparsify_workspace_bytes", "cspn_sparsify"])
+    lib = ctypes.CDLL(_lib.build())
+    for name in declared:
+        assert hasattr(lib, name), name
+    L = _lib.lib()
+    assert L.cspn_sparsify_abi_version() == _lib.SPARSIFY_ABI_VERSION == 1
+    assert L.cspn_abi_version() == _lib.ABI_VERSION == 10                   # the main ABI did not move
+    assert not set(_lib.SPARSIFY_EXPORTS) & (set(_lib.EXPORTS) | set(_lib.CRITERION_EXPORTS) | set(_lib.MAX8_EXPORTS) | set(_lib.ABN_EXPORTS))
+    assert (_lib.UNIFORM_PHILOX, _lib.UNIFORM_F32, _lib.UNIFORM_F64) == (0, 1, 2) and (_lib.RGB_NONE, _lib.RGB_F32, _lib.RGB_U8) == (0, 1, 2)
+    assert (_lib.SPARSIFY_UAR, _lib.SPARSIFY_DENSE) == (0, 1)
+    assert (_lib.SPARSIFY_SLICE_PIXELS, _lib.SPARSIFY_MAX_SLICES) == (sc.SLICE_PIXELS, sc.MAX_SLICES) == (1024, 64)
+    # nothing else of this translation unit leaves the library: every dynamic symbol that names the sampler is a declared one
+    import shutil
+    import subprocess
+    if shutil.which("nm"):
+        nm = subprocess.run(["nm", "-D", "--defined-only", _lib.SO_PATH], capture_output=True, text=True, check=True)
+        ours = sorted(ln.split()[-1] for ln in nm.stdout.splitlines() if "sparsify" in ln and " T " in ln)
+        assert ours == declared
+
+
+def test_sparsify_sources_stay_out_of_the_benchmark_digest():
+    assert "cspn_sparsify.hip" in _lib.SOURCES and "cspn_sparsify.hip" in _lib.BENCH_UNRELATED
+    hdr = os.path.join(ROOT, "include", "cspn_sparsify.h")
+    assert hdr in _lib.BUILD_HEADERS and hdr not in _lib.HEADERS
+    import hashlib
+    h = hashlib.sha256(b"")                                                 # code_digest() over its own file list, restated
+    for path in [os.path.join(_lib.CSRC, f) for f in _lib.SOURCES if f not in _lib.BENCH_UNRELATED] + list(_lib.HEADERS):
+        data = re.sub(rb"/\*.*?\*/", b"", open(path, "rb").read(), flags=re.S)
+        lines = (re.sub(rb"//.*$", b"", ln).strip() for ln in data.splitlines())
+        h.update(b"\n".join(re.sub(rb"\s+", b" ", ln) for ln in lines if ln))
+    assert _lib.code_digest() == h.hexdigest()
+
+
+def test_workspace_bytes_need_no_device_and_follow_the_slices():
+    L = _lib.lib()
+    assert L.cspn_sparsify_workspace_bytes(0, 100) == 0 and L.cspn_sparsify_workspace_bytes(3, 0) == 0
+    assert L.cspn_sparsify_workspace_bytes(-1, 100) == 0
+    assert L.cspn_sparsify_workspace_bytes(1, 1) == 4 and L.cspn_sparsify_workspace_bytes(3, 1024) == 12
+    assert L.cspn_sparsify_workspace_bytes(3, 1025) == 24
+    assert L.cspn_sparsify_workspace_bytes(24, 228 * 304) == 24 * 64 * 4 == L.cspn_sparsify_workspace_bytes(24, 1 << 31)
+    for hw in (1, 35, 1024, 1025, 1517, 4332, 65536, 65537, 69312, 1 << 31):
+        assert L.cspn_sparsify_slices(hw) == sc.slices(hw)
+
+
+def test_entry_point_rejects_bad_arguments_without_a_gpu():
+    """Validation happens on the host before any launch: 0 and a message in cspn_last_error()."""
+    L = _lib.lib()
+    err = lambda: L.cspn_last_error().decode()                                     # noqa: E731
+    p, odd, odd8 = ctypes.c_void_p(64), ctypes.c_void_p(66), ctypes.c_void_p(68)   # never dereferenced: validation fails first
+    F32, UAR, DENSE, inf = _lib.CSPN_F32, _lib.SPARSIFY_UAR, _lib.SPARSIFY_DENSE, float("inf")
+
+    def call(depth=p, dtype=F32, B=2, H=3, W=5, mode=UAR, ns=4, md=inf, u=p, uk=_lib.UNIFORM_F64, ids=None, seed=0, sparse=p, sbs=15, rgb=None,
+             rk=_lib.RGB_NONE, rout=None, rbs=60, rcs=15, mask=None, work=p):
+        return L.cspn_sparsify(depth, dtype, B, H, W, mode, ns, md, u, uk, ids, seed, sparse, sbs, rgb, rk, rout, rbs, rcs, mask, work, None)
+
+    assert call(depth=None) == 0 and "null depth" in err()
+    assert call(dtype=_lib.CSPN_F16) == 0 and "fp32 only" in err()
+    assert call(dtype=7) == 0 and "dtype" in err()
+    for bad in (dict(B=0), dict(B=65536), dict(H=0), dict(W=-1)):
+        assert call(**bad) == 0 and "bad size" in err()
+    assert call(H=1 << 16, W=1 << 16) == 0 and "2^32" in err()
+    assert call(mode=2) == 0 and "unknown mode" in err()
+    assert call(depth=odd) == 0 and "element size" in err()
+    assert call(uk=3) == 0 and "unknown uniform_kind" in err()
+    assert call(u=None) == 0 and "null uniform" in err()
+    assert call(u=odd8) == 0 and "element size" in err()                            # 68 is 4-byte aligned: not enough for fp64
+    assert call(u=odd, uk=_lib.UNIFORM_F32) == 0 and "element size" in err()
+    assert call(u=None, uk=_lib.UNIFORM_PHILOX) == 0 and "needs frame_ids" in err()
+    assert call(u=None, uk=_lib.UNIFORM_PHILOX, ids=odd8) == 0 and "8-byte aligned" in err()
+    assert call(work=None) == 0 and "null work" in err()
+    assert call(work=odd) == 0 and "4-byte aligned" in err()
+    assert call(sparse=None) == 0 and "sparse or a mask" in err()
+    assert call(sparse=odd) == 0 and "element size" in err()
+    assert call(sbs=14) == 0 and "sparse_batch_stride" in err()
+    assert call(sbs=-15) == 0 and "sparse_batch_stride" in err()
+    assert call(rk=3) == 0 and "unknown rgb_kind" in err()
+    assert call(rk=_lib.RGB_F32, rgb=None, rout=p) == 0 and "null rgb" in err()
+    assert call(rk=_lib.RGB_U8, rgb=p, rout=None) == 0 and "null rgb" in err()
+    assert call(rk=_lib.RGB_F32, rgb=odd, rout=p) == 0 and "element size" in err()
+    assert call(rk=_lib.RGB_U8, rgb=odd, rout=odd) == 0 and "element size" in err()
+    assert call(rk=_lib.RGB_F32, rgb=p, rout=p, rcs=14) == 0 and "rgb_out_channel_stride" in err()
+    assert call(rk=_lib.RGB_F32, rgb=p, rout=p, rbs=14) == 0 and "rgb_out_batch_stride" in err()
+    # the dense mode reads neither uniforms nor work, and still wants an output
+    assert call(mode=DENSE, u=None, work=None, sparse=None) == 0 and "sparse or a mask" in err()
+
+
+def test_module_checks_its_arguments_and_has_no_cpu_path():
+    us = d2s.UniformSampling(10)
+    depth, rgb = torch.rand(2, 1, 3, 5), torch.rand(2, 3, 3, 5)
+    with pytest.raises(RuntimeError, match="ROCm device"):
+        us.dense_to_sparse(rgb, depth)
+    with pytest.raises(RuntimeError, match="ROCm device"):
+        d2s.create_rgbd(us, rgb, depth)
+    with pytest.raises(RuntimeError, match="ROCm device"):
+        d2s.create_sparse_depth(us, None, depth, uniform=torch.rand(2, 1, 3, 5))
+    for bad in (depth.half(), depth.double(), depth.numpy(), (depth > 0)):
+        with pytest.raises(TypeError):
+            us.dense_to_sparse(None, bad)
+    for bad in (depth[0], depth[:, 0], torch.rand(2, 2, 3, 5), torch.rand(0, 1, 3, 5), torch.rand(2, 1, 0, 5)):
+        with pytest.raises(ValueError):
+            us.dense_to_sparse(None, bad)
+    with pytest.raises(TypeError, match="rgb"):
+        d2s.create_rgbd(us, rgb.half(), depth)
+    with pytest.raises(TypeError, match="needs rgb"):
+        d2s.create_rgbd(us, None, depth)
+    with pytest.raises(ValueError, match="rgb"):
+        d2s.create_rgbd(us, torch.rand(2, 3, 3, 6), depth)
+    with pytest.raises(ValueError, match="rgb"):
+        d2s.create_rgbd(us, torch.rand(2, 4, 3, 5), depth)
+    with pytest.raises(TypeError, match="uniform"):
+        us.dense_to_sparse(None, depth, uniform=torch.rand(2, 1, 3, 5).half())
+    with pytest.raises(ValueError, match="uniform"):
+        us.dense_to_sparse(None, depth, uniform=torch.rand(2, 3, 5))
+    with pytest.raises(TypeError, match="frame_ids"):
+        us.dense_to_sparse(None, depth, frame_ids=[0, 1])
+    with pytest.raises(TypeError, match="frame_ids"):
+        us.dense_to_sparse(None, depth, frame_ids=torch.arange(2, dtype=torch.int32))
+    with pytest.raises(ValueError, match="frame_ids"):
+        us.dense_to_sparse(None, depth, frame_ids=torch.arange(3))
+    with pytest.raises(TypeError, match="seed"):
+        us.dense_to_sparse(None, depth, seed=1.5)
+    for bad in (-1, 1 << 64):
+        with pytest.raises(ValueError, match="seed"):
+            us.dense_to_sparse(None, depth, seed=bad)
+    with pytest.raises(ValueError, match="num_samples"):
+        d2s.create_sparse_depth(d2s.UniformSampling(10.5), None, depth)
+    assert d2s.create_sparse_depth(None, rgb, depth) is depth                   # dataloader.py:86-87
+
+
+def test_names_reprs_and_the_sparsifier_that_is_not_built():
+    import inspect
+    us, st = d2s.UniformSampling(500), d2s.SimulatedStereo(500, 3.0)
+    assert us.name == "uar" and st.name == "sim_stereo" and d2s.UniformSampling.name == "uar"
+    assert repr(us) == "uar{ns=500,md=inf}" and repr(d2s.UniformSampling(20, 3.5)) == "uar{ns=20,md=3.500000}"
+    assert repr(st) == "sim_stereo{ns=500,md=3.000000,dil=3.1}"
+    assert us.max_depth is np.inf and isinstance(us, d2s.DenseToSparse) and isinstance(st, d2s.DenseToSparse)
+    assert list(inspect.signature(d2s.UniformSampling.__init__).parameters) == ["self", "num_samples", "max_depth"]
+    assert list(inspect.signature(d2s.SimulatedStereo.__init__).parameters) == ["self", "num_samples", "max_depth", "dilate_kernel", "dilate_iterations"]
+    assert list(inspect.signature(d2s.UniformSampling.dense_to_sparse).parameters) == ["self", "rgb", "depth", "uniform", "frame_ids", "seed"]
+    assert list(inspect.signature(d2s.create_rgbd).parameters) == ["sparsifier", "rgb", "depth", "uniform", "frame_ids", "seed"]
+    depth, rgb = torch.rand(1, 1, 3, 5), torch.rand(1, 3, 3, 5)
+    with pytest.raises(NotImplementedError, match="OpenCV"):
+        st.dense_to_sparse(rgb, depth)
+    with pytest.raises(NotImplementedError, match="OpenCV"):
+        d2s.create_rgbd(st, rgb, depth)
+    with pytest.raises(NotImplementedError, match="OpenCV"):
+        d2s.create_sparse_depth(st, rgb, depth)
+    assert pkg.dataloaders.nyu_dataloader.dense_to_sparse is d2s and pkg.dataloaders.nyu_dataloader.UniformSampling is d2s.UniformSampling
+
+
+def test_numpy_philox_reproduces_the_published_known_answers():
+    """The three philox4x32_10 lines of the known-answer file the Random123 library publishes (kat_vectors: counter, key -> output),
+    restated here: the file itself is not part of this repository.  Beyond them the numpy restatement is the anchor the device is
+    held to."""
+    kat = [((0, 0, 0, 0), (0, 0), (0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8)),
+           ((0xffffffff,) * 4, (0xffffffff,) * 2, (0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd)),
+           ((0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344), (0xa4093822, 0x299f31d0), (0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1))]
+    for ctr, key, want in kat:
+        assert tuple(int(v) for v in sc.philox4x32_10(*ctr, *key)) == want
+    # vectorised over counters = one call per counter
+    c0 = np.arange(5, dtype=np.uint64)
+    many = sc.philox4x32_10(c0, 0, 7, 1, 0x89abcdef, 0x01234567)
+    for i in range(5):
+        assert tuple(int(v[i]) for v in many) == tuple(int(v) for v in sc.philox4x32_10(i, 0, 7, 1, 0x89abcdef, 0x01234567))
+    u = sc.philox_uniform(1000, (1 << 32) + 7, 0x0123456789abcdef)
+    assert u.min() >= 0 and u.max() < 1 and sc.fp32_exact(u) and np.array_equal(u[:5], (many[0] >> np.uint64(8)) * 2.0 ** -24)
+
+
+def count_bounds():
+    """n = 69 312 valid pixels, each sampled with p = 500 / n: the count is Binomial(n, p), mean 500, sigma = sqrt(n p (1 - p))."""
+    n = FULL_HW[0] * FULL_HW[1]
+    p = 500.0 / n
+    sigma = math.sqrt(n * p * (1.0 - p))
+    assert n == 69312 and abs(sigma - 22.28) < 0.01
+    return 500.0 - 6.0 * sigma, 500.0 + 6.0 * sigma
+
+
+def test_seed_of_the_count_test_keeps_the_restatement_inside():
+    lo, hi = count_bounds()
+    for fid in (0, 1, 2):
+        c = int((sc.philox_uniform(FULL_HW[0] * FULL_HW[1], fid, FULL_SEED) < 500.0 / (FULL_HW[0] * FULL_HW[1])).sum())
+        print("frame %d: %d samples, bounds %.1f .. %.1f" % (fid, c, lo, hi))
+        assert lo <= c <= hi
+
+
+# ------------------------------------------------------------------------------------------------ GPU
+GUARD = 8
+
+
+class Placed(object):
+    """`n` elements that start `off` elements into a larger sentinel-filled buffer (off = 0: 16-byte aligned, as the allocator gives)."""
+
+    def __init__(self, n, dtype, off, src=None):
+        self.n, self.off = n, off
+        self.buf = torch.empty(off + n + GUARD, dtype=dtype, device=DEV)
+        self.sentinel = float("nan") if dtype.is_floating_point else 0xAB
+        self.buf.fill_(self.sentinel)
+        self.view = self.buf[off:off + n]
+        if src is not None:
+            self.view.copy_(torch.from_numpy(np.ascontiguousarray(src).reshape(-1)))
+        assert self.buf.data_ptr() % 16 == 0
+
+    def guards_untouched(self):
+        g = torch.cat([self.buf[:self.off], self.buf[self.off + self.n:]])
+        return bool(torch.isnan(g).all()) if self.buf.dtype.is_floating_point else bool((g == self.sentinel).all())
+
+    def every_element_written(self):
+        return not bool(torch.isnan(self.view).any()) if self.buf.dtype.is_floating_point else True
+
+
+def abi_run(z, u_kind, off=0, philox=None, mode=_lib.SPARSIFY_UAR):
+    """One cspn_sparsify call on caller-owned buffers, every plane `off` elements into its buffer.  u_kind: "f64", "f32" or
+    "philox" (philox = (ids, seed)).  -> dict of numpy arrays mask / sparse / rgbd (rgbd only with rgb)."""
+    L = _lib.lib()
+    B, _, H, W = z["depth"].shape
+    HW = H * W
+    depth = Placed(B * HW, torch.float32, off, z["depth"])
+    has_rgb = "rgb" in z
+    kind, u_ptr, ids_ptr, seed = _lib.UNIFORM_PHILOX, None, None, 0
+    if u_kind == "philox":
+        ids = Placed(B, torch.int64, off % 2, np.asarray(philox[0], np.int64))
+        ids_ptr, seed = ids.view.data_ptr(), philox[1]
+    else:
+        u = Placed(B * HW, torch.float64 if u_kind == "f64" else torch.float32, off,
+                   z["u"] if u_kind == "f64" else z["u"].astype(np.float32))
+        kind, u_ptr = (_lib.UNIFORM_F64 if u_kind == "f64" else _lib.UNIFORM_F32), u.view.data_ptr()
+    mask = Placed(B * HW, torch.uint8, off)
+    work = torch.empty(L.cspn_sparsify_workspace_bytes(B, HW) // 4 + 1, dtype=torch.int32, device=DEV)
+    outs = [mask]
+    if has_rgb:
+        rgb = Placed(B * 3 * HW, torch.uint8 if z["rgb"].dtype == np.uint8 else torch.float32, off, z["rgb"])
+        rgbd = Placed(B * 4 * HW, torch.float32, off)
+        sparse_ptr, sbs = rgbd.view.data_ptr() + 3 * HW * 4, 4 * HW
+        rk = _lib.RGB_U8 if z["rgb"].dtype == np.uint8 else _lib.RGB_F32
+        rgb_ptr, rout_ptr = rgb.view.data_ptr(), rgbd.view.data_ptr()
+        outs.append(rgbd)
+    else:
+        sparse = Placed(B * HW, torch.float32, off)
+        sparse_ptr, sbs, rk, rgb_ptr, rout_ptr = sparse.view.data_ptr(), HW, _lib.RGB_NONE, None, None
+        outs.append(sparse)
+    assert (depth.view.data_ptr() % 16 == 0) == (off % 4 == 0)
+    _lib.check(L.cspn_sparsify(depth.view.data_ptr(), _lib.CSPN_F32, B, H, W, mode, int(z["num_samples"]), float(np.float32(float(z["max_depth"]))),
+                               u_ptr, kind, ids_ptr, seed, sparse_ptr, sbs, rgb_ptr, rk, rout_ptr, 4 * HW, HW, mask.view.data_ptr(),
+                               work[off % 2:].data_ptr(), torch.cuda.current_stream().cuda_stream), "cspn_sparsify")
+    torch.cuda.synchronize()
+    for o in outs:                  # (the dense mode copies the depth's NaNs: there the comparison with the depth says what was written)
+        assert o.guards_untouched() and (mode == _lib.SPARSIFY_DENSE or o.every_element_written())
+    res = dict(mask=host(mask.view).reshape(B, 1, H, W))
+    assert set(np.unique(res["mask"]).tolist()) <= {0, 1}
+    res["mask"] = res["mask"].astype(bool)
+    if has_rgb:
+        res["rgbd"] = host(rgbd.view).reshape(B, 4, H, W)
+        res["sparse"] = np.ascontiguousarray(res["rgbd"][:, 3:4])
+    else:
+        res["sparse"] = host(sparse.view).reshape(B, 1, H, W)
+    return res
+
+
+def equals_reference(res, z):
+    ok = np.array_equal(res["mask"], z["mask"]) and sc.same_bits(res["sparse"], z["sparse"])
+    if "rgbd" in z:
+        ok = ok and sc.same_bits(res["rgbd"], z["rgbd"])
+    return ok
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", NAMES)
+def test_case_through_the_c_abi_is_bit_equal_to_the_reference(name):
+    """fp64 u; fp32 u where the stored plane fits fp32; each also with every plane one element off its buffer's alignment
+    (the element-wise path of every load and store) — all equal to the reference, hence to each other."""
+    z = golden(name)
+    kinds = ["f64"] + (["f32"] if sc.fp32_exact(z["u"]) else [])
+    assert kinds == ["f64", "f32"] or sc.CASES[name[len("g21_sparsify_"):]]["u"] != "f32"
+    for u_kind in kinds:
+        for off in (0, 1, 2, 3):
+            assert equals_reference(abi_run(z, u_kind, off), z), (name, u_kind, off)
+
+
+def module_run(z, uniform, rgb=None, depth=None):
+    us = sparsifier_of(z)
+    depth = dev(z["depth"]) if depth is None else depth
+    mask = us.dense_to_sparse(rgb, depth, uniform=uniform)
+    sparse = d2s.create_sparse_depth(us, rgb, depth, uniform=uniform)
+    assert mask.dtype == torch.bool and mask.shape == depth.shape and sparse.dtype == torch.float32 and sparse.shape == depth.shape
+    res = dict(mask=host(mask), sparse=host(sparse))
+    if rgb is not None:
+        rgbd, view = d2s.create_rgbd(us, rgb, depth, uniform=uniform)
+        assert rgbd.shape == (depth.shape[0], 4) + tuple(depth.shape[2:]) and rgbd.is_contiguous()
+        assert view.data_ptr() == rgbd[:, 3:4].data_ptr() and view.shape == depth.shape and view.stride() == rgbd[:, 3:4].stride()
+        res["rgbd"] = host(rgbd)
+        assert sc.same_bits(host(view), res["sparse"])
+    return res
+
+
+def off_view(a, off):
+    """the values of numpy `a` as a device tensor of its shape that starts `off` elements into a larger buffer"""
+    return Placed(a.size, torch.from_numpy(a.reshape(-1)[:1]).dtype, off, a).view.view(a.shape)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", NAMES)
+def test_case_through_the_module_is_bit_equal_to_the_reference(name):
+    z = golden(name)
+    rgb = dev(z["rgb"]) if "rgb" in z else None
+    assert equals_reference(module_run(z, dev(z["u"]), rgb), z)
+    if sc.fp32_exact(z["u"]):
+        assert equals_reference(module_run(z, dev(z["u"].astype(np.float32)), rgb), z)
+    # views that start inside larger buffers: nothing is 16-byte aligned
+    u_off = off_view(z["u"], 1)
+    rgb_off = off_view(z["rgb"], 1) if "rgb" in z else None
+    depth_off = off_view(z["depth"], 3)
+    assert depth_off.data_ptr() % 16 == 12 and u_off.data_ptr() % 16 == 8
+    assert equals_reference(module_run(z, u_off, rgb_off, depth_off), z)
+
+
+@pytest.mark.gpu
+def test_dense_mode_puts_the_depth_in_unchanged():
+    """sparsifier None (dataloader.py:86-87): channel 3 is the dense depth, NaN payloads, infinities, negatives and -0.0 included."""
+    z = golden("g21_sparsify_hostile_2x5x7")
+    depth = z["depth"].copy()
+    depth.reshape(-1).view(np.uint32)[9] = 0x7fc12345                           # a NaN with a payload
+    rgb = sc.make_rgb(dict(sc.CASES["hostile_2x5x7"], rgb="u8"))
+    for off in (0, 1):
+        rgbd, view = d2s.create_rgbd(None, off_view(rgb, off), off_view(depth, off))
+        assert sc.same_bits(host(rgbd), sc.restate_rgbd(rgb, depth)) and sc.same_bits(host(view), depth)
+    res = abi_run(dict(z, depth=depth), "f64", 1, mode=_lib.SPARSIFY_DENSE)
+    assert sc.same_bits(res["sparse"], depth) and res["mask"].all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["g21_sparsify_odd_3x5x7", "g21_sparsify_hostile_cut_2x5x7", "g21_sparsify_two_slices_2x37x41",
+                                  "g21_sparsify_valid_1x1", "g21_sparsify_frame_57x76"])
+def test_generated_mode_equals_the_numpy_philox(name):
+    """Frame ids on both sides of 2^32 and a 64-bit seed: mask and sparse equal the restatement fed philox_plane, through the C ABI
+    (aligned and not) and through the module."""
+    z = golden(name)
+    B, _, H, W = z["depth"].shape
+    ids, seed = [5, (1 << 33) + 1, (1 << 63) - 1][:B], 0xfedcba9876543210
+    u = sc.philox_plane((B, H, W), ids, seed)
+    want_mask, want_sparse = sc.restate(z["depth"], u, int(z["num_samples"]), float(z["max_depth"]))
+    assert 0 < want_mask.sum() < (z["depth"] > 0).sum() or name.endswith("1x1")
+    for off in (0, 1):
+        res = abi_run(z, "philox", off, philox=(ids, seed))
+        assert np.array_equal(res["mask"], want_mask) and sc.same_bits(res["sparse"], want_sparse)
+        if "rgbd" in z:
+            assert sc.same_bits(res["rgbd"], sc.restate_rgbd(z["rgb"], want_sparse))
+    us, depth, tid = sparsifier_of(z), dev(z["depth"]), torch.tensor(ids, dtype=torch.int64, device=DEV)
+    assert np.array_equal(host(us.dense_to_sparse(None, depth, frame_ids=tid, seed=seed)), want_mask)
+    assert sc.same_bits(host(d2s.create_sparse_depth(us, None, depth, frame_ids=tid, seed=seed)), want_sparse)
+    # default ids are 0 .. B-1, default seed 0
+    want0, _ = sc.restate(z["depth"], sc.philox_plane((B, H, W), range(B), 0), int(z["num_samples"]), float(z["max_depth"]))
+    assert np.array_equal(host(us.dense_to_sparse(None, depth)), want0)
+
+
+@pytest.mark.gpu
+def test_a_frame_id_means_the_same_mask_wherever_the_frame_sits():
+    """Frame id 41 at b = 0 of B = 1 and at b = 2 of B = 3 (5 x 7: frame 2 starts off alignment, frame 0 on it); other ids and other
+    seeds give other masks."""
+    z = golden("g21_sparsify_odd_3x5x7")
+    us = d2s.UniformSampling(12)
+    frame = np.ascontiguousarray(z["depth"][2:3])
+    batch = np.concatenate([z["depth"][0:2], frame])
+    ids = lambda *v: torch.tensor(v, dtype=torch.int64, device=DEV)             # noqa: E731
+    alone = host(us.dense_to_sparse(None, dev(frame), frame_ids=ids(41), seed=9))
+    third = host(us.dense_to_sparse(None, dev(batch), frame_ids=ids(7, 8, 41), seed=9))
+    assert alone.any() and np.array_equal(alone[0], third[2])
+    want, _ = sc.restate(frame, sc.philox_plane((1, 5, 7), [41], 9), 12)
+    assert np.array_equal(alone, want)
+    other_id = host(us.dense_to_sparse(None, dev(frame), frame_ids=ids(42), seed=9))
+    other_seed = host(us.dense_to_sparse(None, dev(frame), frame_ids=ids(41), seed=10))
+    high_id = host(us.dense_to_sparse(None, dev(frame), frame_ids=ids(41 + (1 << 32)), seed=9))
+    high_seed = host(us.dense_to_sparse(None, dev(frame), frame_ids=ids(41), seed=9 + (1 << 32)))
+    for m in (other_id, other_seed, high_id, high_seed):
+        assert m.any() and not np.array_equal(m, alone)
+    # the same frame twice in one batch under different ids: two different masks; under the same id: the same mask
+    twice = np.concatenate([frame, frame])
+    m = host(us.dense_to_sparse(None, dev(twice), frame_ids=ids(41, 42), seed=9))
+    assert np.array_equal(m[0], alone[0]) and np.array_equal(m[1], other_id[0])
+    m = host(us.dense_to_sparse(None, dev(twice), frame_ids=ids(41, 41), seed=9))
+    assert np.array_equal(m[0], m[1])
+
+
+@pytest.mark.gpu
+def test_sample_count_of_a_full_frame_lies_within_six_sigma():
+    """228 x 304, every pixel valid, 500 samples: 68 units-of-1024 > 64 slices, so some count slices take two trips.  The device mask
+    equals the restatement's, and its count lies within 6 binomial standard deviations of 500 (count_bounds)."""
+    H, W = FULL_HW
+    lo, hi = count_bounds()
+    depth = (np.random.RandomState(7).uniform(0.5, 10.0, (3, 1, H, W))).astype(np.float32)
+    us = d2s.UniformSampling(500)
+    ids = torch.arange(3, dtype=torch.int64, device=DEV)
+    mask = us.dense_to_sparse(None, dev(depth), frame_ids=ids, seed=FULL_SEED)
+    counts = [int(v) for v in mask.sum(dim=(1, 2, 3)).cpu()]
+    print("counts %s, bounds %.1f .. %.1f" % (counts, lo, hi))
+    assert all(lo <= c <= hi for c in counts)
+    want, want_sparse = sc.restate(depth, sc.philox_plane((3, H, W), range(3), FULL_SEED), 500)
+    assert np.array_equal(host(mask), want)
+    # 15 % invalid: n_keep differs per frame and spans all 64 slices; fp32 RGB next to it
+    depth[np.random.RandomState(8).uniform(size=depth.shape) < 0.15] = 0.0
+    rgb = np.random.RandomState(9).uniform(size=(3, 3, H, W)).astype(np.float32)
+    want, want_sparse = sc.restate(depth, sc.philox_plane((3, H, W), range(3), FULL_SEED), 500)
+    rgbd, view = d2s.create_rgbd(us, dev(rgb), dev(depth), frame_ids=ids, seed=FULL_SEED)
+    assert sc.same_bits(host(rgbd), sc.restate_rgbd(rgb, want_sparse)) and all(lo <= int(m.sum()) <= hi for m in want)
+
+
+@pytest.mark.gpu
+def test_no_lds_is_read_before_it_is_written():
+    z = golden("g21_sparsify_frame_57x76")
+    with lds_poison():
+        res = module_run(z, dev(z["u"]), dev(z["rgb"]))
+        torch.cuda.synchronize()
+    assert equals_reference(res, z)
+
+
+@pytest.mark.gpu
+def test_call_does_not_synchronise():
+    z = golden("g21_sparsify_odd_3x5x7")
+    us, rgb, depth, ids = sparsifier_of(z), dev(z["rgb"]), dev(z["depth"]), torch.arange(3, dtype=torch.int64, device=DEV)
+    d2s.create_rgbd(us, rgb, depth, frame_ids=ids, seed=3)                       # first use: library load, allocator warm-up
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        rgbd, _ = d2s.create_rgbd(us, rgb, depth, frame_ids=ids, seed=3)
+        mask = us.dense_to_sparse(rgb, depth, frame_ids=ids, seed=3)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    want, want_sparse = sc.restate(z["depth"], sc.philox_plane((3, 5, 7), range(3), 3), int(z["num_samples"]))
+    assert np.array_equal(host(mask), want) and sc.same_bits(host(rgbd), sc.restate_rgbd(z["rgb"], want_sparse))
+
+
+@pytest.mark.gpu
+def test_captured_loop_replays_what_eager_calls_compute():
+    """create_rgbd followed by `ids += B`, captured once and replayed three times = three eager calls with the ids advanced."""
+    z = golden("g21_sparsify_frame_57x76")
+    depth3 = np.concatenate([z["depth"], np.roll(z["depth"], 5, axis=3), np.roll(z["depth"], 11, axis=2)])
+    rgb3 = np.concatenate([z["rgb"], np.roll(z["rgb"], 3, axis=3), np.roll(z["rgb"], 7, axis=2)])
+    us, B, seed, start = d2s.UniformSampling(500), 3, 77, 1000
+    rgb, depth = dev(rgb3), dev(depth3)
+    ids = torch.arange(start, start + B, dtype=torch.int64, device=DEV)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            d2s.create_rgbd(us, rgb, depth, frame_ids=ids, seed=seed)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        static_rgbd, static_sparse = d2s.create_rgbd(us, rgb, depth, frame_ids=ids, seed=seed)
+        ids += B
+    assert ids.tolist() == [start, start + 1, start + 2]                          # a capture runs nothing
+    seen = []
+    for k in range(3):
+        graph.replay()
+        torch.cuda.synchronize()
+        eager_ids = torch.arange(start + k * B, start + (k + 1) * B, dtype=torch.int64, device=DEV)
+        eager, _ = d2s.create_rgbd(us, rgb, depth, frame_ids=eager_ids, seed=seed)
+        assert torch.equal(static_rgbd.view(torch.int32), eager.view(torch.int32))
+        assert torch.equal(static_sparse.contiguous().view(torch.int32), eager[:, 3:4].contiguous().view(torch.int32))
+        want, want_sparse = sc.restate(depth3, sc.philox_plane((B, 57, 76), range(start + k * B, start + (k + 1) * B), seed), 500)
+        assert sc.same_bits(host(eager), sc.restate_rgbd(rgb3, want_sparse))
+        seen.append(host(static_sparse) != 0)
+    assert ids.tolist() == [start + 3 * B, start + 3 * B + 1, start + 3 * B + 2]
+    assert not np.array_equal(seen[0], seen[1]) and not np.array_equal(seen[1], seen[2])
+
+
+@pytest.mark.gpu
+def test_the_sparse_view_feeds_the_propagation_like_a_contiguous_copy():
+    """CSPN_new.AffinityPropagate given rgbd[:, 3:4] (a view with the batch stride of the 4-channel input) returns the bits it returns
+    for a contiguous copy of the same plane."""
+    from oracle import cspn_oracle as orc
+    B, H, W = 2, 57, 76
+    g, d, _ = orc.synthetic_inputs(211, B, H, W, 8)
+    rgb = np.random.RandomState(212).uniform(size=(B, 3, H, W)).astype(np.float32)
+    ids = torch.arange(B, dtype=torch.int64, device=DEV)
+    rgbd, sparse = d2s.create_rgbd(d2s.UniformSampling(500), dev(rgb), dev(np.abs(d) + 0.5), frame_ids=ids, seed=5)
+    assert not sparse.is_contiguous() and 300 < int((sparse > 0).sum()) < 2 * 700
+    m = pkg.CSPN_new.AffinityPropagate(12, 3)
+    with torch.no_grad():
+        a = m(dev(g), dev(d), sparse)
+        b = m(dev(g), dev(d), sparse.contiguous())
+    assert a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
+    assert bool(torch.isfinite(a).all()) and not torch.equal(a, dev(d))

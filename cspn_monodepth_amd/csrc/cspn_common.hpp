@@ -172,6 +172,54 @@ __device__ __forceinline__ void div8_shared_reciprocal(const float (&a)[8], floa
     }
 #endif
 }
+// The same for the four pixels of a quad, in place (w[k][e]: gate k of pixel e -> its quotient), with the true division behind ONE
+// wave-uniform test (a ballot over the wavefront) per quad.  In the per-pixel form above the compiler gives each of the 8 quotients
+// its own exec-masked division sequence (v_div_scale x 2 / v_div_fmas / v_div_fixup inside s_and_saveexec + s_cbranch_execz): in the
+// derive of the 768-thread resident launch 88 such regions per wavefront, issued or skipped for an S that real guidance never
+// produces.  Here the shared reciprocal is formed branch-free for every pixel, and a wavefront that holds an out-of-range S takes one
+// cold block that redoes the quad with a select per quotient.  Both sides give every lane the bits of div8_shared_reciprocal.
+// `keep` = false zeroes the quad instead (w must then hold zeros already: the reciprocal is replaced by 0, which costs 4 selects
+// where zeroing the 32 quotients costs 32).
+// (`&` / `|`, not `&&` / `||`: three compares and two scalar mask operations; the short-circuit form becomes exec-masked regions)
+__device__ __forceinline__ bool reciprocal_in_range(float S) { return (S <= 0x1p+100f) & ((S >= 0x1p-100f) | (S == 0.f)); }
+__device__ __forceinline__ float reciprocal_newton(float S) {
+    float r = __builtin_amdgcn_rcpf(S);
+    const float e = fmaf(-S, r, 1.0f);
+    return fmaf(e, r, r);
+}
+__device__ __forceinline__ void div8_quad_shared_reciprocal(float (&w)[8][4], const float (&S)[4], bool keep = true) {
+#ifndef CSPN_IEEE_NORMALISE
+    float r[4];
+    bool okr[4], bad = false;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        okr[e] = !keep | reciprocal_in_range(S[e]);
+        r[e] = keep ? reciprocal_newton(S[e]) : 0.f;
+        bad |= !okr[e];
+    }
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0ull, 0)) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) w[k][e] = okr[e] ? w[k][e] * r[e] : w[k][e] / S[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) w[k][e] *= r[e];
+    }
+#else
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float av[8], qv[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) av[k] = w[k][e];
+        div8_shared_reciprocal(av, S[e], qv);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[k][e] = keep ? qv[k] : 0.f;
+    }
+#endif
+}
 
 // exp(x) for x <= 0 (the max-subtracted logits) on the hardware exponential: v_exp_f32 is 2^t to 1 ulp; the product
 // x * log2(e) is formed in two pieces (fma recovers its rounding error) so that the result stays within ~2 ulp of

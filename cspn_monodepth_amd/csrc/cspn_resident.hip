@@ -69,7 +69,15 @@ struct ResArgs {
     unsigned long long* dbg;  // developer probe: [grid][16] wall-clock stamps (100 MHz) per workgroup, or null
     int th0, thl;            // heights of the first / last tile row (res_row_h); th is the height of the rows in between.  (Last: only the
                              // clipped instances read them, and the kernel arguments of the others stay where their code was tuned.)
+    // Quotients the kernel needs in front of its first load, as host-made reciprocals (res_magic / res_div): a division by a run-time
+    // value is ~20 dependent instructions, and five of them stood between the kernel's entry and the request for the depth region.
+    unsigned mg_wq, mg_tiles_x, mg_tpi, mg_round;       // of wq, tiles_x, tiles_x * tiles_y, nb * tiles_x * tiles_y
+    int step_r, step_q;                                 // NTHREADS / wq and NTHREADS % wq of the launch's instance
 };
+// n / d for 0 <= n < 2^16, 1 <= d < 2^16 as the high word of n * ceil(2^32 / d): exact, because the excess n * (d * m - 2^32) / (d * 2^32)
+// of n * m / 2^32 over n / d stays below 1 / d while n * d < 2^32.  d == 1 has no 32-bit reciprocal: m = 0 stands for it.
+inline unsigned res_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1u) / (unsigned)d); }
+__device__ __forceinline__ int res_div(int n, unsigned m) { return m ? (int)__umulhi((unsigned)n, m) : n; }
 
 __device__ __forceinline__ void st4_dev(float* base, unsigned elem, float a, float b, float c, float d) {
     // ONE 16-byte device-scope store (global_store_dwordx4 ... sc1): visible to every XCD once vmcnt drops.  Written as
@@ -204,6 +212,12 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
     // (no shifted gather at all), times the forward's refined reciprocal of S at the 3 x 3 neighbours (NQ + 2 aligned row quads
     // of ONE plane per thread, neighbours by DPP, strip ends by scalars).  The training forward then publishes S only: the
     // 53 MB volume of config 2 is neither written nor read (the tail rebuilds its w_j the same way, cspn_backward.hip).
+    // LEAN: the 768-thread instances (CLEAN by construction, the flagship's) run the derive with host-made reciprocals in place of their
+    // prologue divisions, without the selects a CLEAN launch cannot need, with one pixel offset per thread and with ONE cold division
+    // block per quad (div8_quad_shared_reciprocal).  Same bits.  The 512- / 1024-thread instances keep their code: the NQ = 5 ones are
+    // register-tuned to the last scratch slot, and this form cost them 6-17 more spilled VGPRs (8 x 352 x 1216: +1.4 us, sparse +3.5 us).
+    constexpr bool LEAN = NTHREADS == RES_THREADS_CLIPPED;
+    static_assert(!LEAN || CLEAN, "the clipped instances are CLEAN only");
     constexpr bool SCORE = MODE == 1, TRANSG = MODE == 4, TRANS = MODE == 3 || TRANSG, HIST = MODE == 2 || TRANS;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ int wg_bad;
@@ -215,11 +229,11 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
     // in blockIdx order as round r's finish.  Flags and exchange planes are per image, so the rounds share nothing.  (cspnk_resident's
     // reverse sweep runs that way: cspnk_resident.hip.)
     const int wg_round = a.nb * tiles_per_img;
-    const int round = (int)blockIdx.x / wg_round;
+    const int round = LEAN ? res_div((int)blockIdx.x, a.mg_round) : (int)blockIdx.x / wg_round;
     const int tile = xcd_contiguous_id((int)blockIdx.x - round * wg_round, wg_round);
-    const int bl = tile / tiles_per_img;                 // image within this round
+    const int bl = LEAN ? res_div(tile, a.mg_tpi) : tile / tiles_per_img;                 // image within this round
     const int trem = tile - bl * tiles_per_img;
-    const int ty = trem / a.tiles_x;
+    const int ty = LEAN ? res_div(trem, a.mg_tiles_x) : trem / a.tiles_x;
     const int tx = trem - ty * a.tiles_x;
     const int b = a.b0 + round * a.nb + bl;
     const int H = a.H, W = a.W;
@@ -257,7 +271,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
 
     // ---- ownership: strip (sx, sy) = NQ vertically consecutive quads of the weight region (tile + halo) -------------
     const int wq = a.wq, wr = a.wr;
-    const int sy = tid / wq;
+    const int sy = LEAN ? res_div(tid, a.mg_wq) : tid / wq;
     const int sx = tid - sy * wq;
     const int r0 = sy * NQ;
     // Region origin: the tile's halo is laid out around it, but SHIFTED back into the image at image edges (a region that
@@ -290,22 +304,25 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
     unsigned st0_in = 0;
     // quad u * NTHREADS + tid of the region, row-major: (row, qx) advances by a uniform (NTHREADS / wq, NTHREADS % wq) per
     // u — no per-quad division, whose temporaries the register-bound derive cannot afford
-    const int step_r = NTHREADS / wq, step_q = NTHREADS - step_r * wq;
+    const int step_r = LEAN ? a.step_r : NTHREADS / wq, step_q = LEAN ? a.step_q : NTHREADS - step_r * wq;
     {
     int row = sy, qx = sx;
+    // ... LEAN: and no per-quad multiply either, the pixel offset advances with (row, qx)
+    int soff = (yd0 + sy) * W + xd0 + 4 + 4 * sx;
+    const int soff_step = step_r * W + 4 * step_q, soff_wrap = W - 4 * wq;
 #pragma unroll
     for (int u = 0; u <= NQ; ++u) {
         const int y = yd0 + row, x = xd0 + 4 + 4 * qx;
         const bool valid = row < dr;
         const bool in = valid && (y >= 0 && y < H && x >= 0 && x < a.Wv);
         if (in) st0_in |= 1u << u;
-        st0[u] = ld4(at32(din0, in ? (unsigned)(y * W + x) : 0u));
+        st0[u] = ld4(at32(din0, in ? (unsigned)(LEAN ? soff : y * W + x) : 0u));
         if (TRANS && BLEND) {                          // PREMASK: the sweep starts from (1-m) G_T
             const float4 sp = ld4(at32(spg, in ? (unsigned)(y * W + x) : 0u));
             st0[u].x *= 1.f - sgnf(sp.x); st0[u].y *= 1.f - sgnf(sp.y); st0[u].z *= 1.f - sgnf(sp.z); st0[u].w *= 1.f - sgnf(sp.w);
         }
-        row += step_r; qx += step_q;
-        if (qx >= wq) { qx -= wq; ++row; }
+        row += step_r; qx += step_q; soff += soff_step;
+        if (qx >= wq) { qx -= wq; ++row; soff += soff_wrap; }
     }
     }
     float ring0 = 0.f;
@@ -336,6 +353,9 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
     // scalars are requested right behind quad i's planes and the arithmetic below can start on quad 0 while quads 1.. stream.)
     float edge[NQ][6];                     // [0..2]: column xq-1 of the dx<0 taps (j = 0,3,5); [3..5]: column xq+4 of the dx>0 taps (j = 2,4,7)
     const unsigned ucs = (unsigned)a.g_cs;
+    // LEAN: one pixel offset per thread (the quad of row yq0) and uniform multiples of W from there; the channel sits in the (scalar)
+    // base of the load, not in its offset: no multiply and no addition per load.
+    const int o0 = yq0 * W + xq;
     // MODE 4: rows yq0-1 .. yq0+NQ of S, requested in front of the guidance (in-order return: the reciprocals are formed while
     // the guidance streams); [m][0..3] the aligned quad, [m][4] / [m][5] columns xq-1 / xq+4 for the strip-end lanes
     float srow[TRANSG ? NQ + 2 : 1][6];
@@ -355,7 +375,9 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
         const int r = r0 + i, y = yq0 + i;
-        const bool ok = (r < wr) && x_in && (y >= 0) && (y < H);
+        // LEAN (CLEAN): every region lies inside the image and Wv == W, so a row of the region is a row of the image and every owned quad
+        // has its four columns: what is left is the rows past the region and, for the dy = +-1 taps, the image's first and last row
+        const bool ok = LEAN ? (r < wr) : ((r < wr) && x_in && (y >= 0) && (y < H));
         if (ok) in_img |= 1u << i;
         if (ok && y >= y0 && y < y0 + th_t && xq >= x0 && xq < x0 + a.tw) interior |= 1u << i;
         unsigned orow[3];
@@ -364,13 +386,14 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
         for (int d = 0; d < 3; ++d) {
             const int row = y + d - 1;
             rokv[d] = ok && row >= 0 && row < H;
-            orow[d] = rokv[d] ? (unsigned)(row * W + xq) : 0u;   // outside the image: a safe address of the plane, zeroed below
+            orow[d] = rokv[d] ? (unsigned)(LEAN ? o0 + (i + d - 1) * W : row * W + xq) : 0u;   // outside the image: a safe address of the plane, zeroed below
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int lin = j < 4 ? j : j + 1;
             const int d = (PAC || TRANSG) ? 1 : lin / 3;              // PAC / MODE 4: channel j at the quad itself
-            const float4 v = ld4(at32(gq, (unsigned)((PAC || TRANSG) ? j : 7 - j) * ucs + orow[d]));
+            const int ch = (PAC || TRANSG) ? j : 7 - j;
+            const float4 v = ld4(LEAN ? at32(gq + (size_t)ch * a.g_cs, orow[d]) : at32(gq, (unsigned)ch * ucs + orow[d]));
             wreg[i][j][0] = rokv[d] ? v.x : 0.f; wreg[i][j][1] = rokv[d] ? v.y : 0.f;
             wreg[i][j][2] = rokv[d] ? v.z : 0.f; wreg[i][j][3] = rokv[d] ? v.w : 0.f;
         }
@@ -386,7 +409,8 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
                 const int xx = lft ? xq - 1 : xq + 4;
                 const bool c = rokv[d] && (lft ? fix_left : fix_right) && xx >= 0 && xx < W;
                 // raw value only: consuming it here would make this block wait for the quad's loads (in-order return)
-                edge[i][t] = ld1(at32(gq, (unsigned)(7 - j) * ucs + (c ? orow[d] + (unsigned)(xx - xq) : 0u)));
+                edge[i][t] = ld1(LEAN ? at32(gq + (size_t)(7 - j) * a.g_cs, c ? orow[d] + (unsigned)(xx - xq) : 0u)
+                                      : at32(gq, (unsigned)(7 - j) * ucs + (c ? orow[d] + (unsigned)(xx - xq) : 0u)));
             }
         }
     }
@@ -511,6 +535,16 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
             for (int e = 0; e < 4; ++e)
 #pragma unroll
                 for (int j = 0; j < NT; ++j) wreg[i][j][e] = (ok && e < nval) ? wreg[i][j][e] : 0.f;
+        } else if constexpr (LEAN) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float S = wreg[i][7][e];
+#pragma unroll
+                for (int k = 1; k < 8; ++k) S += wreg[i][7 - k][e];
+                Sq[e] = S;
+            }
+            // a quad is kept or dropped as a whole, and a dropped one holds zero gates (every tap select above has `ok` in it)
+            div8_quad_shared_reciprocal(wreg[i], Sq, ok);
         } else
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -1353,6 +1387,8 @@ int resident_launch(const void* guidance, long bs, long cs, const void* d0, cons
     a.wq = g.wq; a.wr = g.wr; a.hxw = g.hxw; a.hyw = g.hyw; a.dr = g.dr; a.ls = g.ls;
     a.spin_limit = plan_spin_limit(rp);
     a.dbg = rp.debug_stamps;
+    a.mg_wq = res_magic(g.wq); a.mg_tiles_x = res_magic(g.tiles_x); a.mg_tpi = res_magic(g.tiles_x * g.tiles_y);
+    a.step_r = g.threads / g.wq; a.step_q = g.threads % g.wq;
     const bool clean = regions_inside_image(g, H, W, a.Wv, T);
     // (refused rather than ignored: a host that asked for the guard relies on `out` being complete for GPU-side consumers)
     if (rp.guard && (!resident_form_guarded(form) || (resident_form_mode(form) <= 1 && !out) || !cspn_detail::resident_repair_fits(T)))
@@ -1380,6 +1416,7 @@ int resident_launch(const void* guidance, long bs, long cs, const void* d0, cons
     for (int b0 = 0; b0 < B; b0 += ipl * max_rounds) {
         a.b0 = b0;
         a.nb = (B - b0) < ipl ? (B - b0) : ipl;
+        a.mg_round = res_magic(a.nb * g.tiles_x * g.tiles_y);
         const int rounds = ceil_div(B - b0, ipl) < max_rounds ? ceil_div(B - b0, ipl) : max_rounds;
         a.last_chunk = (b0 + ipl * max_rounds >= B) ? 1 : 0;
         if (!launch(rounds * a.nb * g.tiles_x * g.tiles_y, g.threads, g.lds_bytes, st, a)) return 0;

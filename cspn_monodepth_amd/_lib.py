@@ -15,13 +15,15 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 SO_PATH = os.environ.get("CSPN_HIP_LIB") or os.path.join(_PKG, "libcspn_hip.so")   # env override: A/B builds
 CSRC = os.path.join(_PKG, "csrc")
-SOURCES = ("cspn_propagate.hip", "cspn_resident.hip", "cspnk_resident.hip", "cspnk_d2.hip", "cspn_prepare.hip", "cspn_backward.hip", "cspn_metrics.hip", "cspn_metrics_frame.hip", "cspn_debug.hip", "cspn_repair.hip", "pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_criterion.hip", "cspn_max8.hip", "cspn_abn.hip", "cspn_sparsify.hip", "cspn_transform.hip")   # one TU each
+SOURCES = ("cspn_propagate.hip", "cspn_resident.hip", "cspnk_resident.hip", "cspnk_d2.hip", "cspn_prepare.hip", "cspn_backward.hip", "cspn_metrics.hip", "cspn_metrics_frame.hip", "cspn_debug.hip", "cspn_repair.hip", "pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_criterion.hip", "cspn_max8.hip", "cspn_abn.hip", "cspn_sparsify.hip", "cspn_transform.hip", "cspn_losses.hip")   # one TU each
 HEADERS = (os.path.join(CSRC, "cspn_common.hpp"), os.path.join(CSRC, "cspnk_helpers.hpp"), os.path.join(_ROOT, "include", "cspn_hip.h"))
 INCLUDE = os.path.join(_ROOT, "include")
-# include/cspn_criterion.h, include/cspn_max8.h, include/cspn_abn.h, include/cspn_sparsify.h, include/cspn_transform.h, csrc/pac_launch.hpp: part of the build's staleness hash, NOT of code_digest() — no benchmarked
+# include/cspn_criterion.h, include/cspn_max8.h, include/cspn_abn.h, include/cspn_sparsify.h, include/cspn_transform.h, include/cspn_losses.h,
+# csrc/pac_launch.hpp, csrc/cspn_loss_units.hpp: part of the build's staleness hash, NOT of code_digest() — no benchmarked
 # kernel sees it, and a digest that moved would mark the HBM traffic recorded under profiles/ as stale (bench.py `traffic_stale`)
 BUILD_HEADERS = HEADERS + (os.path.join(INCLUDE, "cspn_criterion.h"), os.path.join(INCLUDE, "cspn_max8.h"), os.path.join(INCLUDE, "cspn_abn.h"),
-                           os.path.join(INCLUDE, "cspn_sparsify.h"), os.path.join(INCLUDE, "cspn_transform.h"), os.path.join(CSRC, "pac_launch.hpp"))
+                           os.path.join(INCLUDE, "cspn_sparsify.h"), os.path.join(INCLUDE, "cspn_transform.h"), os.path.join(CSRC, "pac_launch.hpp"),
+                           os.path.join(INCLUDE, "cspn_losses.h"), os.path.join(CSRC, "cspn_loss_units.hpp"))
 
 CSPN_F32, CSPN_F16 = 0, 1
 ABI_VERSION = 10         # CSPN_ABI_VERSION of include/cspn_hip.h this host code was written against
@@ -41,6 +43,9 @@ TRANSFORM_ABI_VERSION = 1   # CSPN_TRANSFORM_ABI_VERSION of include/cspn_transfo
 TRANSFORM_VAL, TRANSFORM_TRAIN = 0, 1                       # cspn_transform's `mode`
 TRANSFORM_PARAMS, TRANSFORM_GATHER_PIXELS, TRANSFORM_MAX_SECOND = 8, 256, 32768
 LOSS_L1, LOSS_L2, LOSS_L1_LOG = 0, 1, 2
+LOSSES_ABI_VERSION = 1      # CSPN_LOSSES_ABI_VERSION of include/cspn_losses.h
+MEAN_L1, MEAN_GRAD, MEAN_RMSE, MEAN_RMSE_LOG = 0, 1, 2, 3   # the `kind` of cspn_mean_loss_*
+LOSSES_STATE_BYTES = 48
 BLEND_NONE, BLEND_SPARSE, BLEND_PREMASK = 0, 1, 2
 
 # every symbol include/cspn_hip.h declares (tests check the .so exports all of them)
@@ -65,6 +70,9 @@ SPARSIFY_EXPORTS = ("cspn_sparsify_abi_version", "cspn_sparsify_slices", "cspn_s
 # every symbol include/cspn_transform.h declares
 TRANSFORM_EXPORTS = ("cspn_transform_abi_version", "cspn_transform_first_size", "cspn_transform_workspace_bytes", "cspn_transform",
                      "cspn_transform_draw_params")
+# every symbol include/cspn_losses.h declares
+LOSSES_EXPORTS = ("cspn_losses_abi_version", "cspn_losses_workspace_bytes", "cspn_berhu_forward", "cspn_berhu_backward",
+                  "cspn_mean_loss_forward", "cspn_mean_loss_backward")
 
 
 class cspn_plan(ctypes.Structure):
@@ -92,7 +100,7 @@ class cspn_abn_plan(ctypes.Structure):           # cspn_abn_plan_t (include/cspn
 
 
 BENCH_UNRELATED = ("pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_metrics_frame.hip", "cspn_criterion.hip", "cspn_max8.hip",
-                   "cspn_abn.hip", "cspn_sparsify.hip", "cspn_transform.hip")       # kernels no bench.py workload launches
+                   "cspn_abn.hip", "cspn_sparsify.hip", "cspn_transform.hip", "cspn_losses.hip")       # kernels no bench.py workload launches
 
 
 def _source_digest(flags, code_only=False):
@@ -274,6 +282,17 @@ def _declare(lib):
     lib.cspn_transform.restype = ci
     lib.cspn_transform_draw_params.argtypes = [vp, ci, ull, vp, vp]
     lib.cspn_transform_draw_params.restype = ci
+    lib.cspn_losses_abi_version.restype = ci
+    lib.cspn_losses_workspace_bytes.argtypes = [cs]
+    lib.cspn_losses_workspace_bytes.restype = cs
+    lib.cspn_berhu_forward.argtypes = [vp, vp, ci, cs, vp, vp, vp]
+    lib.cspn_berhu_forward.restype = ci
+    lib.cspn_berhu_backward.argtypes = [vp, vp, ci, cs, vp, vp, vp, vp]
+    lib.cspn_berhu_backward.restype = ci
+    lib.cspn_mean_loss_forward.argtypes = [vp, vp, ci, ci, cs, vp, vp, vp]
+    lib.cspn_mean_loss_forward.restype = ci
+    lib.cspn_mean_loss_backward.argtypes = [vp, vp, ci, ci, cs, vp, vp, vp, vp]
+    lib.cspn_mean_loss_backward.restype = ci
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("cspn_last_error", "cspn_propagate_workspace_bytes", "cspn3_resident_workspace_bytes",
@@ -305,6 +324,8 @@ def lib():
                     raise RuntimeError("cspn_monodepth_amd: sparsify ABI version mismatch")
                 if _lib.cspn_transform_abi_version() != TRANSFORM_ABI_VERSION:
                     raise RuntimeError("cspn_monodepth_amd: transform ABI version mismatch")
+                if _lib.cspn_losses_abi_version() != LOSSES_ABI_VERSION:
+                    raise RuntimeError("cspn_monodepth_amd: losses ABI version mismatch")
                 poison = os.environ.get("CSPN_DEBUG_LDS_POISON", "")      # debugging aid (include/cspn_hip.h): "nan" or a hex word
                 if poison and poison != "0":
                     _lib.cspn_debug_set_lds_poison(1, 0x7fc00000 if poison in ("1", "nan") else int(poison, 16), None)

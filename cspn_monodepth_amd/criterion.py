@@ -4,8 +4,13 @@
 
 `get_criteria(args)` offers what the reference's does (libs/criterion/__init__.py:11-30): `args.criterion` in l1 / l2 / l1_log
 -> MaskedL1Loss / MaskedMSELoss / L1_log (criteria.py:14-39, 91-107), wrapped by `args.loss_wrapper`: "dsn" -> CriterionDSN
-(loss1 + 0.4 * loss2), anything else -> Criterion_No_DSN (criteria.py:170-219).  berHuLoss, BerHu, RMSE*, L1, GradLoss and
-NormalLoss are not here: get_criteria does not offer them either, and berHu needs a dependent max pass.
+(loss1 + 0.4 * loss2), anything else -> Criterion_No_DSN (criteria.py:170-219).
+
+The reference's other working criteria are modules to construct directly, as get_criteria does not offer them there either:
+berHuLoss (criteria.py:42-64; works inside both wrappers), RMSE, RMSE_log, L1 and GradLoss (:67-88, :133-152), on the kernels
+of include/cspn_losses.h — berHu's threshold 0.2 * max(pred - target) is a dependent pass on the device, three launches
+forward, and never reaches the host.  BerHu(threshold) and NormalLoss are not built: the reference's BerHu raises IndexError
+(`.numpy()[0]` on a 0-dim array) and its NormalLoss divides [B,C,H,W] by a [B,C,H] norm, which raises for almost every shape.
 
 The reference selects the valid pixels with `diff[valid_mask]`: boolean indexing calls nonzero, a device-to-host copy on every
 step that no graph can capture.  Here a loss is three launches of include/cspn_criterion.h on the current stream — per-slice
@@ -23,6 +28,7 @@ import torch.nn.functional as F
 from . import _lib
 
 KINDS = {"l1": _lib.LOSS_L1, "l2": _lib.LOSS_L2, "l1_log": _lib.LOSS_L1_LOG}
+MEAN_KINDS = {"l1": _lib.MEAN_L1, "grad": _lib.MEAN_GRAD, "rmse": _lib.MEAN_RMSE, "rmse_log": _lib.MEAN_RMSE_LOG}
 STATE_BYTES = 32     # CSPN_CRITERION_STATE_BYTES: float loss, float 1 / count, double sum, double count, 8 reserved
 
 _FP32_ONLY = ("masked_loss: fp32 only, got %s — the gradient of a mean over ~1e6 pixels (g / count) is below the smallest fp16 "
@@ -146,6 +152,125 @@ class CriterionDSN(_Wrapper):
 
     def forward(self, preds, target):
         return self._one(preds[0], target) + 0.4 * self._one(preds[1], target)
+
+
+class _Loss(torch.autograd.Function):
+    """berHu (kind None) or one unmasked mean of include/cspn_losses.h over (a, b) = (pred, target) / (fake, real)."""
+
+    @staticmethod
+    def forward(ctx, a, b, kind):
+        n = a.numel()
+        work, state = losses_workspace(n, a.device)
+        L, st = _lib.lib(), torch.cuda.current_stream(a.device).cuda_stream
+        with torch.cuda.device(a.device):
+            if kind is None:
+                ok = L.cspn_berhu_forward(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, n, work.data_ptr(), state.data_ptr(), st)
+            else:
+                ok = L.cspn_mean_loss_forward(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, kind, n, work.data_ptr(), state.data_ptr(), st)
+        _lib.check(ok, "cspn_berhu_forward" if kind is None else "cspn_mean_loss_forward")
+        ctx.save_for_backward(a, b)
+        ctx.state, ctx.kind = state, kind
+        return state[0]                                  # 0-dim view of the state's first word: no copy, no launch
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable         # double backward raises
+    def backward(ctx, grad_loss):
+        a, b = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        g = grad_loss
+        if g.dtype != torch.float32 or g.device != a.device:
+            g = g.to(device=a.device, dtype=torch.float32)
+        g = g.contiguous()
+        grad = torch.empty_like(a, memory_format=torch.contiguous_format)
+        L, st = _lib.lib(), torch.cuda.current_stream(a.device).cuda_stream
+        with torch.cuda.device(a.device):
+            if ctx.kind is None:
+                ok = L.cspn_berhu_backward(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, a.numel(), ctx.state.data_ptr(), g.data_ptr(),
+                                           grad.data_ptr(), st)
+            else:
+                ok = L.cspn_mean_loss_backward(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, ctx.kind, a.numel(), ctx.state.data_ptr(),
+                                               g.data_ptr(), grad.data_ptr(), st)
+        _lib.check(ok, "cspn_berhu_backward" if ctx.kind is None else "cspn_mean_loss_backward")
+        return grad, None, None
+
+
+def losses_workspace(n, device):
+    """(work, state) of one forward of include/cspn_losses.h over n elements; fresh on every call, as criterion_workspace."""
+    nbytes = _lib.lib().cspn_losses_workspace_bytes(int(n))
+    return (torch.empty((nbytes // 8,), dtype=torch.float64, device=device),
+            torch.empty((_lib.LOSSES_STATE_BYTES // 4,), dtype=torch.float32, device=device))
+
+
+def _checked(who, a, b):
+    if a.dtype != torch.float32:
+        raise TypeError(_FP32_ONLY.replace("masked_loss", who) % (a.dtype,))
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("%s: both tensors must have the same shape and device, got %s and %s" % (who, tuple(a.shape), tuple(b.shape)))
+    if a.numel() < 1:
+        raise ValueError("%s: empty tensors" % who)
+    if not (a.is_cuda and b.is_cuda):
+        raise RuntimeError("%s: tensors must live on a ROCm device (no CPU implementation here)" % who)
+    b = b.detach()
+    if b.dtype != torch.float32:
+        b = b.float()
+    return a.contiguous(), b.contiguous()
+
+
+def berhu_loss(pred, target):
+    """The reverse Huber loss of criteria.py:42-64: c = 0.2 * max(pred - target) over ALL pixels, d = |target - pred| over
+    target > 0, mean of the d and of the d^2 of those with d > c — a 0-dim fp32 device tensor with a gradient for `pred` only
+    (c enters a comparison only).  No valid pixel: NaN, and a zero gradient.  Inputs as masked_loss takes them."""
+    return _Loss.apply(*_checked("berhu_loss", pred, target), None)
+
+
+def unmasked_loss(fake, real, kind):
+    """A mean over all elements: "l1" mean |10 r - 10 f|, "grad" mean |r - f|, "rmse" sqrt(mean (10 r - 10 f)^2), "rmse_log"
+    sqrt(mean (log r - log f)^2) — a 0-dim fp32 device tensor with a gradient for `fake` only."""
+    if kind not in MEAN_KINDS:
+        raise NotImplementedError("unmasked_loss: no criterion named %r (%s)" % (kind, ", ".join(MEAN_KINDS)))
+    return _Loss.apply(*_checked("unmasked_loss", fake, real), MEAN_KINDS[kind])
+
+
+class berHuLoss(nn.Module):
+    """criteria.py:42-64; the result is also kept in self.loss."""
+
+    def forward(self, pred, target):
+        if pred.dim() != target.dim():
+            raise AssertionError("inconsistent dimensions")
+        self.loss = berhu_loss(pred, target)
+        return self.loss
+
+
+class GradLoss(nn.Module):
+    """criteria.py:145-152: mean |target - pred|."""
+
+    def forward(self, pred, target):
+        if pred.dim() != target.dim():
+            raise AssertionError("inconsistent dimensions")
+        return unmasked_loss(pred, target, "grad")
+
+
+class _Unmasked(nn.Module):
+    """(fake, real); a fake of another shape is resized as the reference's F.upsample does: bilinear, align_corners=False."""
+    kind = None
+
+    def forward(self, fake, real):
+        if fake.shape != real.shape and fake.dim() == 4 and real.dim() == 4:
+            fake = F.interpolate(fake, size=tuple(real.shape[-2:]), mode="bilinear", align_corners=False)
+        return unmasked_loss(fake, real, self.kind)
+
+
+class RMSE(_Unmasked):
+    kind = "rmse"
+
+
+class RMSE_log(_Unmasked):
+    kind = "rmse_log"
+
+
+class L1(_Unmasked):
+    kind = "l1"
 
 
 key_to_criteria = {"l1": MaskedL1Loss, "l2": MaskedMSELoss, "l1_log": L1_log}

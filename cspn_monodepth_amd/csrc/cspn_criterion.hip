@@ -11,31 +11,16 @@
 // Whether the 16 bytes of a unit come in one load (16-byte aligned bases) or element by element (a view that starts inside a
 // larger buffer, the partial last unit) changes the load instructions only: both fill the same registers in front of ONE copy
 // of the arithmetic.  The backward is element-wise, so it has no order to fix.
-#include "cspn_common.hpp"
+#include "cspn_loss_units.hpp"
 #include "cspn_criterion.h"
 
 namespace {
-
-constexpr int CRIT_THREADS = 256;      // 4 wavefronts per slice workgroup
-constexpr int CRIT_GROUP = 4;          // units a thread adds in fp32 before the partial goes to fp64 (16 pixels)
-constexpr int CRIT_MAX_SLICES = 1024;
-constexpr int CRIT_BWD_MAX_GRID = 2048;
 
 struct CriterionState {                // include/cspn_criterion.h: CSPN_CRITERION_STATE_BYTES
     float loss, inv_count;
     double sum, count, reserved;
 };
 static_assert(sizeof(CriterionState) == CSPN_CRITERION_STATE_BYTES, "state layout");
-
-// Slices (workgroups) of the forward: a function of n ONLY — one slice per 256 units (1024 pixels) up to 1024 slices, so a
-// 3 x 228 x 304 batch already spreads over 204 workgroups and 24 x 228 x 304 over four per CU; larger inputs grid-stride.
-inline int criterion_slices(size_t n) {
-    const size_t nu = (n + 3) / 4;
-    size_t s = (nu + CRIT_THREADS - 1) / CRIT_THREADS;
-    if (s < 1) s = 1;
-    if (s > CRIT_MAX_SLICES) s = CRIT_MAX_SLICES;
-    return (int)s;
-}
 
 // the term of one pixel, 0 for an invalid one (the selects keep a NaN / Inf of an invalid pixel out of the sum)
 template <int KIND>
@@ -54,25 +39,8 @@ __device__ __forceinline__ void criterion_term(float p, float t, float& sum, flo
     cnt += valid ? 1.f : 0.f;
 }
 
-// pixels [4u, 4u + 4) of both planes; past the end: an invalid pixel (pred 1, target 0)
-__device__ __forceinline__ void load_unit(const float* __restrict__ pred, const float* __restrict__ target, size_t u, size_t n,
-                                          bool vec, float (&p)[4], float (&t)[4]) {
-    const size_t e0 = u * 4;
-    if (vec && e0 + 4 <= n) {
-        const float4 a = ld4(pred + e0), b = ld4(target + e0);
-        p[0] = a.x; p[1] = a.y; p[2] = a.z; p[3] = a.w;
-        t[0] = b.x; t[1] = b.y; t[2] = b.z; t[3] = b.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool in = e0 + e < n;
-            p[e] = in ? ld1(pred + e0 + e) : 1.f;
-            t[e] = in ? ld1(target + e0 + e) : 0.f;
-        }
-    }
-}
-
-// grid (S): workgroup s -> work[s][0] = sum of the term, work[s][1] = valid pixels
+// grid (S): workgroup s -> work[s][0] = sum of the term, work[s][1] = valid pixels; past the end of the planes load_unit
+// (cspn_loss_units.hpp) gives an invalid pixel: pred 1, target 0
 template <int KIND>
 __global__ __launch_bounds__(CRIT_THREADS) void cspn_criterion_slice_kernel(const float* __restrict__ pred,
                                                                             const float* __restrict__ target, size_t n,
@@ -90,7 +58,7 @@ __global__ __launch_bounds__(CRIT_THREADS) void cspn_criterion_slice_kernel(cons
         for (int j = 0; j < CRIT_GROUP; ++j) {
             const size_t u = u0 + (size_t)j * stride;
             if (u < nu) {
-                load_unit(pred, target, u, n, vec, p[j], t[j]);
+                load_unit(pred, target, u, n, vec, p[j], t[j], 1.f, 0.f);
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { p[j][e] = 1.f; t[j][e] = 0.f; }
@@ -169,7 +137,7 @@ __global__ __launch_bounds__(CRIT_THREADS) void cspn_criterion_backward_kernel(c
     for (size_t u = (size_t)blockIdx.x * CRIT_THREADS + threadIdx.x; u < nu; u += stride) {
         const size_t e0 = u * 4;
         float p[4], t[4], g[4];
-        load_unit(pred, target, u, n, vec, p, t);
+        load_unit(pred, target, u, n, vec, p, t, 1.f, 0.f);
 #pragma unroll
         for (int e = 0; e < 4; ++e) g[e] = criterion_grad<KIND>(p[e], t[e], scale);
         if (vec && e0 + 4 <= n) {
@@ -237,19 +205,17 @@ int cspn_criterion_backward(const void* pred, const void* target, int dtype, int
     if ((reinterpret_cast<uintptr_t>(grad_loss) | reinterpret_cast<uintptr_t>(grad_pred)) & 3)
         return fail("cspn_criterion_backward: grad_loss / grad_pred are not aligned to their element size");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t nu = (n + 3) / 4;
-    size_t grid = (nu + CRIT_THREADS - 1) / CRIT_THREADS;
-    if (grid > CRIT_BWD_MAX_GRID) grid = CRIT_BWD_MAX_GRID;
+    const unsigned grid = loss_backward_grid(n);
     const float* p = static_cast<const float*>(pred);
     const float* t = static_cast<const float*>(target);
     const CriterionState* s = static_cast<const CriterionState*>(state);
     float* g = static_cast<float*>(grad_pred);
     if (kind == CSPN_LOSS_L1)
-        hipLaunchKernelGGL((cspn_criterion_backward_kernel<CSPN_LOSS_L1>), dim3((unsigned)grid), dim3(CRIT_THREADS), 0, st, p, t, n, s, grad_loss, g);
+        hipLaunchKernelGGL((cspn_criterion_backward_kernel<CSPN_LOSS_L1>), dim3(grid), dim3(CRIT_THREADS), 0, st, p, t, n, s, grad_loss, g);
     else if (kind == CSPN_LOSS_L2)
-        hipLaunchKernelGGL((cspn_criterion_backward_kernel<CSPN_LOSS_L2>), dim3((unsigned)grid), dim3(CRIT_THREADS), 0, st, p, t, n, s, grad_loss, g);
+        hipLaunchKernelGGL((cspn_criterion_backward_kernel<CSPN_LOSS_L2>), dim3(grid), dim3(CRIT_THREADS), 0, st, p, t, n, s, grad_loss, g);
     else
-        hipLaunchKernelGGL((cspn_criterion_backward_kernel<CSPN_LOSS_L1_LOG>), dim3((unsigned)grid), dim3(CRIT_THREADS), 0, st, p, t, n, s, grad_loss, g);
+        hipLaunchKernelGGL((cspn_criterion_backward_kernel<CSPN_LOSS_L1_LOG>), dim3(grid), dim3(CRIT_THREADS), 0, st, p, t, n, s, grad_loss, g);
     HIP_OK(hipGetLastError());
     return 1;
 }

@@ -15,15 +15,16 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 SO_PATH = os.environ.get("CSPN_HIP_LIB") or os.path.join(_PKG, "libcspn_hip.so")   # env override: A/B builds
 CSRC = os.path.join(_PKG, "csrc")
-SOURCES = ("cspn_propagate.hip", "cspn_resident.hip", "cspnk_resident.hip", "cspnk_d2.hip", "cspn_prepare.hip", "cspn_backward.hip", "cspn_metrics.hip", "cspn_metrics_frame.hip", "cspn_debug.hip", "cspn_repair.hip", "pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_criterion.hip", "cspn_max8.hip", "cspn_abn.hip", "cspn_sparsify.hip", "cspn_transform.hip", "cspn_losses.hip", "cspn_optim.hip")   # one TU each
+SOURCES = ("cspn_propagate.hip", "cspn_resident.hip", "cspnk_resident.hip", "cspnk_d2.hip", "cspn_prepare.hip", "cspn_backward.hip", "cspn_metrics.hip", "cspn_metrics_frame.hip", "cspn_debug.hip", "cspn_repair.hip", "pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_criterion.hip", "cspn_max8.hip", "cspn_abn.hip", "cspn_sparsify.hip", "cspn_transform.hip", "cspn_losses.hip", "cspn_optim.hip", "cspn_visual.hip")   # one TU each
 HEADERS = (os.path.join(CSRC, "cspn_common.hpp"), os.path.join(CSRC, "cspnk_helpers.hpp"), os.path.join(_ROOT, "include", "cspn_hip.h"))
 INCLUDE = os.path.join(_ROOT, "include")
 # include/cspn_criterion.h, include/cspn_max8.h, include/cspn_abn.h, include/cspn_sparsify.h, include/cspn_transform.h, include/cspn_losses.h,
-# include/cspn_optim.h, csrc/pac_launch.hpp, csrc/cspn_loss_units.hpp: part of the build's staleness hash, NOT of code_digest() — no benchmarked
+# include/cspn_optim.h, include/cspn_visual.h, csrc/pac_launch.hpp, csrc/cspn_loss_units.hpp: part of the build's staleness hash, NOT of code_digest() — no benchmarked
 # kernel sees it, and a digest that moved would mark the HBM traffic recorded under profiles/ as stale (bench.py `traffic_stale`)
 BUILD_HEADERS = HEADERS + (os.path.join(INCLUDE, "cspn_criterion.h"), os.path.join(INCLUDE, "cspn_max8.h"), os.path.join(INCLUDE, "cspn_abn.h"),
                            os.path.join(INCLUDE, "cspn_sparsify.h"), os.path.join(INCLUDE, "cspn_transform.h"), os.path.join(CSRC, "pac_launch.hpp"),
-                           os.path.join(INCLUDE, "cspn_losses.h"), os.path.join(CSRC, "cspn_loss_units.hpp"), os.path.join(INCLUDE, "cspn_optim.h"))
+                           os.path.join(INCLUDE, "cspn_losses.h"), os.path.join(CSRC, "cspn_loss_units.hpp"), os.path.join(INCLUDE, "cspn_optim.h"),
+                           os.path.join(INCLUDE, "cspn_visual.h"))
 
 CSPN_F32, CSPN_F16 = 0, 1
 ABI_VERSION = 10         # CSPN_ABI_VERSION of include/cspn_hip.h this host code was written against
@@ -48,6 +49,9 @@ MEAN_L1, MEAN_GRAD, MEAN_RMSE, MEAN_RMSE_LOG = 0, 1, 2, 3   # the `kind` of cspn
 LOSSES_STATE_BYTES = 48
 OPTIM_ABI_VERSION = 1       # CSPN_OPTIM_ABI_VERSION of include/cspn_optim.h
 SGD_CHUNK, SGD_TENSORS_PER_LAUNCH, SGD_MAX_WORKGROUPS = 4096, 109, 2048
+VISUAL_ABI_VERSION = 1      # CSPN_VISUAL_ABI_VERSION of include/cspn_visual.h
+VISUAL_RANGE_CHUNK, VISUAL_MAX_PLANES = 4096, 3
+VISUAL_RGB_NONE, VISUAL_RGB_F32, VISUAL_RGB_U8 = 0, 1, 2      # cspn_visual_rows_t.rgb_kind
 BLEND_NONE, BLEND_SPARSE, BLEND_PREMASK = 0, 1, 2
 
 # every symbol include/cspn_hip.h declares (tests check the .so exports all of them)
@@ -77,6 +81,8 @@ LOSSES_EXPORTS = ("cspn_losses_abi_version", "cspn_losses_workspace_bytes", "csp
                   "cspn_mean_loss_forward", "cspn_mean_loss_backward")
 # every symbol include/cspn_optim.h declares
 OPTIM_EXPORTS = ("cspn_optim_abi_version", "cspn_sgd_plan", "cspn_sgd_step")
+# every symbol include/cspn_visual.h declares
+VISUAL_EXPORTS = ("cspn_visual_abi_version", "cspn_visual_workspace_bytes", "cspn_visual_rows", "cspn_visual_features")
 
 
 class cspn_plan(ctypes.Structure):
@@ -113,8 +119,15 @@ class cspn_sgd_hyper(ctypes.Structure):          # cspn_sgd_hyper_t (include/csp
                 ("weight_decay", ctypes.c_double), ("nesterov", ctypes.c_int), ("maximize", ctypes.c_int)]
 
 
+class cspn_visual_rows(ctypes.Structure):       # cspn_visual_rows_t (include/cspn_visual.h)
+    _fields_ = [("rgb", ctypes.c_void_p), ("rgb_kind", ctypes.c_int), ("rgb_scale", ctypes.c_float), ("rgb_frame_stride", ctypes.c_long),
+                ("rgb_channel_stride", ctypes.c_long), ("depth", ctypes.c_void_p * 3), ("depth_frame_stride", ctypes.c_long * 3),
+                ("n_depth", ctypes.c_int), ("use_min", ctypes.c_int), ("use_max", ctypes.c_int), ("d_min", ctypes.c_float),
+                ("d_max", ctypes.c_float)]
+
+
 BENCH_UNRELATED = ("pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_metrics_frame.hip", "cspn_criterion.hip", "cspn_max8.hip",
-                   "cspn_abn.hip", "cspn_sparsify.hip", "cspn_transform.hip", "cspn_losses.hip", "cspn_optim.hip")       # kernels no bench.py workload launches
+                   "cspn_abn.hip", "cspn_sparsify.hip", "cspn_transform.hip", "cspn_losses.hip", "cspn_optim.hip", "cspn_visual.hip")       # kernels no bench.py workload launches
 
 
 def _source_digest(flags, code_only=False):
@@ -312,6 +325,13 @@ def _declare(lib):
     lib.cspn_sgd_plan.restype = ci
     lib.cspn_sgd_step.argtypes = [ctypes.POINTER(cspn_sgd_tensor), ci, ctypes.POINTER(cspn_sgd_hyper), ci, ci, vp]
     lib.cspn_sgd_step.restype = ci
+    lib.cspn_visual_abi_version.restype = ci
+    lib.cspn_visual_workspace_bytes.argtypes = [ci, ci, cs]
+    lib.cspn_visual_workspace_bytes.restype = cs
+    lib.cspn_visual_rows.argtypes = [ctypes.POINTER(cspn_visual_rows), ci, ci, ci, vp, cs, vp, vp]
+    lib.cspn_visual_rows.restype = ci
+    lib.cspn_visual_features.argtypes = [vp, cl, ci, ci, ci, ci, ci, vp, cs, vp, vp]
+    lib.cspn_visual_features.restype = ci
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("cspn_last_error", "cspn_propagate_workspace_bytes", "cspn3_resident_workspace_bytes",
@@ -347,6 +367,8 @@ def lib():
                     raise RuntimeError("cspn_monodepth_amd: losses ABI version mismatch")
                 if _lib.cspn_optim_abi_version() != OPTIM_ABI_VERSION:
                     raise RuntimeError("cspn_monodepth_amd: optim ABI version mismatch")
+                if _lib.cspn_visual_abi_version() != VISUAL_ABI_VERSION:
+                    raise RuntimeError("cspn_monodepth_amd: visual ABI version mismatch")
                 poison = os.environ.get("CSPN_DEBUG_LDS_POISON", "")      # debugging aid (include/cspn_hip.h): "nan" or a hex word
                 if poison and poison != "0":
                     _lib.cspn_debug_set_lds_poison(1, 0x7fc00000 if poison in ("1", "nan") else int(poison, 16), None)

@@ -9,6 +9,7 @@ host synchronisation per batch and one `average()` at the end.
     python examples/eval_loop.py --frames 96 --compare-host-meter        # the old way: batch 1, metric_sums + a .cpu() per frame
     python examples/eval_loop.py --batch 24 --frames 96 --graph --sparsifier device   # the reference's sampler inside the replay
     python examples/eval_loop.py --batch 24 --frames 96 --graph --transform device    # ... from RAW 480 x 640 frames: val_transform too
+    python examples/eval_loop.py --batch 8 --frames 96 --graph --comparison sheet.png # ... and the reference's comparison sheet
 
 Synthetic data (device RNG, one seed per frame, so a frame does not depend on the batch it is generated in; SURVEY.md §8d
 value distributions): `prior` = a dense depth U(0.5, 10); input = RGB U(0, 1) + sparse samples of `prior` (500 per frame);
@@ -23,6 +24,11 @@ depends on (--seed, frame index) only, not on the batch size.  --transform devic
 Resize(240 / 480), CenterCrop to --height x --width) runs inside the step and inside the captured replay, in front of the device
 sampler, which it implies; target goes through the same geometry as `prior`.  The numbers say nothing about depth estimation — they exercise
 the protocol, and tests/test_eval_protocol.py checks them against a per-frame fp64 evaluation of the dumped tensors.
+
+--comparison FILE draws the sheet trainer.eval saves (libs/trainers/single_gpu_trainer.py:140-175): frame 0 of the batches 0, skip, ..,
+7 * skip with skip = batches // 9 (at least 1), each as one merge_into_row_with_gt row — RGB, sparse input, target, prediction —
+written by cspn_monodepth_amd.utils.ComparisonSheet straight into one device buffer, two launches per row and no host
+synchronisation; the file is written after the loop, from the sheet's only copy to the host.  The printed line does not change.
 
 Prints one JSON line: the ten averages, `count` (frames) and `seconds_per_frame` (whole loop, model included, wall clock
 between two device synchronisations — a whole-model figure dominated by the stock convolutions).
@@ -85,6 +91,9 @@ def main():
     ap.add_argument("--transform", choices=("none", "device"), default="none",
                     help="none: the frames are made at --height x --width; device: raw 480 x 640 uint8 + depth frames, the reference's "
                          "val_transform on the device inside every step (include/cspn_transform.h); implies --sparsifier device")
+    ap.add_argument("--comparison", metavar="FILE",
+                    help="save the reference's comparison sheet there: 8 rows of RGB | sparse input | target | prediction, drawn on the device "
+                         "(include/cspn_visual.h) without a host synchronisation")
     a = ap.parse_args()
     if a.compare_host_meter:
         a.batch, a.graph = 1, False
@@ -100,6 +109,11 @@ def main():
     ids = (torch.arange(a.frames, dtype=torch.int64, device=dev),) if a.sparsifier == "device" else ()
     meter = ev.FrameAverageMeter(dev)
     host_meter = ev.BatchAverageMeter()
+    sheet, drawn = None, {}
+    if a.comparison:
+        from cspn_monodepth_amd.utils import ComparisonSheet
+        sheet = ComparisonSheet(8, "rgbd")
+        skip = max(-(-a.frames // a.batch) // 9, 1)
 
     def predict(xb, pb):
         return (pb + net(xb)[0]).clamp_(min=0.1)                           # the plain forward: device-guarded, safe to score unsynchronised
@@ -116,12 +130,14 @@ def main():
         xb, pb, tb = prepare(xb, pb, tb, *ib)
         pred = predict(xb, pb)
         meter.update(pred, tb)
+        drawn["eager"] = (xb, tb)                                          # what the network saw: under capture, the replay's own tensors
         return pred
 
     nb = min(a.batch, a.frames)
     with torch.no_grad():
         step(x[:nb], prior[:nb], target[:nb], *(i[:nb] for i in ids))      # warm-up: kernel selection of the convolutions, meter buffers
         graphed = GraphedForward(step, x[:nb], prior[:nb], target[:nb], *(i[:nb] for i in ids)) if a.graph else None
+        drawn["graph"] = drawn["eager"]                                    # the captured step's tensors: every replay refills them
         meter.reset()
         preds = []
         torch.cuda.synchronize(dev)
@@ -137,10 +153,18 @@ def main():
                 pred = graphed(xb, pb, tb, *ib)
             else:                                                          # eager (and the ragged last batch of a --graph run)
                 pred = step(xb, pb, tb, *ib)
+            if sheet is not None and not sheet.full and (lo // a.batch) % skip == 0:
+                if a.compare_host_meter:
+                    xin, tin = xb, tb
+                else:
+                    xin, tin = drawn["graph" if graphed is not None and hi - lo == nb else "eager"]
+                sheet.add(xin[0], tin[0], pred[0])
             if a.dump:
                 preds.append(pred.clone())
         torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0
+    if sheet is not None:
+        sheet.save(a.comparison)
     res = host_meter.average() if a.compare_host_meter else meter.average()
     if a.dump:
         os.makedirs(a.dump, exist_ok=True)

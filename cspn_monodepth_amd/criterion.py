@@ -31,7 +31,7 @@ KINDS = {"l1": _lib.LOSS_L1, "l2": _lib.LOSS_L2, "l1_log": _lib.LOSS_L1_LOG}
 MEAN_KINDS = {"l1": _lib.MEAN_L1, "grad": _lib.MEAN_GRAD, "rmse": _lib.MEAN_RMSE, "rmse_log": _lib.MEAN_RMSE_LOG}
 STATE_BYTES = 32     # CSPN_CRITERION_STATE_BYTES: float loss, float 1 / count, double sum, double count, 8 reserved
 
-_FP32_ONLY = ("masked_loss: fp32 only, got %s — the gradient of a mean over ~1e6 pixels (g / count) is below the smallest fp16 "
+_FP32_ONLY = ("%s: fp32 only, got %s — the gradient of a mean over ~1e6 pixels (g / count) is below the smallest fp16 "
               "subnormal; cast the prediction with .float() first")
 
 
@@ -44,36 +44,70 @@ def criterion_workspace(n, device):
             torch.empty((STATE_BYTES // 4,), dtype=torch.float32, device=device))
 
 
-class _MaskedLoss(torch.autograd.Function):
+def losses_workspace(n, device):
+    """(work, state) of one forward of include/cspn_losses.h over n elements; fresh on every call, as criterion_workspace."""
+    nbytes = _lib.lib().cspn_losses_workspace_bytes(int(n))
+    return (torch.empty((nbytes // 8,), dtype=torch.float64, device=device),
+            torch.empty((_lib.LOSSES_STATE_BYTES // 4,), dtype=torch.float32, device=device))
+
+
+# family -> (forward entry, backward entry, workspace function, whether the entries take a `kind`)
+_FAMILIES = {"masked": ("cspn_criterion_forward", "cspn_criterion_backward", criterion_workspace, True),
+             "berhu": ("cspn_berhu_forward", "cspn_berhu_backward", losses_workspace, False),
+             "mean": ("cspn_mean_loss_forward", "cspn_mean_loss_backward", losses_workspace, True)}
+
+
+class _Loss(torch.autograd.Function):
+    """One loss of a family of _FAMILIES over (a, b) = (pred, target) / (fake, real), with a gradient for `a` only."""
+
     @staticmethod
-    def forward(ctx, pred, target, kind):
-        n = pred.numel()
-        work, state = criterion_workspace(n, pred.device)
-        with torch.cuda.device(pred.device):
-            ok = _lib.lib().cspn_criterion_forward(pred.data_ptr(), target.data_ptr(), _lib.CSPN_F32, kind, n, work.data_ptr(),
-                                                   state.data_ptr(), torch.cuda.current_stream(pred.device).cuda_stream)
-        _lib.check(ok, "cspn_criterion_forward")
-        ctx.save_for_backward(pred, target)
-        ctx.state, ctx.kind = state, kind
+    def forward(ctx, a, b, family, kind):
+        entry, _, workspace, has_kind = _FAMILIES[family]
+        n = a.numel()
+        work, state = workspace(n, a.device)
+        with torch.cuda.device(a.device):
+            ok = getattr(_lib.lib(), entry)(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, *((kind,) if has_kind else ()), n, work.data_ptr(),
+                                            state.data_ptr(), torch.cuda.current_stream(a.device).cuda_stream)
+        _lib.check(ok, entry)
+        ctx.save_for_backward(a, b)
+        ctx.state, ctx.family, ctx.kind = state, family, kind
         return state[0]                                  # 0-dim view of the state's first word: no copy, no launch
 
     @staticmethod
     @torch.autograd.function.once_differentiable         # double backward raises
     def backward(ctx, grad_loss):
-        pred, target = ctx.saved_tensors
+        a, b = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
-            return None, None, None
+            return None, None, None, None
+        _, entry, _, has_kind = _FAMILIES[ctx.family]
         g = grad_loss
-        if g.dtype != torch.float32 or g.device != pred.device:
-            g = g.to(device=pred.device, dtype=torch.float32)
+        if g.dtype != torch.float32 or g.device != a.device:
+            g = g.to(device=a.device, dtype=torch.float32)
         g = g.contiguous()
-        grad = torch.empty_like(pred, memory_format=torch.contiguous_format)
-        with torch.cuda.device(pred.device):
-            ok = _lib.lib().cspn_criterion_backward(pred.data_ptr(), target.data_ptr(), _lib.CSPN_F32, ctx.kind, pred.numel(),
-                                                    ctx.state.data_ptr(), g.data_ptr(), grad.data_ptr(),
-                                                    torch.cuda.current_stream(pred.device).cuda_stream)
-        _lib.check(ok, "cspn_criterion_backward")
-        return grad, None, None
+        grad = torch.empty_like(a, memory_format=torch.contiguous_format)
+        with torch.cuda.device(a.device):
+            ok = getattr(_lib.lib(), entry)(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, *((ctx.kind,) if has_kind else ()), a.numel(),
+                                            ctx.state.data_ptr(), g.data_ptr(), grad.data_ptr(),
+                                            torch.cuda.current_stream(a.device).cuda_stream)
+        _lib.check(ok, entry)
+        return grad, None, None, None
+
+
+def _apply(who, family, a, b, kind=None):
+    """The one validation of every loss here, then the launches: fp32 `a`, equal shapes and devices, at least one element, a ROCm
+    device; `b` is detached and cast to fp32, both are made contiguous."""
+    if a.dtype != torch.float32:
+        raise TypeError(_FP32_ONLY % (who, a.dtype))
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("%s: both tensors must have the same shape and device, got %s and %s" % (who, tuple(a.shape), tuple(b.shape)))
+    if a.numel() < 1:
+        raise ValueError("%s: empty tensors" % who)
+    if not (a.is_cuda and b.is_cuda):
+        raise RuntimeError("%s: tensors must live on a ROCm device (no CPU implementation here)" % who)
+    b = b.detach()
+    if b.dtype != torch.float32:
+        b = b.float()
+    return _Loss.apply(a.contiguous(), b.contiguous(), family, kind)
 
 
 def masked_loss(pred, target, kind):
@@ -81,18 +115,7 @@ def masked_loss(pred, target, kind):
     a gradient for `pred` only.  No valid pixel: NaN, and a zero gradient, as the reference gives."""
     if kind not in KINDS:
         raise NotImplementedError("masked_loss: no criterion named %r (l1, l2, l1_log)" % (kind,))
-    if pred.dtype != torch.float32:
-        raise TypeError(_FP32_ONLY % (pred.dtype,))
-    if not (pred.is_cuda and target.is_cuda):
-        raise RuntimeError("masked_loss: tensors must live on a ROCm device (no CPU implementation here)")
-    if pred.shape != target.shape or pred.device != target.device:
-        raise ValueError("pred / target must have the same shape and device, got %s and %s" % (tuple(pred.shape), tuple(target.shape)))
-    if pred.numel() < 1:
-        raise ValueError("masked_loss: empty tensors")
-    target = target.detach()
-    if target.dtype != torch.float32:
-        target = target.float()
-    return _MaskedLoss.apply(pred.contiguous(), target.contiguous(), KINDS[kind])
+    return _apply("masked_loss", "masked", pred, target, KINDS[kind])
 
 
 def _resized(pred, target):
@@ -154,74 +177,11 @@ class CriterionDSN(_Wrapper):
         return self._one(preds[0], target) + 0.4 * self._one(preds[1], target)
 
 
-class _Loss(torch.autograd.Function):
-    """berHu (kind None) or one unmasked mean of include/cspn_losses.h over (a, b) = (pred, target) / (fake, real)."""
-
-    @staticmethod
-    def forward(ctx, a, b, kind):
-        n = a.numel()
-        work, state = losses_workspace(n, a.device)
-        L, st = _lib.lib(), torch.cuda.current_stream(a.device).cuda_stream
-        with torch.cuda.device(a.device):
-            if kind is None:
-                ok = L.cspn_berhu_forward(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, n, work.data_ptr(), state.data_ptr(), st)
-            else:
-                ok = L.cspn_mean_loss_forward(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, kind, n, work.data_ptr(), state.data_ptr(), st)
-        _lib.check(ok, "cspn_berhu_forward" if kind is None else "cspn_mean_loss_forward")
-        ctx.save_for_backward(a, b)
-        ctx.state, ctx.kind = state, kind
-        return state[0]                                  # 0-dim view of the state's first word: no copy, no launch
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable         # double backward raises
-    def backward(ctx, grad_loss):
-        a, b = ctx.saved_tensors
-        if not ctx.needs_input_grad[0]:
-            return None, None, None
-        g = grad_loss
-        if g.dtype != torch.float32 or g.device != a.device:
-            g = g.to(device=a.device, dtype=torch.float32)
-        g = g.contiguous()
-        grad = torch.empty_like(a, memory_format=torch.contiguous_format)
-        L, st = _lib.lib(), torch.cuda.current_stream(a.device).cuda_stream
-        with torch.cuda.device(a.device):
-            if ctx.kind is None:
-                ok = L.cspn_berhu_backward(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, a.numel(), ctx.state.data_ptr(), g.data_ptr(),
-                                           grad.data_ptr(), st)
-            else:
-                ok = L.cspn_mean_loss_backward(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, ctx.kind, a.numel(), ctx.state.data_ptr(),
-                                               g.data_ptr(), grad.data_ptr(), st)
-        _lib.check(ok, "cspn_berhu_backward" if ctx.kind is None else "cspn_mean_loss_backward")
-        return grad, None, None
-
-
-def losses_workspace(n, device):
-    """(work, state) of one forward of include/cspn_losses.h over n elements; fresh on every call, as criterion_workspace."""
-    nbytes = _lib.lib().cspn_losses_workspace_bytes(int(n))
-    return (torch.empty((nbytes // 8,), dtype=torch.float64, device=device),
-            torch.empty((_lib.LOSSES_STATE_BYTES // 4,), dtype=torch.float32, device=device))
-
-
-def _checked(who, a, b):
-    if a.dtype != torch.float32:
-        raise TypeError(_FP32_ONLY.replace("masked_loss", who) % (a.dtype,))
-    if a.shape != b.shape or a.device != b.device:
-        raise ValueError("%s: both tensors must have the same shape and device, got %s and %s" % (who, tuple(a.shape), tuple(b.shape)))
-    if a.numel() < 1:
-        raise ValueError("%s: empty tensors" % who)
-    if not (a.is_cuda and b.is_cuda):
-        raise RuntimeError("%s: tensors must live on a ROCm device (no CPU implementation here)" % who)
-    b = b.detach()
-    if b.dtype != torch.float32:
-        b = b.float()
-    return a.contiguous(), b.contiguous()
-
-
 def berhu_loss(pred, target):
     """The reverse Huber loss of criteria.py:42-64: c = 0.2 * max(pred - target) over ALL pixels, d = |target - pred| over
     target > 0, mean of the d and of the d^2 of those with d > c — a 0-dim fp32 device tensor with a gradient for `pred` only
     (c enters a comparison only).  No valid pixel: NaN, and a zero gradient.  Inputs as masked_loss takes them."""
-    return _Loss.apply(*_checked("berhu_loss", pred, target), None)
+    return _apply("berhu_loss", "berhu", pred, target)
 
 
 def unmasked_loss(fake, real, kind):
@@ -229,7 +189,7 @@ def unmasked_loss(fake, real, kind):
     sqrt(mean (log r - log f)^2) — a 0-dim fp32 device tensor with a gradient for `fake` only."""
     if kind not in MEAN_KINDS:
         raise NotImplementedError("unmasked_loss: no criterion named %r (%s)" % (kind, ", ".join(MEAN_KINDS)))
-    return _Loss.apply(*_checked("unmasked_loss", fake, real), MEAN_KINDS[kind])
+    return _apply("unmasked_loss", "mean", fake, real, MEAN_KINDS[kind])
 
 
 class berHuLoss(nn.Module):

@@ -1,8 +1,9 @@
 // cspn_losses.hip — the reference's berHuLoss (libs/criterion/criteria.py:42-64) and its unmasked means L1, GradLoss, RMSE and
 // RMSE_log (:79-88, :145-152, :133-142, :67-76), forward and backward, as kernels without atomics (include/cspn_losses.h).
 //
-// The sums follow the slice discipline of cspn_loss_units.hpp, shared with cspn_criterion.hip.  berHu needs max(pred - target)
-// in front of its second sum:
+// Every pass, sum, streaming backward and argument check is the core of cspn_loss_units.hpp, where the determinism contract is
+// written out; this file holds the TERM / GRAD structs, the state and berHu's maximum.  berHu needs max(pred - target) in front
+// of its second sum:
 //   launch 1, grid S: work[s] = {sum_valid d, n_valid, -, -, max e} of slice s;
 //   launch 2, grid S: every workgroup reduces the S <= 1024 slice maxima itself, c = 0.2f * m, then adds {sum_huber d^2, n_huber}
 //                     over the SAME units its slice had in launch 1 (a second read of both planes);
@@ -39,76 +40,6 @@ __device__ __forceinline__ float max_of_slices(const double* __restrict__ work, 
     float m = -INFINITY;
     for (int s = threadIdx.x; s < S; s += CRIT_THREADS) m = nanmax(m, (float)work[(size_t)s * LOSS_WORK + 4]);
     return block_nanmax(m, wave_max);
-}
-
-// Quantity k of the S <= 1024 slices, added by one wavefront: lane l adds slices l, l + 64, ... in increasing order, the lanes go
-// through wave_sum_to_lane63 (valid in lane 63).  All of a lane's loads are issued before its first add — the slices were written
-// by other workgroups, so each load is a trip past the L2, and sixteen of them one after the other were the launch's whole time;
-// a slice past S adds +0.0, which changes no bit.
-__device__ __forceinline__ double wave_sum_of_slices(const double* __restrict__ work, int S, int k, int lane) {
-    constexpr int PER_LANE = CRIT_MAX_SLICES / 64;
-    double part[PER_LANE];
-#pragma unroll
-    for (int j = 0; j < PER_LANE; ++j) {
-        const int s = lane + 64 * j;
-        part[j] = s < S ? work[(size_t)s * LOSS_WORK + k] : 0.0;
-    }
-    double v = 0.0;
-#pragma unroll
-    for (int j = 0; j < PER_LANE; ++j) v += part[j];
-    return wave_sum_to_lane63(v);
-}
-
-// the workgroup's sums of K per-thread fp64 partials -> work[s * LOSS_WORK + slot0 + k]: wave_sum_to_lane63, then the 4
-// wavefronts in wavefront order
-template <int K>
-__device__ __forceinline__ void block_sums_to_work(const double (&acc)[K], double (&part)[CRIT_THREADS / 64][K], double* __restrict__ out) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double v = wave_sum_to_lane63(acc[k]);
-        if (lane == 63) part[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double v = part[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < CRIT_THREADS / 64; ++w) v += part[w][threadIdx.x];
-        out[threadIdx.x] = v;
-    }
-}
-
-// One trip structure for every sliced pass: TERM::add(a, b, fs, fc) is called for the 16 pixels of a group with fp32 partials,
-// which then go to fp64.  Past the end of the planes a pixel is (TERM::pad_a, TERM::pad_b), which adds nothing.
-template <class TERM>
-__device__ __forceinline__ void slice_pass(const float* __restrict__ a, const float* __restrict__ b, size_t n, TERM& term,
-                                           double (&acc)[2]) {
-    const int S = gridDim.x, s = blockIdx.x;
-    const bool vec = (((uintptr_t)a | (uintptr_t)b) & 15) == 0;              // workgroup-uniform
-    const size_t nu = (n + 3) / 4;                                           // the last unit may be partial
-    const size_t stride = (size_t)S * CRIT_THREADS;
-    acc[0] = 0.0;
-    acc[1] = 0.0;
-    for (size_t u0 = (size_t)s * CRIT_THREADS + threadIdx.x; u0 < nu; u0 += CRIT_GROUP * stride) {
-        float va[CRIT_GROUP][4], vb[CRIT_GROUP][4];
-#pragma unroll
-        for (int j = 0; j < CRIT_GROUP; ++j) {
-            const size_t u = u0 + (size_t)j * stride;
-            if (u < nu) {
-                load_unit(a, b, u, n, vec, va[j], vb[j], TERM::pad_a(), TERM::pad_b());
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { va[j][e] = TERM::pad_a(); vb[j][e] = TERM::pad_b(); }
-            }
-        }
-        float fs = 0.f, fc = 0.f;
-#pragma unroll
-        for (int j = 0; j < CRIT_GROUP; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) term.add(va[j][e], vb[j][e], fs, fc);
-        acc[0] += (double)fs;
-        acc[1] += (double)fc;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ berHu
@@ -167,7 +98,7 @@ __global__ __launch_bounds__(CRIT_THREADS) void cspn_berhu_combine_kernel(const 
     __shared__ float wave_max[CRIT_THREADS / 64];
     const float c = BERHU_RATIO * max_of_slices(work, S, wave_max);
     const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const double v = wave_sum_of_slices(work, S, k, lane);
+    const double v = wave_sum_of_slices<LOSS_WORK>(work, S, k, lane);
     if (lane == 63) tot[k] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -221,7 +152,7 @@ __global__ __launch_bounds__(CRIT_THREADS) void cspn_mean_slice_kernel(const flo
 // One wavefront adds the S slices; lane 63 writes the state.
 __global__ __launch_bounds__(64) void cspn_mean_combine_kernel(const double* __restrict__ work, int S, int kind, double n,
                                                                LossState* __restrict__ state) {
-    const double v = wave_sum_of_slices(work, S, 0, threadIdx.x);
+    const double v = wave_sum_of_slices<LOSS_WORK>(work, S, 0, threadIdx.x);
     if (threadIdx.x == 63) {
         const double mean = v / n;
         const bool root = kind == CSPN_MEAN_RMSE || kind == CSPN_MEAN_RMSE_LOG;
@@ -261,29 +192,6 @@ struct MeanGrad {
     }
 };
 
-// grid-stride over units, one unit (16 bytes of each plane) per thread and trip; GRAD is built from the state on the device
-template <class GRAD>
-__device__ __forceinline__ void stream_grad(const float* __restrict__ a, const float* __restrict__ b, size_t n, const GRAD& grad,
-                                            float* __restrict__ out) {
-    const bool vec = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0;
-    const size_t nu = (n + 3) / 4;
-    const size_t stride = (size_t)gridDim.x * CRIT_THREADS;
-    for (size_t u = (size_t)blockIdx.x * CRIT_THREADS + threadIdx.x; u < nu; u += stride) {
-        const size_t e0 = u * 4;
-        float va[4], vb[4], g[4];
-        load_unit(a, b, u, n, vec, va, vb, 1.f, 1.f);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) g[e] = grad(va[e], vb[e]);
-        if (vec && e0 + 4 <= n) {
-            st4(out + e0, make_float4(g[0], g[1], g[2], g[3]));
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e0 + e < n) st1(out + e0 + e, g[e]);
-        }
-    }
-}
-
 __global__ __launch_bounds__(CRIT_THREADS) void cspn_berhu_backward_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                                            size_t n, const LossState* __restrict__ state,
                                                                            const float* __restrict__ grad_loss, float* __restrict__ grad_pred) {
@@ -300,32 +208,6 @@ __global__ __launch_bounds__(CRIT_THREADS) void cspn_mean_backward_kernel(const 
     MeanGrad<KIND> grad;
     grad.scale = *grad_loss * state->factor;
     stream_grad(fake, real, n, grad, grad_fake);
-}
-
-int check_planes(const char* who, const void* a, const void* b, int dtype, size_t n) {
-    if (!a || !b) return fail("%s: null input plane", who);
-    if (n < 1) return fail("%s: n must be at least 1", who);
-    if (dtype != CSPN_F32)
-        return fail("%s: unsupported dtype %d, fp32 only: the gradient of a mean over ~1e6 pixels is below what fp16 can hold "
-                    "(include/cspn_criterion.h)", who, dtype);
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3)
-        return fail("%s: the input planes are not aligned to their element size", who);
-    return 1;
-}
-
-int check_forward(const char* who, const void* work, const void* state) {
-    if (!work || !state) return fail("%s: null work / state", who);
-    if (reinterpret_cast<uintptr_t>(work) & 7 || reinterpret_cast<uintptr_t>(state) & 7)
-        return fail("%s: work / state must be 8-byte aligned", who);
-    return 1;
-}
-
-int check_backward(const char* who, const void* state, const float* grad_loss, const void* grad) {
-    if (!state || !grad_loss || !grad) return fail("%s: null state / grad_loss / gradient plane", who);
-    if (reinterpret_cast<uintptr_t>(state) & 7) return fail("%s: state must be 8-byte aligned", who);
-    if ((reinterpret_cast<uintptr_t>(grad_loss) | reinterpret_cast<uintptr_t>(grad)) & 3)
-        return fail("%s: grad_loss / the gradient plane are not aligned to their element size", who);
-    return 1;
 }
 
 bool mean_kind_ok(int kind) { return kind >= CSPN_MEAN_L1 && kind <= CSPN_MEAN_RMSE_LOG; }

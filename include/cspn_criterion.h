@@ -24,7 +24,8 @@
  *   - unit u belongs to slice (u / 256) % S, thread u % 256; a thread adds its units in increasing u, fp32 over a group of 4
  *     units (16 pixels), groups into fp64; the 64 lanes of a wavefront and the 4 wavefronts of a slice are added in a fixed order;
  *   - cspn_criterion_forward's second launch adds the S slices in an order that depends on S only.
- * The backward is element-wise.
+ * The backward is element-wise.  The one implementation of this order, for this header and for cspn_losses.h, is
+ * csrc/cspn_loss_units.hpp.
  */
 #ifndef CSPN_CRITERION_H_
 #define CSPN_CRITERION_H_

@@ -16,7 +16,8 @@
  * mean, and g / n is below what fp16 can hold (cspn_criterion.h).
  *
  * Determinism contract: the state is a function of the n values of both planes, the loss and n only.  Sums follow the slice
- * discipline of cspn_criterion.h (units of 16 bytes, unit u -> slice (u / 256) % S, fp32 over 16 pixels, then fp64, fixed orders).
+ * discipline of cspn_criterion.h (units of 16 bytes, unit u -> slice (u / 256) % S, fp32 over 16 pixels, then fp64, fixed orders),
+ * through the same code: csrc/cspn_loss_units.hpp.
  * berHu's maximum is combined with a NaN-propagating maximum, whose result does not depend on an order.
  *
  * berHu, every operation in fp32 as written:

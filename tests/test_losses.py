@@ -133,9 +133,19 @@ def test_losses_sources_stay_out_of_the_benchmark_digest():
         lines = (re.sub(rb"//.*$", b"", ln).strip() for ln in data.splitlines())
         h.update(b"\n".join(re.sub(rb"\s+", b" ", ln) for ln in lines if ln))
     assert _lib.code_digest() == h.hexdigest()
-    # one copy of the slice discipline: the criterion's translation unit takes it from the shared header
-    crit_src = open(os.path.join(_lib.CSRC, "cspn_criterion.hip")).read()
-    assert '#include "cspn_loss_units.hpp"' in crit_src and "inline int criterion_slices" not in crit_src
+    # one copy of the slice discipline: both translation units take the cut, the passes, both stages of the sums, the streaming
+    # backward and the checks from the shared header, and hold no loop over units or slices of their own
+    core = open(os.path.join(_lib.CSRC, "cspn_loss_units.hpp")).read()
+    shared = ("criterion_slices", "load_unit", "slice_pass", "block_sums_to_work", "wave_sum_of_slices", "loss_backward_grid", "stream_grad",
+              "check_planes", "check_forward", "check_backward")
+    defined = r"\b(?:void|int|double|unsigned) (%s)\(" % "|".join(shared)
+    assert sorted(re.findall(defined, core)) == sorted(shared)
+    for tu in ("cspn_criterion.hip", "cspn_losses.hip"):
+        code = re.sub(r"//.*$", "", open(os.path.join(_lib.CSRC, tu)).read(), flags=re.M)
+        assert '#include "cspn_loss_units.hpp"' in code and not re.findall(defined, code)
+        assert "load_unit" not in code and "wave_sum_to_lane63" not in code
+        loops = re.findall(r"\bfor \(([^;]*);", code)                      # berHu's maximum over lanes and over slice maxima, nothing else
+        assert loops == ([] if tu == "cspn_criterion.hip" else ["int off = 32", "int s = threadIdx.x"]), (tu, loops)
 
 
 def test_workspace_bytes_are_a_function_of_n():

@@ -5,6 +5,7 @@ _ext/__init__.py:2-13 — removed from PyTorch 1.0); here it is a plain ``ctypes
 There is NO fallback: if the library is missing or a call fails, a RuntimeError is raised
 (the reference's ``_check`` does the same, inplace_abn/functions.py:13-16).
 """
+import collections
 import ctypes
 import os
 import shutil
@@ -15,74 +16,27 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 SO_PATH = os.environ.get("CSPN_HIP_LIB") or os.path.join(_PKG, "libcspn_hip.so")   # env override: A/B builds
 CSRC = os.path.join(_PKG, "csrc")
-SOURCES = ("cspn_propagate.hip", "cspn_resident.hip", "cspnk_resident.hip", "cspnk_d2.hip", "cspn_prepare.hip", "cspn_backward.hip", "cspn_metrics.hip", "cspn_metrics_frame.hip", "cspn_debug.hip", "cspn_repair.hip", "pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_criterion.hip", "cspn_max8.hip", "cspn_abn.hip", "cspn_sparsify.hip", "cspn_transform.hip", "cspn_losses.hip", "cspn_optim.hip", "cspn_visual.hip")   # one TU each
-HEADERS = (os.path.join(CSRC, "cspn_common.hpp"), os.path.join(CSRC, "cspnk_helpers.hpp"), os.path.join(_ROOT, "include", "cspn_hip.h"))
 INCLUDE = os.path.join(_ROOT, "include")
-# include/cspn_criterion.h, include/cspn_max8.h, include/cspn_abn.h, include/cspn_sparsify.h, include/cspn_transform.h, include/cspn_losses.h,
-# include/cspn_optim.h, include/cspn_visual.h, csrc/pac_launch.hpp, csrc/cspn_loss_units.hpp: part of the build's staleness hash, NOT of code_digest() — no benchmarked
-# kernel sees it, and a digest that moved would mark the HBM traffic recorded under profiles/ as stale (bench.py `traffic_stale`)
-BUILD_HEADERS = HEADERS + (os.path.join(INCLUDE, "cspn_criterion.h"), os.path.join(INCLUDE, "cspn_max8.h"), os.path.join(INCLUDE, "cspn_abn.h"),
-                           os.path.join(INCLUDE, "cspn_sparsify.h"), os.path.join(INCLUDE, "cspn_transform.h"), os.path.join(CSRC, "pac_launch.hpp"),
-                           os.path.join(INCLUDE, "cspn_losses.h"), os.path.join(CSRC, "cspn_loss_units.hpp"), os.path.join(INCLUDE, "cspn_optim.h"),
-                           os.path.join(INCLUDE, "cspn_visual.h"))
 
 CSPN_F32, CSPN_F16 = 0, 1
 ABI_VERSION = 10         # CSPN_ABI_VERSION of include/cspn_hip.h this host code was written against
-CRITERION_ABI_VERSION = 1   # CSPN_CRITERION_ABI_VERSION of include/cspn_criterion.h
-MAX8_ABI_VERSION = 1        # CSPN_MAX8_ABI_VERSION of include/cspn_max8.h
 MAX8_MAX_STEPS_PER_LAUNCH = 16
-ABN_ABI_VERSION = 1         # CSPN_ABN_ABI_VERSION of include/cspn_abn.h
 ABN_ACT_LEAKY_RELU, ABN_ACT_ELU, ABN_ACT_NONE = 0, 1, 2
 ABN_SMALL, ABN_SPLIT = 0, 1                                 # cspn_abn_plan_t.regime
 ABN_FULL, ABN_STATS_ONLY, ABN_APPLY_ONLY = 0, 1, 2          # the `phase` of a training-mode cspn_abn_forward
-SPARSIFY_ABI_VERSION = 1    # CSPN_SPARSIFY_ABI_VERSION of include/cspn_sparsify.h
 SPARSIFY_UAR, SPARSIFY_DENSE = 0, 1                         # cspn_sparsify's `mode`
 UNIFORM_PHILOX, UNIFORM_F32, UNIFORM_F64 = 0, 1, 2          # ... `uniform_kind`
 RGB_NONE, RGB_F32, RGB_U8 = 0, 1, 2                         # ... `rgb_kind`
 SPARSIFY_SLICE_PIXELS, SPARSIFY_MAX_SLICES = 1024, 64
-TRANSFORM_ABI_VERSION = 1   # CSPN_TRANSFORM_ABI_VERSION of include/cspn_transform.h
 TRANSFORM_VAL, TRANSFORM_TRAIN = 0, 1                       # cspn_transform's `mode`
 TRANSFORM_PARAMS, TRANSFORM_GATHER_PIXELS, TRANSFORM_MAX_SECOND = 8, 256, 32768
 LOSS_L1, LOSS_L2, LOSS_L1_LOG = 0, 1, 2
-LOSSES_ABI_VERSION = 1      # CSPN_LOSSES_ABI_VERSION of include/cspn_losses.h
 MEAN_L1, MEAN_GRAD, MEAN_RMSE, MEAN_RMSE_LOG = 0, 1, 2, 3   # the `kind` of cspn_mean_loss_*
 LOSSES_STATE_BYTES = 48
-OPTIM_ABI_VERSION = 1       # CSPN_OPTIM_ABI_VERSION of include/cspn_optim.h
 SGD_CHUNK, SGD_TENSORS_PER_LAUNCH, SGD_MAX_WORKGROUPS = 4096, 109, 2048
-VISUAL_ABI_VERSION = 1      # CSPN_VISUAL_ABI_VERSION of include/cspn_visual.h
 VISUAL_RANGE_CHUNK, VISUAL_MAX_PLANES = 4096, 3
 VISUAL_RGB_NONE, VISUAL_RGB_F32, VISUAL_RGB_U8 = 0, 1, 2      # cspn_visual_rows_t.rgb_kind
 BLEND_NONE, BLEND_SPARSE, BLEND_PREMASK = 0, 1, 2
-
-# every symbol include/cspn_hip.h declares (tests check the .so exports all of them)
-EXPORTS = (
-    "cspn_abi_version", "cspn_last_error", "cspn_plan_resolve", "cspn3_prepare", "cspn_pac_prepare",
-    "cspn_propagate_workspace_bytes", "cspn_propagate", "cspn_propagate_scored", "cspn_propagate_transposed", "cspn3_propagate_from_guidance",
-    "cspn_transpose_weights", "cspn3_resident_plan", "cspn3_resident_workspace_bytes", "cspn3_forward_resident", "cspn3_transposed_resident", "cspn3_transposed_resident_guidance",
-    "cspnk_resident_plan", "cspnk_resident_workspace_bytes", "cspnk_forward_resident", "cspnk_forward_resident_history", "cspnk_transposed_resident",
-    "cspn_grad_weights", "cspn3_grad_guidance", "cspn_pac_grad_guided", "cspn3_backward_tail",
-    "cspn_pac_backward_tail", "cspn_metrics_accumulate", "cspn_metrics_per_frame_workspace_bytes", "cspn_metrics_per_frame", "cspn_meter_update",
-    "cspn_pac_out_size", "cspn_pac_force_generic", "cspn_pac_conv2d", "cspn_pac_conv2d_grad_input", "cspn_pac_conv2d_grad_kernel", "cspn_pac_nd2col", "cspn_unpool2d", "cspn_unpool2d_backward", "cspn_debug_set_lds_poison",
-)
-# every symbol include/cspn_criterion.h declares
-CRITERION_EXPORTS = ("cspn_criterion_abi_version", "cspn_criterion_workspace_bytes", "cspn_criterion_forward", "cspn_criterion_backward")
-# every symbol include/cspn_max8.h declares
-MAX8_EXPORTS = ("cspn_max8_abi_version", "cspn_max8_workspace_bytes", "cspn_max8_forward", "cspn_max8_backward")
-# every symbol include/cspn_abn.h declares
-ABN_EXPORTS = ("cspn_abn_abi_version", "cspn_abn_plan", "cspn_abn_workspace_bytes", "cspn_abn_forward", "cspn_abn_backward_reduce",
-               "cspn_abn_backward")
-# every symbol include/cspn_sparsify.h declares
-SPARSIFY_EXPORTS = ("cspn_sparsify_abi_version", "cspn_sparsify_slices", "cspn_sparsify_workspace_bytes", "cspn_sparsify")
-# every symbol include/cspn_transform.h declares
-TRANSFORM_EXPORTS = ("cspn_transform_abi_version", "cspn_transform_first_size", "cspn_transform_workspace_bytes", "cspn_transform",
-                     "cspn_transform_draw_params")
-# every symbol include/cspn_losses.h declares
-LOSSES_EXPORTS = ("cspn_losses_abi_version", "cspn_losses_workspace_bytes", "cspn_berhu_forward", "cspn_berhu_backward",
-                  "cspn_mean_loss_forward", "cspn_mean_loss_backward")
-# every symbol include/cspn_optim.h declares
-OPTIM_EXPORTS = ("cspn_optim_abi_version", "cspn_sgd_plan", "cspn_sgd_step")
-# every symbol include/cspn_visual.h declares
-VISUAL_EXPORTS = ("cspn_visual_abi_version", "cspn_visual_workspace_bytes", "cspn_visual_rows", "cspn_visual_features")
 
 
 class cspn_plan(ctypes.Structure):
@@ -126,8 +80,134 @@ class cspn_visual_rows(ctypes.Structure):       # cspn_visual_rows_t (include/cs
                 ("d_max", ctypes.c_float)]
 
 
-BENCH_UNRELATED = ("pac_conv2d.hip", "pac_conv2d_s2.hip", "cspn_unpool.hip", "cspn_metrics_frame.hip", "cspn_criterion.hip", "cspn_max8.hip",
-                   "cspn_abn.hip", "cspn_sparsify.hip", "cspn_transform.hip", "cspn_losses.hip", "cspn_optim.hip", "cspn_visual.hip")       # kernels no bench.py workload launches
+Family = collections.namedtuple("Family", "name header abi_version files functions")
+
+
+def _families():
+    """The one list of what the library is made of: everything below that names a file or a function reads it.  A family is a
+    header under include/, the ABI version of it this host code was written against, its files under csrc/ and its functions.
+    A file marked True is run by a bench.py workload and so part of code_digest(), as is the header of a family with such a file;
+    the others are part of the build's staleness hash only (a digest that moved would mark the HBM traffic recorded under
+    profiles/ as stale, bench.py `traffic_stale`).  A function is name -> argtypes (None: left unset) where it returns int, and
+    name -> (restype, argtypes) where it does not."""
+    vp, ci, cu, cl, cs, cf, cd = (ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_long, ctypes.c_size_t, ctypes.c_float,
+                                  ctypes.c_double)
+    ll, ull, ptr = ctypes.c_longlong, ctypes.c_ulonglong, ctypes.POINTER
+    plan, rplan, geom = ptr(cspn_plan), ptr(cspn_resident_plan), ptr(cspn_conv_geometry)
+
+    def family(name, header, abi_version, files, functions):
+        return Family(name, os.path.join(INCLUDE, header), abi_version, files,
+                      {n: sig if isinstance(sig, tuple) else (ci, sig) for n, sig in functions.items()})
+
+    return (
+        family("core", "cspn_hip.h", ABI_VERSION, {
+            "cspn_propagate.hip": True, "cspn_resident.hip": True, "cspnk_resident.hip": True, "cspnk_d2.hip": True,
+            "cspn_prepare.hip": True, "cspn_backward.hip": True, "cspn_metrics.hip": True, "cspn_metrics_frame.hip": False,
+            "cspn_debug.hip": True, "cspn_repair.hip": True, "pac_conv2d.hip": False, "pac_conv2d_s2.hip": False,
+            "cspn_unpool.hip": False, "cspn_common.hpp": True, "cspnk_helpers.hpp": True, "pac_launch.hpp": False}, {
+            "cspn_abi_version": None,
+            "cspn_last_error": (ctypes.c_char_p, None),
+            "cspn_plan_resolve": [ci, ci, ci, ci, ci, ci, plan, plan],
+            "cspn3_prepare": [vp, ci, cl, cl, ci, ci, ci, ci, vp, ci, vp, vp],
+            "cspn_pac_prepare": [vp, ci, ci, ci, ci, ci, vp, ci, vp],
+            "cspn_propagate_workspace_bytes": (cs, [ci, ci, ci, ci, ci, ci]),
+            "cspn_propagate": [vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, plan, vp],
+            "cspn_propagate_scored": [vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci, plan, vp],
+            "cspn_propagate_transposed": [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, plan, vp],
+            "cspn3_propagate_from_guidance": [vp, ci, cl, cl, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci, plan, vp],
+            "cspn_transpose_weights": [vp, vp, ci, ci, ci, ci, ci, vp],
+            "cspn3_resident_plan": [ci, ci, ci, ci, ci, ci, rplan],
+            "cspn3_resident_workspace_bytes": (cs, [ci, ci, ci]),
+            "cspn3_forward_resident": [vp, cl, cl, vp, vp, vp, vp, vp, vp, vp, cu, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, rplan, vp],
+            "cspn3_transposed_resident": [vp, vp, vp, vp, vp, cu, vp, ci, ci, ci, ci, ci, ci, rplan, vp],
+            "cspn3_transposed_resident_guidance": [vp, cl, cl, vp, vp, vp, vp, vp, cu, vp, ci, ci, ci, ci, ci, ci, rplan, vp],
+            "cspnk_resident_plan": [ci, ci, ci, ci, ci, ci, ci, ci, rplan],
+            "cspnk_resident_workspace_bytes": (cs, [ci, ci, ci, ci]),
+            "cspnk_forward_resident": [vp, ci, ci, vp, vp, vp, ci, vp, cu, vp, ci, ci, ci, ci, ci, vp, vp, ci, rplan, vp],
+            "cspnk_forward_resident_history": [vp, ci, ci, vp, vp, vp, vp, vp, cu, vp, ci, ci, ci, ci, ci, rplan, vp],
+            "cspnk_transposed_resident": [vp, ci, ci, vp, vp, ci, vp, vp, vp, cu, vp, ci, ci, ci, ci, ci, rplan, vp],
+            "cspn_grad_weights": [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp],
+            "cspn3_grad_guidance": [vp, ci, cl, cl, ci, vp, ci, vp, vp, vp, ci, ci, ci, vp],
+            "cspn_pac_grad_guided": [vp, ci, vp, vp, ci, ci, ci, ci, ci, vp],
+            "cspn3_backward_tail": [vp, vp, vp, vp, vp, vp, cl, cl, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp],
+            "cspn_pac_backward_tail": [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp],
+            "cspn_metrics_accumulate": [vp, vp, ci, cs, vp, ci, vp],
+            "cspn_metrics_per_frame_workspace_bytes": (cs, [ci, cs]),
+            "cspn_metrics_per_frame": [vp, vp, ci, ci, cs, vp, vp, vp],
+            "cspn_meter_update": [vp, ci, vp, vp],
+            "cspn_pac_out_size": [ci, ci, geom, ptr(ci), ptr(ci)],
+            "cspn_pac_force_generic": [ci, ptr(ci)],
+            "cspn_pac_conv2d": [vp, vp, vp, ci, ci, ci, ci, ci, ci, geom, vp],
+            "cspn_pac_conv2d_grad_input": [vp, vp, vp, ci, ci, ci, ci, ci, ci, geom, vp],
+            "cspn_pac_conv2d_grad_kernel": [vp, vp, vp, ci, ci, ci, ci, ci, ci, geom, vp],
+            "cspn_pac_nd2col": [vp, vp, ci, ci, ci, ci, ci, geom, vp],
+            "cspn_unpool2d": [vp, vp, ci, cl, ci, ci, ci, ci, ci, vp],
+            "cspn_unpool2d_backward": [vp, vp, ci, cl, ci, ci, ci, ci, ci, vp],
+            "cspn_debug_set_lds_poison": [ci, cu, ptr(ci)]}),
+        family("criterion", "cspn_criterion.h", 1, {"cspn_criterion.hip": False, "cspn_loss_units.hpp": False}, {
+            "cspn_criterion_abi_version": None,
+            "cspn_criterion_workspace_bytes": (cs, [cs]),
+            "cspn_criterion_forward": [vp, vp, ci, ci, cs, vp, vp, vp],
+            "cspn_criterion_backward": [vp, vp, ci, ci, cs, vp, vp, vp, vp]}),
+        family("max8", "cspn_max8.h", 1, {"cspn_max8.hip": False}, {
+            "cspn_max8_abi_version": None,
+            "cspn_max8_workspace_bytes": (cs, [ci, ci, ci, ci, ci]),
+            "cspn_max8_forward": [vp, cl, cl, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp],
+            "cspn_max8_backward": [vp, cl, cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]}),
+        family("abn", "cspn_abn.h", 1, {"cspn_abn.hip": False}, {
+            "cspn_abn_abi_version": None,
+            "cspn_abn_plan": [ci, ci, ci, ptr(cspn_abn_plan)],
+            "cspn_abn_workspace_bytes": (cs, [ci, ci, ci]),
+            "cspn_abn_forward": [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, ci, cf, vp, vp],
+            "cspn_abn_backward_reduce": [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, ci, cf, vp, vp],
+            "cspn_abn_backward": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, cf, vp, vp]}),
+        family("sparsify", "cspn_sparsify.h", 1, {"cspn_sparsify.hip": False, "cspn_philox.hpp": False}, {
+            "cspn_sparsify_abi_version": None,
+            "cspn_sparsify_slices": [cs],
+            "cspn_sparsify_workspace_bytes": (cs, [ci, cs]),
+            "cspn_sparsify": [vp, ci, ci, ci, ci, ci, ll, cf, vp, ci, vp, ull, vp, cl, vp, ci, vp, cl, cl, vp, vp, vp]}),
+        family("transform", "cspn_transform.h", 1, {"cspn_transform.hip": False}, {
+            "cspn_transform_abi_version": None,
+            "cspn_transform_first_size": [ci, ci, cd, ptr(ci), ptr(ci)],
+            "cspn_transform_workspace_bytes": (cs, [ci, ci, ci, ci, cd, ci, ci]),
+            "cspn_transform": [vp, vp, ci, ci, ci, cd, ci, ci, ci, vp, vp, cl, cl, vp, cl, vp, vp],
+            "cspn_transform_draw_params": [vp, ci, ull, vp, vp]}),
+        family("losses", "cspn_losses.h", 1, {"cspn_losses.hip": False}, {
+            "cspn_losses_abi_version": None,
+            "cspn_losses_workspace_bytes": (cs, [cs]),
+            "cspn_berhu_forward": [vp, vp, ci, cs, vp, vp, vp],
+            "cspn_berhu_backward": [vp, vp, ci, cs, vp, vp, vp, vp],
+            "cspn_mean_loss_forward": [vp, vp, ci, ci, cs, vp, vp, vp],
+            "cspn_mean_loss_backward": [vp, vp, ci, ci, cs, vp, vp, vp, vp]}),
+        family("optim", "cspn_optim.h", 1, {"cspn_optim.hip": False}, {
+            "cspn_optim_abi_version": None,
+            "cspn_sgd_plan": [ptr(cs), ci, ci, ptr(ci), ptr(cs)],
+            "cspn_sgd_step": [ptr(cspn_sgd_tensor), ci, ptr(cspn_sgd_hyper), ci, ci, vp]}),
+        family("visual", "cspn_visual.h", 1, {"cspn_visual.hip": False}, {
+            "cspn_visual_abi_version": None,
+            "cspn_visual_workspace_bytes": (cs, [ci, ci, cs]),
+            "cspn_visual_rows": [ptr(cspn_visual_rows), ci, ci, ci, vp, cs, vp, vp],
+            "cspn_visual_features": [vp, cl, ci, ci, ci, ci, ci, vp, cs, vp, vp]}),
+    )
+
+
+FAMILIES = _families()
+
+
+def family(name):
+    return next(f for f in FAMILIES if f.name == name)
+
+
+def _files(suffix, benchmarked=None):
+    return tuple(f for fam in FAMILIES for f, b in fam.files.items() if f.endswith(suffix) and benchmarked in (None, b))
+
+
+SOURCES = _files(".hip")                      # one TU each
+BENCH_UNRELATED = _files(".hip", False)       # kernels no bench.py workload launches
+HEADERS = tuple(os.path.join(CSRC, f) for f in _files(".hpp", True)) + tuple(f.header for f in FAMILIES if any(f.files.values()))
+BUILD_HEADERS = HEADERS + tuple(os.path.join(CSRC, f) for f in _files(".hpp", False)) + \
+    tuple(f.header for f in FAMILIES if not any(f.files.values()))
+EXPORTS = tuple(family("core").functions)      # every symbol include/cspn_hip.h declares
 
 
 def _source_digest(flags, code_only=False):
@@ -210,133 +290,13 @@ _lock = threading.Lock()
 
 
 def _declare(lib):
-    vp, ci, cl, cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_size_t
-    lib.cspn_abi_version.restype = ci
-    lib.cspn_last_error.restype = ctypes.c_char_p
-    lib.cspn_plan_resolve.argtypes = [ci, ci, ci, ci, ci, ci, ctypes.POINTER(cspn_plan), ctypes.POINTER(cspn_plan)]
-    lib.cspn3_prepare.argtypes = [vp, ci, cl, cl, ci, ci, ci, ci, vp, ci, vp, vp]
-    lib.cspn_pac_prepare.argtypes = [vp, ci, ci, ci, ci, ci, vp, ci, vp]
-    lib.cspn_propagate_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci]
-    lib.cspn_propagate_workspace_bytes.restype = cs
-    lib.cspn_propagate.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci,
-                                   ctypes.POINTER(cspn_plan), vp]
-    lib.cspn_propagate_scored.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci,
-                                          ctypes.POINTER(cspn_plan), vp]
-    lib.cspn_propagate_transposed.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ctypes.POINTER(cspn_plan), vp]
-    lib.cspn3_propagate_from_guidance.argtypes = [vp, ci, cl, cl, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci,
-                                                  vp, vp, ci,
-                                                  ctypes.POINTER(cspn_plan), vp]
-    lib.cspn3_resident_plan.argtypes = [ci, ci, ci, ci, ci, ci, ctypes.POINTER(cspn_resident_plan)]
-    lib.cspn3_resident_workspace_bytes.argtypes = [ci, ci, ci]
-    lib.cspn3_resident_workspace_bytes.restype = cs
-    lib.cspn3_forward_resident.argtypes = [vp, cl, cl, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci,
-                                           ctypes.POINTER(cspn_resident_plan), vp]
-    lib.cspn3_transposed_resident.argtypes = [vp, vp, vp, vp, vp, ctypes.c_uint, vp, ci, ci, ci, ci, ci, ci,
-                                              ctypes.POINTER(cspn_resident_plan), vp]
-    lib.cspn3_transposed_resident_guidance.argtypes = [vp, cl, cl, vp, vp, vp, vp, vp, ctypes.c_uint, vp, ci, ci, ci, ci, ci, ci,
-                                                       ctypes.POINTER(cspn_resident_plan), vp]
-    lib.cspnk_resident_plan.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ctypes.POINTER(cspn_resident_plan)]
-    lib.cspnk_resident_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    lib.cspnk_resident_workspace_bytes.restype = cs
-    lib.cspnk_forward_resident.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, ctypes.c_uint, vp, ci, ci, ci, ci, ci, vp, vp, ci,
-                                           ctypes.POINTER(cspn_resident_plan), vp]
-    lib.cspnk_forward_resident_history.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ctypes.c_uint, vp, ci, ci, ci, ci, ci,
-                                                   ctypes.POINTER(cspn_resident_plan), vp]
-    lib.cspnk_transposed_resident.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp, ctypes.c_uint, vp, ci, ci, ci, ci, ci,
-                                              ctypes.POINTER(cspn_resident_plan), vp]
-    lib.cspn_transpose_weights.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
-    lib.cspn_grad_weights.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-    lib.cspn3_grad_guidance.argtypes = [vp, ci, cl, cl, ci, vp, ci, vp, vp, vp, ci, ci, ci, vp]
-    lib.cspn_pac_grad_guided.argtypes = [vp, ci, vp, vp, ci, ci, ci, ci, ci, vp]
-    lib.cspn3_backward_tail.argtypes = [vp, vp, vp, vp, vp, vp, cl, cl, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
-    lib.cspn_pac_backward_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
-    lib.cspn_metrics_accumulate.argtypes = [vp, vp, ci, cs, vp, ci, vp]
-    lib.cspn_metrics_per_frame_workspace_bytes.argtypes = [ci, cs]
-    lib.cspn_metrics_per_frame_workspace_bytes.restype = cs
-    lib.cspn_metrics_per_frame.argtypes = [vp, vp, ci, ci, cs, vp, vp, vp]
-    lib.cspn_meter_update.argtypes = [vp, ci, vp, vp]
-    geom = ctypes.POINTER(cspn_conv_geometry)
-    lib.cspn_pac_out_size.argtypes = [ci, ci, geom, ctypes.POINTER(ci), ctypes.POINTER(ci)]
-    lib.cspn_pac_force_generic.argtypes = [ci, ctypes.POINTER(ci)]
-    lib.cspn_pac_conv2d.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, geom, vp]
-    lib.cspn_pac_conv2d_grad_input.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, geom, vp]
-    lib.cspn_pac_conv2d_grad_kernel.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, geom, vp]
-    lib.cspn_pac_nd2col.argtypes = [vp, vp, ci, ci, ci, ci, ci, geom, vp]
-    lib.cspn_unpool2d.argtypes = [vp, vp, ci, cl, ci, ci, ci, ci, ci, vp]
-    lib.cspn_unpool2d_backward.argtypes = [vp, vp, ci, cl, ci, ci, ci, ci, ci, vp]
-    lib.cspn_debug_set_lds_poison.argtypes = [ci, ctypes.c_uint, ctypes.POINTER(ci)]
-    lib.cspn_criterion_abi_version.restype = ci
-    lib.cspn_criterion_workspace_bytes.argtypes = [cs]
-    lib.cspn_criterion_workspace_bytes.restype = cs
-    lib.cspn_criterion_forward.argtypes = [vp, vp, ci, ci, cs, vp, vp, vp]
-    lib.cspn_criterion_forward.restype = ci
-    lib.cspn_criterion_backward.argtypes = [vp, vp, ci, ci, cs, vp, vp, vp, vp]
-    lib.cspn_criterion_backward.restype = ci
-    lib.cspn_max8_abi_version.restype = ci
-    lib.cspn_max8_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
-    lib.cspn_max8_workspace_bytes.restype = cs
-    lib.cspn_max8_forward.argtypes = [vp, cl, cl, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
-    lib.cspn_max8_forward.restype = ci
-    lib.cspn_max8_backward.argtypes = [vp, cl, cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
-    lib.cspn_max8_backward.restype = ci
-    cf = ctypes.c_float
-    lib.cspn_abn_abi_version.restype = ci
-    lib.cspn_abn_plan.argtypes = [ci, ci, ci, ctypes.POINTER(cspn_abn_plan)]
-    lib.cspn_abn_plan.restype = ci
-    lib.cspn_abn_workspace_bytes.argtypes = [ci, ci, ci]
-    lib.cspn_abn_workspace_bytes.restype = cs
-    lib.cspn_abn_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, ci, cf, vp, vp]
-    lib.cspn_abn_forward.restype = ci
-    lib.cspn_abn_backward_reduce.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, ci, cf, vp, vp]
-    lib.cspn_abn_backward_reduce.restype = ci
-    lib.cspn_abn_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, cf, vp, vp]
-    lib.cspn_abn_backward.restype = ci
-    ll, ull = ctypes.c_longlong, ctypes.c_ulonglong
-    lib.cspn_sparsify_abi_version.restype = ci
-    lib.cspn_sparsify_slices.argtypes = [cs]
-    lib.cspn_sparsify_slices.restype = ci
-    lib.cspn_sparsify_workspace_bytes.argtypes = [ci, cs]
-    lib.cspn_sparsify_workspace_bytes.restype = cs
-    lib.cspn_sparsify.argtypes = [vp, ci, ci, ci, ci, ci, ll, cf, vp, ci, vp, ull, vp, cl, vp, ci, vp, cl, cl, vp, vp, vp]
-    lib.cspn_sparsify.restype = ci
-    cd = ctypes.c_double
-    lib.cspn_transform_abi_version.restype = ci
-    lib.cspn_transform_first_size.argtypes = [ci, ci, cd, ctypes.POINTER(ci), ctypes.POINTER(ci)]
-    lib.cspn_transform_first_size.restype = ci
-    lib.cspn_transform_workspace_bytes.argtypes = [ci, ci, ci, ci, cd, ci, ci]
-    lib.cspn_transform_workspace_bytes.restype = cs
-    lib.cspn_transform.argtypes = [vp, vp, ci, ci, ci, cd, ci, ci, ci, vp, vp, cl, cl, vp, cl, vp, vp]
-    lib.cspn_transform.restype = ci
-    lib.cspn_transform_draw_params.argtypes = [vp, ci, ull, vp, vp]
-    lib.cspn_transform_draw_params.restype = ci
-    lib.cspn_losses_abi_version.restype = ci
-    lib.cspn_losses_workspace_bytes.argtypes = [cs]
-    lib.cspn_losses_workspace_bytes.restype = cs
-    lib.cspn_berhu_forward.argtypes = [vp, vp, ci, cs, vp, vp, vp]
-    lib.cspn_berhu_forward.restype = ci
-    lib.cspn_berhu_backward.argtypes = [vp, vp, ci, cs, vp, vp, vp, vp]
-    lib.cspn_berhu_backward.restype = ci
-    lib.cspn_mean_loss_forward.argtypes = [vp, vp, ci, ci, cs, vp, vp, vp]
-    lib.cspn_mean_loss_forward.restype = ci
-    lib.cspn_mean_loss_backward.argtypes = [vp, vp, ci, ci, cs, vp, vp, vp, vp]
-    lib.cspn_mean_loss_backward.restype = ci
-    lib.cspn_optim_abi_version.restype = ci
-    lib.cspn_sgd_plan.argtypes = [ctypes.POINTER(cs), ci, ci, ctypes.POINTER(ci), ctypes.POINTER(cs)]
-    lib.cspn_sgd_plan.restype = ci
-    lib.cspn_sgd_step.argtypes = [ctypes.POINTER(cspn_sgd_tensor), ci, ctypes.POINTER(cspn_sgd_hyper), ci, ci, vp]
-    lib.cspn_sgd_step.restype = ci
-    lib.cspn_visual_abi_version.restype = ci
-    lib.cspn_visual_workspace_bytes.argtypes = [ci, ci, cs]
-    lib.cspn_visual_workspace_bytes.restype = cs
-    lib.cspn_visual_rows.argtypes = [ctypes.POINTER(cspn_visual_rows), ci, ci, ci, vp, cs, vp, vp]
-    lib.cspn_visual_rows.restype = ci
-    lib.cspn_visual_features.argtypes = [vp, cl, ci, ci, ci, ci, ci, vp, cs, vp, vp]
-    lib.cspn_visual_features.restype = ci
-    for name in EXPORTS:
-        fn = getattr(lib, name)
-        if name not in ("cspn_last_error", "cspn_propagate_workspace_bytes", "cspn3_resident_workspace_bytes",
-                        "cspnk_resident_workspace_bytes", "cspn_metrics_per_frame_workspace_bytes"):
-            fn.restype = ci
+    for fam in FAMILIES:
+        for name, (restype, argtypes) in fam.functions.items():
+            fn = getattr(lib, name)
+            if restype is not ctypes.c_int:           # ctypes' default
+                fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
     return lib
 
 
@@ -351,24 +311,10 @@ def lib():
                         "cspn_monodepth_amd: %s is missing — build it with `python -c 'import __graft_entry__ as g; "
                         "g.build()'` (hipcc --offload-arch=gfx950).  There is no CPU fallback." % SO_PATH)
                 _lib = _declare(ctypes.CDLL(SO_PATH))
-                if _lib.cspn_abi_version() != ABI_VERSION:
-                    raise RuntimeError("cspn_monodepth_amd: ABI version mismatch")
-                if _lib.cspn_criterion_abi_version() != CRITERION_ABI_VERSION:
-                    raise RuntimeError("cspn_monodepth_amd: criterion ABI version mismatch")
-                if _lib.cspn_max8_abi_version() != MAX8_ABI_VERSION:
-                    raise RuntimeError("cspn_monodepth_amd: max8 ABI version mismatch")
-                if _lib.cspn_abn_abi_version() != ABN_ABI_VERSION:
-                    raise RuntimeError("cspn_monodepth_amd: abn ABI version mismatch")
-                if _lib.cspn_sparsify_abi_version() != SPARSIFY_ABI_VERSION:
-                    raise RuntimeError("cspn_monodepth_amd: sparsify ABI version mismatch")
-                if _lib.cspn_transform_abi_version() != TRANSFORM_ABI_VERSION:
-                    raise RuntimeError("cspn_monodepth_amd: transform ABI version mismatch")
-                if _lib.cspn_losses_abi_version() != LOSSES_ABI_VERSION:
-                    raise RuntimeError("cspn_monodepth_amd: losses ABI version mismatch")
-                if _lib.cspn_optim_abi_version() != OPTIM_ABI_VERSION:
-                    raise RuntimeError("cspn_monodepth_amd: optim ABI version mismatch")
-                if _lib.cspn_visual_abi_version() != VISUAL_ABI_VERSION:
-                    raise RuntimeError("cspn_monodepth_amd: visual ABI version mismatch")
+                for fam in FAMILIES:
+                    sub = "" if fam.name == "core" else fam.name      # cspn_abi_version, cspn_<family>_abi_version
+                    if getattr(_lib, "cspn_%sabi_version" % (sub and sub + "_"))() != fam.abi_version:
+                        raise RuntimeError("cspn_monodepth_amd: %sABI version mismatch" % (sub and sub + " "))
                 poison = os.environ.get("CSPN_DEBUG_LDS_POISON", "")      # debugging aid (include/cspn_hip.h): "nan" or a hex word
                 if poison and poison != "0":
                     _lib.cspn_debug_set_lds_poison(1, 0x7fc00000 if poison in ("1", "nan") else int(poison, 16), None)

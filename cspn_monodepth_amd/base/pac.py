@@ -24,7 +24,7 @@ import torch
 from torch.autograd.function import Function, once_differentiable
 
 from .. import _lib
-from ..functional import _device_guard, _dt, _p, _require_device, _stream
+from .._host import _dt, _p, _require_device, launch
 
 __all__ = ["conv2d", "Conv2dFn", "nd2col", "output_size"]
 
@@ -74,9 +74,7 @@ def _forward(input, kernel, g):
     dev = _require_device(input, kernel)
     x, k = input.contiguous(), kernel.contiguous()
     out = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=dev)
-    with _device_guard(dev):
-        ok = _lib.lib().cspn_pac_conv2d(_p(x), _p(k), _p(out), _dt(x), B, C, k.size(1), H, W, ctypes.byref(g), _stream(dev))
-    _lib.check(ok, "cspn_pac_conv2d")
+    launch(dev, "cspn_pac_conv2d", _p(x), _p(k), _p(out), _dt(x), B, C, k.size(1), H, W, ctypes.byref(g))
     return out
 
 
@@ -86,10 +84,7 @@ def _grad_input(grad_output, kernel, input_shape, g):
     dev = _require_device(grad_output, kernel)
     go, k = grad_output.contiguous(), kernel.contiguous()
     grad_input = torch.empty((B, C, H, W), dtype=go.dtype, device=dev)
-    with _device_guard(dev):
-        ok = _lib.lib().cspn_pac_conv2d_grad_input(_p(go), _p(k), _p(grad_input), _dt(go), B, C, k.size(1), H, W,
-                                                   ctypes.byref(g), _stream(dev))
-    _lib.check(ok, "cspn_pac_conv2d_grad_input")
+    launch(dev, "cspn_pac_conv2d_grad_input", _p(go), _p(k), _p(grad_input), _dt(go), B, C, k.size(1), H, W, ctypes.byref(g))
     return grad_input
 
 
@@ -100,10 +95,7 @@ def _grad_kernel(grad_output, input, kernel_ch, g):
     go, x = grad_output.contiguous(), input.contiguous()
     Ho, Wo = go.shape[-2:]
     grad_kernel = torch.empty((B, kernel_ch, g.kh, g.kw, Ho, Wo), dtype=go.dtype, device=dev)
-    with _device_guard(dev):
-        ok = _lib.lib().cspn_pac_conv2d_grad_kernel(_p(go), _p(x), _p(grad_kernel), _dt(go), B, C, kernel_ch, H, W,
-                                                    ctypes.byref(g), _stream(dev))
-    _lib.check(ok, "cspn_pac_conv2d_grad_kernel")
+    launch(dev, "cspn_pac_conv2d_grad_kernel", _p(go), _p(x), _p(grad_kernel), _dt(go), B, C, kernel_ch, H, W, ctypes.byref(g))
     return grad_kernel
 
 
@@ -149,9 +141,7 @@ class _Nd2colFn(Function):
         Ho, Wo = output_size((H, W), (g.kh, g.kw), (g.sh, g.sw), (g.ph, g.pw), (g.dh, g.dw), (g.oph, g.opw), bool(g.transposed))
         x = input_nd.contiguous()
         cols = torch.empty((B, C, g.kh, g.kw, Ho, Wo), dtype=x.dtype, device=dev)
-        with _device_guard(dev):
-            ok = _lib.lib().cspn_pac_nd2col(_p(x), _p(cols), _dt(x), B, C, H, W, ctypes.byref(g), _stream(dev))
-        _lib.check(ok, "cspn_pac_nd2col")
+        launch(dev, "cspn_pac_nd2col", _p(x), _p(cols), _dt(x), B, C, H, W, ctypes.byref(g))
         ctx.geom = g
         ctx.input_shape = (B, C, H, W)
         return cols

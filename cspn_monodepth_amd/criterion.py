@@ -26,6 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from ._host import launch
 
 KINDS = {"l1": _lib.LOSS_L1, "l2": _lib.LOSS_L2, "l1_log": _lib.LOSS_L1_LOG}
 MEAN_KINDS = {"l1": _lib.MEAN_L1, "grad": _lib.MEAN_GRAD, "rmse": _lib.MEAN_RMSE, "rmse_log": _lib.MEAN_RMSE_LOG}
@@ -65,10 +66,7 @@ class _Loss(torch.autograd.Function):
         entry, _, workspace, has_kind = _FAMILIES[family]
         n = a.numel()
         work, state = workspace(n, a.device)
-        with torch.cuda.device(a.device):
-            ok = getattr(_lib.lib(), entry)(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, *((kind,) if has_kind else ()), n, work.data_ptr(),
-                                            state.data_ptr(), torch.cuda.current_stream(a.device).cuda_stream)
-        _lib.check(ok, entry)
+        launch(a.device, entry, a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, *((kind,) if has_kind else ()), n, work.data_ptr(), state.data_ptr())
         ctx.save_for_backward(a, b)
         ctx.state, ctx.family, ctx.kind = state, family, kind
         return state[0]                                  # 0-dim view of the state's first word: no copy, no launch
@@ -85,11 +83,8 @@ class _Loss(torch.autograd.Function):
             g = g.to(device=a.device, dtype=torch.float32)
         g = g.contiguous()
         grad = torch.empty_like(a, memory_format=torch.contiguous_format)
-        with torch.cuda.device(a.device):
-            ok = getattr(_lib.lib(), entry)(a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, *((ctx.kind,) if has_kind else ()), a.numel(),
-                                            ctx.state.data_ptr(), g.data_ptr(), grad.data_ptr(),
-                                            torch.cuda.current_stream(a.device).cuda_stream)
-        _lib.check(ok, entry)
+        launch(a.device, entry, a.data_ptr(), b.data_ptr(), _lib.CSPN_F32, *((ctx.kind,) if has_kind else ()), a.numel(),
+               ctx.state.data_ptr(), g.data_ptr(), grad.data_ptr())
         return grad, None, None, None
 
 

@@ -10,6 +10,7 @@
 // Every pixel index is checked against HW before its load and before its store; the partial last unit of a frame always goes
 // element by element.
 #include "cspn_common.hpp"
+#include "cspn_philox.hpp"
 #include "cspn_sparsify.h"
 
 namespace {
@@ -58,24 +59,6 @@ __device__ __forceinline__ void store_unit_f32(float* __restrict__ plane, size_t
         for (int e = 0; e < 4; ++e)
             if (p0 + e < HW) st1(plane + p0 + e, v[e]);
     }
-}
-
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11) on the counter
-// (c0, 0, c2, c3) with the key (k0, k1); the first output word's upper 24 bits as a uniform in [0, 1).
-__device__ __forceinline__ double philox_uniform(unsigned c0, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-    unsigned c1 = 0u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return (double)(c0 >> 8) * 0x1p-24;
 }
 
 // grid (S, B): work[b * S + s] = kept pixels of the units q of frame b with (q / 256) % S == s
@@ -183,7 +166,7 @@ __global__ __launch_bounds__(SP_THREADS) void cspn_sparsify_apply_kernel(Sparsif
                 }
             } else {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) u[e] = philox_uniform((unsigned)(p0 + e), fid_lo, fid_hi, k0, k1);
+                for (int e = 0; e < 4; ++e) u[e] = philox_uniform<0u>((unsigned)(p0 + e), fid_lo, fid_hi, k0, k1);
             }
         }
         float rgb[3][4];

@@ -13,6 +13,7 @@
 // a rotated coordinate is turned into an index only after it passed 0 <= c <= n - 1 (a NaN fails that), and the second sizes are
 // clamped to [1, CSPN_TRANSFORM_MAX_SECOND].  Every pixel index is checked against oh * ow before its load and its store.
 #include "cspn_common.hpp"
+#include "cspn_philox.hpp"
 #include "cspn_transform.h"
 
 #pragma clang fp contract(off)
@@ -274,24 +275,6 @@ __global__ __launch_bounds__(TF_THREADS) void cspn_transform_finish_kernel(Trans
     store_rgb(a, b, pix, v, lut);
 }
 
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11) on the counter
-// (c0, 1, c2, c3) with the key (k0, k1); the first output word's upper 24 bits as a uniform in [0, 1).
-__device__ __forceinline__ double philox_uniform(unsigned c0, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-    unsigned c1 = 1u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return (double)(c0 >> 8) * 0x1p-24;
-}
-
 // one thread per frame
 __global__ __launch_bounds__(TF_DRAW_THREADS) void cspn_transform_draw_kernel(const long long* __restrict__ frame_ids, int B, unsigned long long seed,
                                                                                double* __restrict__ params) {
@@ -301,7 +284,7 @@ __global__ __launch_bounds__(TF_DRAW_THREADS) void cspn_transform_draw_kernel(co
     const unsigned lo = (unsigned)fid, hi = (unsigned)(fid >> 32), k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     double u[7];
 #pragma unroll
-    for (int k = 0; k < 7; ++k) u[k] = philox_uniform((unsigned)k, lo, hi, k0, k1);
+    for (int k = 0; k < 7; ++k) u[k] = philox_uniform<1u>((unsigned)k, lo, hi, k0, k1);
     double* p = params + (size_t)b * CSPN_TRANSFORM_PARAMS;
     p[0] = add_rn(1.0, mul_rn(0.5, u[0]));
     p[1] = add_rn(-5.0, mul_rn(10.0, u[1]));

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from ... import _lib
+from ..._host import _p, launch
 
 
 def _check_plane(name, t, B, H, W, channels, dtypes):
@@ -108,13 +109,9 @@ def _launch(sparsifier, depth, rgb, uniform, frame_ids, seed, want_mask=False, w
     work = None
     if not dense:
         work = torch.empty((L.cspn_sparsify_workspace_bytes(B, HW) // 4,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        ok = L.cspn_sparsify(depth.data_ptr(), _lib.CSPN_F32, B, H, W, _lib.SPARSIFY_DENSE if dense else _lib.SPARSIFY_UAR,
-                             0 if dense else int(sparsifier.num_samples), float("inf") if dense else float(np.float32(sparsifier.max_depth)),
-                             u_ptr, kind, ids_ptr, seed, None if sparse is None else sparse.data_ptr(), sparse_bs,
-                             rgb_ptr, rgb_kind, rgb_out_ptr, 4 * HW, HW, None if mask is None else mask.data_ptr(),
-                             None if work is None else work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(ok, "cspn_sparsify")
+    launch(dev, "cspn_sparsify", depth.data_ptr(), _lib.CSPN_F32, B, H, W, _lib.SPARSIFY_DENSE if dense else _lib.SPARSIFY_UAR,
+           0 if dense else int(sparsifier.num_samples), float("inf") if dense else float(np.float32(sparsifier.max_depth)),
+           u_ptr, kind, ids_ptr, seed, _p(sparse), sparse_bs, rgb_ptr, rgb_kind, rgb_out_ptr, 4 * HW, HW, _p(mask), _p(work))
     return sparse, rgbd, None if mask is None else mask.view(torch.bool)
 
 

@@ -42,6 +42,7 @@ import ctypes
 import torch
 
 from ... import _lib
+from ..._host import _p, launch
 
 iheight, iwidth = 480, 640      # raw image size (nyu_dataloader.py:5)
 OUTPUT_SIZE = (228, 304)        # nyu_dataloader.py:11
@@ -153,11 +154,8 @@ def _launch(rgb, depth, params, out, first, output_size, mode):
         rgb_out, depth_out = out
     nbytes = L.cspn_transform_workspace_bytes(mode, B, H, W, float(first), oh, ow)
     work = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        ok = L.cspn_transform(rgb.data_ptr(), depth.data_ptr(), B, H, W, float(first), oh, ow, mode,
-                              None if params is None else params.data_ptr(), rgb_out.data_ptr(), rgb_out.stride(0), rgb_out.stride(1),
-                              depth_out.data_ptr(), depth_out.stride(0), work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(ok, "cspn_transform")
+    launch(dev, "cspn_transform", rgb.data_ptr(), depth.data_ptr(), B, H, W, float(first), oh, ow, mode, _p(params), rgb_out.data_ptr(),
+           rgb_out.stride(0), rgb_out.stride(1), depth_out.data_ptr(), depth_out.stride(0), work.data_ptr())
     return rgb_out, depth_out
 
 
@@ -184,10 +182,9 @@ def draw_train_params(B, frame_ids=None, seed=0, device=None):
             raise RuntimeError("device must be a ROCm device (no CPU implementation here), got %s" % dev)
         frame_ids = torch.arange(B, dtype=torch.int64, device=dev)
     frame_ids = frame_ids.contiguous()
+    dev = frame_ids.device                  # a tensor's device has an index; a caller's "cuda" has none
     params = torch.empty((B, _lib.TRANSFORM_PARAMS), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        ok = _lib.lib().cspn_transform_draw_params(frame_ids.data_ptr(), B, seed, params.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(ok, "cspn_transform_draw_params")
+    launch(dev, "cspn_transform_draw_params", frame_ids.data_ptr(), B, seed, params.data_ptr())
     return params
 
 

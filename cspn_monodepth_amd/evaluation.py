@@ -21,7 +21,6 @@ valid-pixel count, and never exactly for rmse / irmse — a mean of square roots
   `trainer.eval` prints (libs/trainers/single_gpu_trainer.py:114-206) — at ANY batch size, without a host synchronisation
   per batch, and capturable in a graph: frame i's sums do not depend on the batch it arrived in.
 """
-import ctypes
 import math
 
 import torch
@@ -29,6 +28,7 @@ import torch.distributed as dist
 
 from . import _lib
 from . import functional as _F
+from ._host import launch
 
 METRIC_NAMES = ("irmse", "imae", "mse", "rmse", "mae", "absrel", "lg10", "delta1", "delta2", "delta3")
 N_SUMS = 10   # {inv^2, inv, diff^2, diff, diff/t, |dlog10|, #<1.25, #<1.25^2, #<1.25^3, n}
@@ -63,12 +63,7 @@ def metric_sums(pred, target, out=None):
     dt = _lib.CSPN_F32 if p.dtype == torch.float32 else _lib.CSPN_F16 if p.dtype == torch.float16 else None
     if dt is None:
         raise TypeError("metric_sums supports float32 / float16")
-    with torch.cuda.device(p.device):
-        ok = _lib.lib().cspn_metrics_accumulate(
-            ctypes.c_void_p(p.data_ptr()), ctypes.c_void_p(t.data_ptr()), dt, p.numel(),
-            ctypes.c_void_p(acc.data_ptr()), int(acc.shape[0]),
-            ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream))
-    _lib.check(ok, "cspn_metrics_accumulate")
+    launch(p.device, "cspn_metrics_accumulate", p.data_ptr(), t.data_ptr(), dt, p.numel(), acc.data_ptr(), int(acc.shape[0]))
     return acc.sum(0) if out is None else acc
 
 
@@ -191,10 +186,7 @@ def per_frame_workspace(B, pixels_per_frame, device):
 
 
 def _per_frame_launch(p, t, dt, B, n, work, sums):
-    with torch.cuda.device(p.device):
-        ok = _lib.lib().cspn_metrics_per_frame(p.data_ptr(), t.data_ptr(), dt, B, n, work.data_ptr(), sums.data_ptr(),
-                                               torch.cuda.current_stream(p.device).cuda_stream)
-    _lib.check(ok, "cspn_metrics_per_frame")
+    launch(p.device, "cspn_metrics_per_frame", p.data_ptr(), t.data_ptr(), dt, B, n, work.data_ptr(), sums.data_ptr())
 
 
 def metric_sums_per_frame(pred, target, out=None):
@@ -286,10 +278,7 @@ class FrameAverageMeter(object):
         if not sums.is_cuda or sums.device != self.device or sums.dtype != torch.float64 or sums.dim() != 2 \
                 or sums.shape[1] != N_SUMS or not sums.is_contiguous():
             raise ValueError("sums must be a contiguous float64 [B, 10] tensor on %s" % (self.device,))
-        with torch.cuda.device(self.device):
-            ok = _lib.lib().cspn_meter_update(sums.data_ptr(), int(sums.shape[0]), self.meter.data_ptr(),
-                                              torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(ok, "cspn_meter_update")
+        launch(self.device, "cspn_meter_update", sums.data_ptr(), int(sums.shape[0]), self.meter.data_ptr())
         return self
 
     def state(self):

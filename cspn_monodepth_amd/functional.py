@@ -16,6 +16,7 @@ import time
 import torch
 
 from . import _lib
+from ._host import _device_guard, _dt, _p, _require_device, _stream
 from ._lib import BLEND_NONE, BLEND_PREMASK, BLEND_SPARSE, CSPN_F16, CSPN_F32, STEP_AUTO, STEP_DOT2, STEP_FMA, cspn_plan
 
 _DEFAULT_PLANS = {}   # K -> dict, set by set_default_plan (e.g. from a tuning run)
@@ -216,54 +217,6 @@ def _plan_ptr(K, plan):
             raise ValueError("unknown plan field %r" % k)
         setattr(p, k, int(v))
     return ctypes.pointer(p)
-
-
-def _dt(t):
-    if t.dtype == torch.float32:
-        return CSPN_F32
-    if t.dtype == torch.float16:
-        return CSPN_F16
-    raise TypeError("CSPN HIP engine supports float32 / float16 tensors, got %s" % t.dtype)
-
-
-def _require_device(*tensors):
-    dev = None
-    for t in tensors:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError("CSPN HIP engine: tensors must live on a ROCm device (got %s); "
-                               "there is no CPU implementation in this package" % t.device)
-        if dev is None:
-            dev = t.device
-        elif t.device != dev:
-            raise RuntimeError("CSPN HIP engine: tensors on different devices (%s vs %s)" % (dev, t.device))
-    return dev
-
-
-class _device_guard(object):
-    """`with torch.cuda.device(dev)` only when `dev` is not already current (the common case costs ~nothing)."""
-    __slots__ = ("ctx",)
-
-    def __init__(self, dev):
-        self.ctx = None if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
-
-    def __enter__(self):
-        if self.ctx is not None:
-            self.ctx.__enter__()
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
-        return False
-
-
-def _stream(dev):
-    return torch._C._cuda_getCurrentRawStream(dev.index)       # (a plain int: the argtypes say c_void_p; no Stream object per call)
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()                  # (a plain int, as above: ~0.4 us per argument less than a c_void_p object)
 
 
 def _plane(t, B, H, W, name):

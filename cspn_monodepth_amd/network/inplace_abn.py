@@ -34,6 +34,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
+from .._host import _p, launch
 
 ACT_LEAKY_RELU = "leaky_relu"
 ACT_ELU = "elu"
@@ -88,10 +89,6 @@ def _validate(x, weight, bias, running_mean, running_var, training, activation, 
             raise RuntimeError("inplace_abn: all tensors must be on the input's device")
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _workspace(x, n, c, s):
     nbytes = _lib.lib().cspn_abn_workspace_bytes(n, c, s)
     return None if nbytes == 0 else torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=x.device)
@@ -100,33 +97,22 @@ def _workspace(x, n, c, s):
 def _native_forward(x, weight, bias, running_mean, running_var, mean, var, training, phase, momentum, eps, activation, slope):
     n, c, s = _ncs(x)
     work = _workspace(x, n, c, s)
-    with torch.cuda.device(x.device):
-        ok = _lib.lib().cspn_abn_forward(x.data_ptr(), _ptr(weight), _ptr(bias), _ptr(running_mean), _ptr(running_var), _ptr(mean),
-                                         _ptr(var), n, c, s, int(bool(training)), phase, float(momentum), float(eps),
-                                         _ACTIVATIONS[activation], float(slope), _ptr(work),
-                                         torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(ok, "cspn_abn_forward")
+    launch(x.device, "cspn_abn_forward", x.data_ptr(), _p(weight), _p(bias), _p(running_mean), _p(running_var), _p(mean),
+           _p(var), n, c, s, int(bool(training)), phase, float(momentum), float(eps), _ACTIVATIONS[activation], float(slope), _p(work))
 
 
 def _native_backward_reduce(z, dz, weight, bias, edz, eydz, eps, activation, slope):
     n, c, s = _ncs(z)
     work = _workspace(z, n, c, s)
-    with torch.cuda.device(z.device):
-        ok = _lib.lib().cspn_abn_backward_reduce(z.data_ptr(), dz.data_ptr(), _ptr(weight), _ptr(bias), edz.data_ptr(), eydz.data_ptr(),
-                                                 n, c, s, float(eps), _ACTIVATIONS[activation], float(slope), _ptr(work),
-                                                 torch.cuda.current_stream(z.device).cuda_stream)
-    _lib.check(ok, "cspn_abn_backward_reduce")
+    launch(z.device, "cspn_abn_backward_reduce", z.data_ptr(), dz.data_ptr(), _p(weight), _p(bias), edz.data_ptr(), eydz.data_ptr(),
+           n, c, s, float(eps), _ACTIVATIONS[activation], float(slope), _p(work))
 
 
 def _native_backward(z, dz, var, weight, bias, edz, eydz, dx, dweight, dbias, training, eps, activation, slope):
     n, c, s = _ncs(z)
     work = _workspace(z, n, c, s)
-    with torch.cuda.device(z.device):
-        ok = _lib.lib().cspn_abn_backward(z.data_ptr(), dz.data_ptr(), var.data_ptr(), _ptr(weight), _ptr(bias), _ptr(edz), _ptr(eydz),
-                                          dx.data_ptr(), _ptr(dweight), _ptr(dbias), n, c, s, int(bool(training)), float(eps),
-                                          _ACTIVATIONS[activation], float(slope), _ptr(work),
-                                          torch.cuda.current_stream(z.device).cuda_stream)
-    _lib.check(ok, "cspn_abn_backward")
+    launch(z.device, "cspn_abn_backward", z.data_ptr(), dz.data_ptr(), var.data_ptr(), _p(weight), _p(bias), _p(edz), _p(eydz),
+           dx.data_ptr(), _p(dweight), _p(dbias), n, c, s, int(bool(training)), float(eps), _ACTIVATIONS[activation], float(slope), _p(work))
 
 
 def _cotangent(dz, z):

@@ -21,8 +21,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import Function, once_differentiable
 
-from .. import _lib
-from ..functional import _device_guard, _dt, _p, _require_device, _stream
+from .._host import _dt, _p, _require_device, launch
 
 __all__ = ["up_pooling", "MyBlock"]
 
@@ -32,9 +31,7 @@ def _forward(x, scale, oh, ow):
     N, C, H, W = x.shape
     xc = x.contiguous()
     out = torch.empty((N, C, oh, ow), dtype=x.dtype, device=dev)
-    with _device_guard(dev):
-        ok = _lib.lib().cspn_unpool2d(_p(xc), _p(out), _dt(xc), N * C, H, W, scale, oh, ow, _stream(dev))
-    _lib.check(ok, "cspn_unpool2d")
+    launch(dev, "cspn_unpool2d", _p(xc), _p(out), _dt(xc), N * C, H, W, scale, oh, ow)
     return out
 
 
@@ -51,9 +48,7 @@ class _UpPooling(Function):
         dev = _require_device(grad_out)
         go = grad_out.contiguous()
         gx = torch.empty((N, C, H, W), dtype=go.dtype, device=dev)
-        with _device_guard(dev):
-            ok = _lib.lib().cspn_unpool2d_backward(_p(go), _p(gx), _dt(go), N * C, H, W, scale, oh, ow, _stream(dev))
-        _lib.check(ok, "cspn_unpool2d_backward")
+        launch(dev, "cspn_unpool2d_backward", _p(go), _p(gx), _dt(go), N * C, H, W, scale, oh, ow)
         return gx, None, None, None
 
 

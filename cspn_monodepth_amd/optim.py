@@ -26,6 +26,7 @@ import torch
 from torch.optim.optimizer import Optimizer
 
 from . import _lib
+from ._host import launch
 
 __all__ = ["SGD", "sgd_step"]
 
@@ -126,10 +127,7 @@ def _launch(device, params, grads, momentum_buffers, lr, momentum, dampening, we
     hyper = _lib.cspn_sgd_hyper(lr=0.0 if by_pointer else float(lr), lr_device=lr.data_ptr() if by_pointer else None,
                                 momentum=float(momentum), dampening=float(dampening), weight_decay=float(weight_decay),
                                 nesterov=int(bool(nesterov)), maximize=int(bool(maximize)))
-    with torch.cuda.device(device):
-        ok = _lib.lib().cspn_sgd_step(tensors, n, ctypes.byref(hyper), _lib.CSPN_F32, int(max_workgroups),
-                                      torch.cuda.current_stream(device).cuda_stream)
-    _lib.check(ok, "cspn_sgd_step")
+    launch(device, "cspn_sgd_step", tensors, n, ctypes.byref(hyper), _lib.CSPN_F32, int(max_workgroups))
 
 
 class SGD(Optimizer):

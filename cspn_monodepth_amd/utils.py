@@ -28,6 +28,7 @@ Left out: `get_save_path`, `get_logger`, `write_config_file`, `save_checkpoint` 
 import torch
 
 from . import _lib
+from ._host import _p, launch
 
 __all__ = ["colored_depthmap", "merge_into_row", "merge_into_row_with_gt", "merge_rgb_depth_into_row", "add_row", "save_image",
            "feature_map", "merge_features_into_row", "add_features_row", "save_featues_map", "save_features", "comparison_rows",
@@ -125,12 +126,9 @@ def _rows(rgb, scale, depths, d_min=None, d_max=None, out=None, work=None):
     a.d_min, a.d_max = float(d_min or 0.0), float(d_max or 0.0)
     P = len(planes) + (rgbp is not None)
     out = _out(out, B, H, P * W, device)
-    with torch.cuda.device(device):
-        if work is None and not (a.use_min and a.use_max):
-            work = torch.empty(workspace_bytes(B, len(planes), H * W), dtype=torch.uint8, device=device)
-        ok = _lib.lib().cspn_visual_rows(a, B, H, W, out.data_ptr(), H * P * W * 3, work.data_ptr() if work is not None else None,
-                                         torch.cuda.current_stream(device).cuda_stream)
-    _lib.check(ok, "cspn_visual_rows")
+    if work is None and not (a.use_min and a.use_max):
+        work = torch.empty(workspace_bytes(B, len(planes), H * W), dtype=torch.uint8, device=device)
+    launch(device, "cspn_visual_rows", a, B, H, W, out.data_ptr(), H * P * W * 3, _p(work))
     return out.view(B, H, P * W, 3)
 
 
@@ -152,11 +150,8 @@ def _features(features, n, out=None):
     if not 1 <= n <= C or H * W == 0:
         raise RuntimeError("utils: %d feature panels of a tensor of shape %s" % (n, tuple(f.shape)))
     out = _out(out, 1, H, n * W, device)
-    with torch.cuda.device(device):
-        work = torch.empty(workspace_bytes(1, 1, C * H * W), dtype=torch.uint8, device=device)
-        ok = _lib.lib().cspn_visual_features(f.data_ptr(), C * H * W, 1, C, H, W, n, out.data_ptr(), H * n * W * 3, work.data_ptr(),
-                                             torch.cuda.current_stream(device).cuda_stream)
-    _lib.check(ok, "cspn_visual_features")
+    work = torch.empty(workspace_bytes(1, 1, C * H * W), dtype=torch.uint8, device=device)
+    launch(device, "cspn_visual_features", f.data_ptr(), C * H * W, 1, C, H, W, n, out.data_ptr(), H * n * W * 3, work.data_ptr())
     return out.view(H, n * W, 3)
 
 

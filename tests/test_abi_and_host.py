@@ -13,22 +13,131 @@ from cspn_monodepth_amd import _lib
 from conftest import ROOT
 
 
-def _header_functions():
-    src = open(os.path.join(ROOT, "include", "cspn_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(cspn\w*)\s*\(", src)))
+# The contract of every family of the native library, stated here in literals (nothing below is read from the code under test):
+# name -> (header under include/, version macro, version, translation units, words a name of the family starts with after "cspn",
+# every function the header declares).  A new family is one more row.
+FAMILY_CONTRACT = {
+    "core": ("cspn_hip.h", "CSPN_ABI_VERSION", 10,
+             ("cspn_propagate.hip", "cspn_resident.hip", "cspnk_resident.hip", "cspnk_d2.hip", "cspn_prepare.hip", "cspn_backward.hip",
+              "cspn_metrics.hip", "cspn_metrics_frame.hip", "cspn_debug.hip", "cspn_repair.hip", "pac_conv2d.hip", "pac_conv2d_s2.hip",
+              "cspn_unpool.hip"), ("",),
+             ("cspn_abi_version", "cspn_last_error", "cspn_plan_resolve", "cspn3_prepare", "cspn_pac_prepare",
+              "cspn_propagate_workspace_bytes", "cspn_propagate", "cspn_propagate_scored", "cspn_propagate_transposed",
+              "cspn3_propagate_from_guidance", "cspn_transpose_weights", "cspn3_resident_plan", "cspn3_resident_workspace_bytes",
+              "cspn3_forward_resident", "cspn3_transposed_resident", "cspn3_transposed_resident_guidance", "cspnk_resident_plan",
+              "cspnk_resident_workspace_bytes", "cspnk_forward_resident", "cspnk_forward_resident_history", "cspnk_transposed_resident",
+              "cspn_grad_weights", "cspn3_grad_guidance", "cspn_pac_grad_guided", "cspn3_backward_tail", "cspn_pac_backward_tail",
+              "cspn_metrics_accumulate", "cspn_metrics_per_frame_workspace_bytes", "cspn_metrics_per_frame", "cspn_meter_update",
+              "cspn_pac_out_size", "cspn_pac_force_generic", "cspn_pac_conv2d", "cspn_pac_conv2d_grad_input", "cspn_pac_conv2d_grad_kernel",
+              "cspn_pac_nd2col", "cspn_unpool2d", "cspn_unpool2d_backward", "cspn_debug_set_lds_poison")),
+    "criterion": ("cspn_criterion.h", "CSPN_CRITERION_ABI_VERSION", 1, ("cspn_criterion.hip",), ("_criterion_",),
+                  ("cspn_criterion_abi_version", "cspn_criterion_workspace_bytes", "cspn_criterion_forward", "cspn_criterion_backward")),
+    "max8": ("cspn_max8.h", "CSPN_MAX8_ABI_VERSION", 1, ("cspn_max8.hip",), ("_max8_",),
+             ("cspn_max8_abi_version", "cspn_max8_workspace_bytes", "cspn_max8_forward", "cspn_max8_backward")),
+    "abn": ("cspn_abn.h", "CSPN_ABN_ABI_VERSION", 1, ("cspn_abn.hip",), ("_abn_",),
+            ("cspn_abn_abi_version", "cspn_abn_plan", "cspn_abn_workspace_bytes", "cspn_abn_forward", "cspn_abn_backward_reduce",
+             "cspn_abn_backward")),
+    "sparsify": ("cspn_sparsify.h", "CSPN_SPARSIFY_ABI_VERSION", 1, ("cspn_sparsify.hip",), ("_sparsify",),
+                 ("cspn_sparsify_abi_version", "cspn_sparsify_slices", "cspn_sparsify_workspace_bytes", "cspn_sparsify")),
+    "transform": ("cspn_transform.h", "CSPN_TRANSFORM_ABI_VERSION", 1, ("cspn_transform.hip",), ("_transform",),
+                  ("cspn_transform_abi_version", "cspn_transform_first_size", "cspn_transform_workspace_bytes", "cspn_transform",
+                   "cspn_transform_draw_params")),
+    "losses": ("cspn_losses.h", "CSPN_LOSSES_ABI_VERSION", 1, ("cspn_losses.hip",), ("_losses_", "_berhu_", "_mean_loss_"),
+               ("cspn_losses_abi_version", "cspn_losses_workspace_bytes", "cspn_berhu_forward", "cspn_berhu_backward",
+                "cspn_mean_loss_forward", "cspn_mean_loss_backward")),
+    "optim": ("cspn_optim.h", "CSPN_OPTIM_ABI_VERSION", 1, ("cspn_optim.hip",), ("_optim_", "_sgd_"),
+              ("cspn_optim_abi_version", "cspn_sgd_plan", "cspn_sgd_step")),
+    "visual": ("cspn_visual.h", "CSPN_VISUAL_ABI_VERSION", 1, ("cspn_visual.hip",), ("_visual_",),
+               ("cspn_visual_abi_version", "cspn_visual_workspace_bytes", "cspn_visual_rows", "cspn_visual_features")),
+}
+BUILD_ONLY_HPP = ("pac_launch.hpp", "cspn_loss_units.hpp", "cspn_philox.hpp")
 
 
-def test_library_exports_every_declared_symbol():
-    _lib.build()
-    lib = ctypes.CDLL(_lib.SO_PATH)
-    declared = _header_functions()
-    assert set(declared) == set(_lib.EXPORTS), (declared, _lib.EXPORTS)
-    for name in declared:
-        assert hasattr(lib, name), name
-    assert _lib.lib().cspn_abi_version() == _lib.ABI_VERSION == 10
-    assert _lib.lib().cspn_propagate_workspace_bytes(24, 228, 304, 24, _lib.CSPN_F32, 0) == 2 * 24 * 228 * 304 * 4
-    assert _lib.lib().cspn_propagate_workspace_bytes(24, 228, 304, 24, _lib.CSPN_F32, 1) == 0
+def _header_source(header):
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+
+
+def test_families_are_the_nine_in_the_order_they_were_added():
+    assert [f.name for f in _lib.FAMILIES] == list(FAMILY_CONTRACT)
+    assert _lib.EXPORTS == FAMILY_CONTRACT["core"][5] and _lib.family("visual") is _lib.FAMILIES[-1]
+    assert _lib.SOURCES == tuple(tu for row in FAMILY_CONTRACT.values() for tu in row[3])
+
+
+@pytest.mark.parametrize("name", list(FAMILY_CONTRACT))
+def test_family_contract(name):
+    """Header, table, library and loader agree on one family: the version macro, the declared functions, their names' prefix,
+    the symbols of a fresh build, the running version, and which hash the family's files belong to."""
+    header, macro, version, tus, prefixes, names = FAMILY_CONTRACT[name]
+    fam = _lib.family(name)
+    assert fam.header == os.path.join(ROOT, "include", header)
+    assert re.search(r"^#define %s %d$" % (macro, version), open(fam.header).read(), flags=re.M)
+    src = _header_source(header)
+    declared = sorted(set(re.findall(r"\b(cspn\w*)\s*\(", src)))
+    assert declared == sorted(fam.functions) == sorted(names), (declared, list(fam.functions))
+    assert all(n.startswith(tuple("cspn" + p for p in prefixes)) for n in names)
+    lib = ctypes.CDLL(_lib.build())
+    for n in names:
+        assert hasattr(lib, n), n
+    version_fn = macro.lower()
+    assert version_fn in names and getattr(_lib.lib(), version_fn)() == fam.abi_version == version
+    assert set(tus) <= set(_lib.SOURCES) and set(tus) == {f for f in fam.files if f.endswith(".hip")}
+    if name == "core":
+        assert _lib.ABI_VERSION == 10 and fam.header in _lib.HEADERS
+        assert _lib.lib().cspn_propagate_workspace_bytes(24, 228, 304, 24, _lib.CSPN_F32, 0) == 2 * 24 * 228 * 304 * 4
+        assert _lib.lib().cspn_propagate_workspace_bytes(24, 228, 304, 24, _lib.CSPN_F32, 1) == 0
+        return
+    assert set(tus) <= set(_lib.BENCH_UNRELATED)
+    assert fam.header in _lib.BUILD_HEADERS and fam.header not in _lib.HEADERS
+    # no family's name inside another's: not in the main header, not in a function name of any other family
+    assert name not in _header_source("cspn_hip.h")
+    for other, row in FAMILY_CONTRACT.items():
+        if other != name:
+            assert not any("cspn" + p in n for p in prefixes for n in row[5]), other
+    # nothing else of the family's translation unit leaves the library: every dynamic symbol that names it is a declared one
+    import shutil
+    import subprocess
+    if shutil.which("nm"):
+        nm = subprocess.run(["nm", "-D", "--defined-only", _lib.SO_PATH], capture_output=True, text=True, check=True)
+        ours = sorted(ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln and any(p.strip("_") in ln for p in prefixes))
+        assert ours == declared
+
+
+def test_family_names_are_pairwise_disjoint():
+    rows = [(name, set(row[5])) for name, row in FAMILY_CONTRACT.items()]
+    assert all(len(row[5]) == len(set(row[5])) for row in FAMILY_CONTRACT.values())
+    for i, (a, na) in enumerate(rows):
+        for b, nb in rows[i + 1:]:
+            assert not na & nb, (a, b, na & nb)
+            assert not set(_lib.family(a).functions) & set(_lib.family(b).functions), (a, b)
+
+
+def test_code_digest_covers_the_benchmarked_files_only():
+    """code_digest() pins the HBM traffic recorded under profiles/ to the benchmarked kernels.  Restated here over its own file
+    list; the headers only the other families see are part of the build's staleness hash, and not part of that digest."""
+    for hpp in BUILD_ONLY_HPP:
+        path = os.path.join(_lib.CSRC, hpp)
+        assert path in _lib.BUILD_HEADERS and path not in _lib.HEADERS
+    assert set(_lib.HEADERS) <= set(_lib.BUILD_HEADERS) and len(_lib.HEADERS) == 3
+    import hashlib
+    h = hashlib.sha256(b"")
+    for path in [os.path.join(_lib.CSRC, f) for f in _lib.SOURCES if f not in _lib.BENCH_UNRELATED] + list(_lib.HEADERS):
+        data = re.sub(rb"/\*.*?\*/", b"", open(path, "rb").read(), flags=re.S)
+        lines = (re.sub(rb"//.*$", b"", ln).strip() for ln in data.splitlines())
+        h.update(b"\n".join(re.sub(rb"\s+", b" ", ln) for ln in lines if ln))
+    assert _lib.code_digest() == h.hexdigest()
+    assert _lib._source_digest(["x"]) != _lib._source_digest(["x"], code_only=True)
+
+
+def test_ctypes_signatures_match_the_recorded_ones():
+    """Every exported function carries the restype and argtypes recorded in tests/golden/g26_ctypes_signatures.json
+    (tools/dump_ctypes_signatures.py, written when every declaration was still a hand-written line)."""
+    import json
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "g26_ctypes_signatures.json")))
+    assert sorted(want) == sorted(n for row in FAMILY_CONTRACT.values() for n in row[5])
+    for name, sig in want.items():
+        fn = getattr(_lib.lib(), name)
+        got = {"restype": getattr(fn.restype, "__name__", None), "argtypes": fn.argtypes and [t.__name__ for t in fn.argtypes]}
+        assert got == sig, (name, got, sig)
 
 
 def test_module_api_matches_reference_contract():
@@ -460,3 +569,27 @@ def test_bench_dump_outputs_writes_float_arrays_and_samples_past_the_budget(tmp_
     s1, s2 = np.load(str(tmp_path / "one" / "big.npy")), np.load(str(tmp_path / "two" / "big.npy"))
     assert s1.dtype == np.float32 and 0 < s1.nbytes <= 40000 and np.array_equal(s1, s2)
     assert np.all(np.diff(s1) > 0) and np.isin(s1, big.numpy()).all()
+
+
+@pytest.mark.gpu
+def test_a_device_without_an_index_is_the_current_device():
+    """The launch helpers read `dev.index`; a caller's torch.device("cuda") has none.  The entries that take a device from the
+    caller — the frame meter, the drawn transform parameters — and tensors made on "cuda" give what "cuda:0" gives."""
+    from cspn_monodepth_amd import evaluation as ev
+    from cspn_monodepth_amd import utils
+    from cspn_monodepth_amd.dataloaders.nyu_dataloader import draw_train_params
+    g = torch.Generator().manual_seed(5)
+    target = torch.rand(2, 1, 3, 5, generator=g) + 0.5
+    pred = target + 0.1 * torch.rand(2, 1, 3, 5, generator=g)
+    depth = torch.tensor([[[[0.5, 1.0, 2.0]]]])                      # 1 x 1 x 1 x 3
+    rgb = torch.arange(9, dtype=torch.uint8).reshape(1, 3, 1, 3)
+    got = []
+    for dev in (torch.device("cuda"), torch.device("cuda:0")):
+        assert torch.cuda.current_device() == 0
+        meter = ev.FrameAverageMeter(dev).update(pred.to(dev), target.to(dev))
+        got.append((meter.state().cpu(), utils.colored_depthmap(depth[0, 0].to(dev)).cpu(),
+                    utils.comparison_rows(rgb.to(dev), depth.to(dev), (2 * depth).to(dev), "rgb").cpu(),
+                    draw_train_params(2, seed=7, device=dev).cpu()))
+    assert got[0][0][10] == 2 and got[0][1].shape == (1, 3, 3) and got[0][2].shape == (1, 1, 9, 3) and got[0][3].shape == (2, 8)
+    for a, b in zip(*got):
+        assert torch.equal(a, b)

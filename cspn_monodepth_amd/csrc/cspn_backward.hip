@@ -142,13 +142,10 @@ struct TailArgs {
 // profiles/r04_kernel_stats_train_leg_pac5_state16.csv).  Raw loads from a safe address + a select after the conversion keep
 // every load of a trip in flight together; the empty asm pins the conversion behind the load phase.
 // Cache policy of the tails' single-use streams.  Every G quad is read by exactly one thread, every d row by the threads of three
-// rows: G loads that allocate in the L2 push out the d lines the neighbouring rows are about to re-read.  Non-temporal G loads
-// (bit 2), epilogue stores (4) and epilogue guidance loads (8): cspn_grad_tail<3, float, float, 1> 107.5-108.7 -> 89.5-93.0 us in a
-// same-box A/B (two alternating repetitions; G loads alone: 92.0-96.8); non-temporal loads of the d history (1) cost 4 us —
-// they are the re-used stream.  The K = 5 split tail does not care (66-69 us either way).  Results are bit-identical.
-#ifndef CSPN_TAIL_NT
-#define CSPN_TAIL_NT 14
-#endif
+// rows: G loads that allocate in the L2 push out the d lines the neighbouring rows are about to re-read.  Non-temporal G loads,
+// epilogue stores (st4_ep) and epilogue guidance loads (ld4_ep): cspn_grad_tail<3, float, float, 1> 107.5-108.7 -> 89.5-93.0 us in a
+// same-box A/B (two alternating repetitions; G loads alone: 92.0-96.8); non-temporal loads of the d history (TailRaw<float>::ldq) cost
+// 4 us — they are the re-used stream — and stay plain.  The K = 5 split tail does not care (66-69 us either way).  Results are bit-identical.
 __device__ __forceinline__ float4 ld4_nt(const float* p) {
     const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
     return make_float4(v.x, v.y, v.z, v.w);
@@ -157,22 +154,17 @@ __device__ __forceinline__ void st4_nt(float* p, float4 q) {
     const v4f v = {q.x, q.y, q.z, q.w};
     __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(p));
 }
-template <typename WT>
-__device__ __forceinline__ float4 ld4_ep(const WT* p) {
-    if constexpr (std::is_same<WT, float>::value && (CSPN_TAIL_NT & 8) != 0) return ld4_nt(p);
-    else return ld4(p);
-}
-template <typename WT>
-__device__ __forceinline__ void st4_ep(WT* p, float4 v) {
-    if constexpr (std::is_same<WT, float>::value && (CSPN_TAIL_NT & 4) != 0) st4_nt(p, v);
-    else st4(p, v);
-}
+// the epilogue's guidance loads and result stores: non-temporal on fp32 planes, plain on fp16 ones
+__device__ __forceinline__ float4 ld4_ep(const float* p) { return ld4_nt(p); }
+__device__ __forceinline__ float4 ld4_ep(const __half* p) { return ld4(p); }
+__device__ __forceinline__ void st4_ep(float* p, float4 v) { st4_nt(p, v); }
+__device__ __forceinline__ void st4_ep(__half* p, float4 v) { st4(p, v); }
 template <typename DT> struct TailRaw;
 template <> struct TailRaw<float> {
     static constexpr bool RAW = false;        // fp32: the guarded loads themselves (no conversion to sink; 124 VGPRs = 4 waves per SIMD)
     typedef float4 Q;
     typedef float S;
-    static __device__ __forceinline__ Q ldq(const float* p) { return (CSPN_TAIL_NT & 1) ? ld4_nt(p) : ld4(p); }
+    static __device__ __forceinline__ Q ldq(const float* p) { return ld4(p); }
     static __device__ __forceinline__ S lds(const float* p) { return *p; }
     static __device__ __forceinline__ float4 f4(Q q) { return q; }
     static __device__ __forceinline__ float f1(S s) { return s; }
@@ -197,12 +189,6 @@ template <> struct TailRaw<__half> {
     static __device__ __forceinline__ S zero() { return 0u; }
 };
 
-#ifndef CSPN_TAIL_REBUILD_W
-#define CSPN_TAIL_REBUILD_W 1      // 3x3 epilogue: rebuild w_j from the guidance quads + S instead of reading the tap volume
-#endif
-#ifndef CSPN_TAIL_PROBE
-#define CSPN_TAIL_PROBE 0          // developer A/B: 1 = no scatter epilogue (stream + epilogue loads only), 2 = no stream loop
-#endif
 template <int K, typename DT, typename WT, int VARIANT>
 __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
     constexpr int R = K / 2;
@@ -237,12 +223,10 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
     // Software-pipelined stream over the histories: the loads of UNR steps (G quad, 2R+1 row quads, and the
     // strip-end lanes' scalar halo patches) are all issued before the first one is consumed; otherwise every
     // step (and every patch load) is a serialised HBM/L2 round trip and the pass is latency-bound.
-#ifndef CSPN_TAIL_UNR3
-#define CSPN_TAIL_UNR3 3       // 124 VGPRs -> 4 waves/SIMD; 4 steps in flight need 146 (3 waves) and measured 2.5 % slower
-#endif
-    constexpr int UNR = (K == 3) ? CSPN_TAIL_UNR3 : (K == 5 ? 2 : 1);
+    constexpr int UNR3 = 3;        // 124 VGPRs -> 4 waves/SIMD; 4 steps in flight need 146 (3 waves) and measured 2.5 % slower
+    constexpr int UNR = (K == 3) ? UNR3 : (K == 5 ? 2 : 1);
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t0 = 0; t0 < (CSPN_TAIL_PROBE == 2 ? 0 : T); t0 += UNR) {
+    for (int t0 = 0; t0 < T; t0 += UNR) {
         typedef TailRaw<DT> RW;
         float4 Gq[UNR];
         typename RW::Q midq[UNR][2 * R + 1];
@@ -253,7 +237,7 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
             const bool tv = live && t < T;
             const DT* d = (t == 0) ? d0 : dh + (size_t)(tv ? t - 1 : 0) * plane;
             const float* gsrc = (t == T - 1) ? a.g_T : a.ghist + (size_t)(tv ? T - 2 - t : 0) * plane;      // G_{t+1}
-            Gq[u] = tv ? ((CSPN_TAIL_NT & 2) ? ld4_nt(gsrc + off) : ld4(gsrc + off)) : z4;
+            Gq[u] = tv ? ld4_nt(gsrc + off) : z4;
 #pragma unroll
             for (int rr = 0; rr < 2 * R + 1; ++rr) {
                 const int row = y + rr - R;
@@ -363,12 +347,11 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
         WT* gg = static_cast<WT*>(a.gout) + (size_t)b * a.g_bs;
         const float4 Sv = ld4(a.S + off);
         const float S4[4] = {Sv.x, Sv.y, Sv.z, Sv.w};
-#if CSPN_TAIL_REBUILD_W
         // w_j[p] = |g_{7-j}[p + off_j]| / S[p] is REBUILT from the guidance quads this epilogue loads anyway (for the signs of the
         // scatter targets) instead of being read back from the forward's tap volume: the aligned quad of channel 7-j on row
         // y + dy_j, shifted by dx_j with one DPP move (strip-end lanes patch with the scalar they load for their extra store).
         // Same recipe as the forward (div8_shared_reciprocal: |g| * refined 1/S), so fp32 taps come out bit-identical; 53 MB
-        // less to read per backward at config 2.
+        // less to read per backward at config 2.  (The epilogue that reads the tap volume a.w: tools/probes/tail_tap_volume_epilogue.patch.)
         float gq[8][4], gl[8], gr[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -383,7 +366,6 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
             if (dx > 0 && lane == 63 && qx < WQ - 1 && tok) gr[j] = ld1(g + o + 4);
             if (dx < 0 && lane == 0 && qx > 0 && tok) gl[j] = ld1(g + o - 1);
         }
-#endif
         float rS[4];          // 1/S by the forward's recipe (rcp + one Newton step): 4 reciprocals instead of 32 divisions
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -391,7 +373,6 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
             rS[e] = fmaf(fmaf(-S4[e], r, 1.0f), r, r);
         }
         float dot[4] = {0.f, 0.f, 0.f, 0.f};
-#if CSPN_TAIL_REBUILD_W
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int lin = j < 4 ? j : j + 1;
@@ -412,21 +393,6 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) dot[e] = fmaf(acc[j][e], fabsf(ax[e]) * rS[e], dot[e]);
         }
-#else
-        {
-            const WT* w8 = static_cast<const WT*>(a.w) + (size_t)b * Taps<WT>::image_elems(8, HW);
-            float w4[8][4];
-            load_taps_quad<8>(w8, (size_t)y * W + x, HW, true, w4);
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) dot[e] = fmaf(acc[j][e], w4[j][e], dot[e]);
-        }
-#endif
-#if CSPN_TAIL_PROBE == 1
-        if (dot[0] == 12345.678f) st4(gg + (size_t)y * W + x, make_float4(dot[0], dot[1], dot[2], dot[3]));      // stream + loads only
-        return;
-#endif
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int lin = j < 4 ? j : j + 1;
@@ -444,12 +410,8 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
             const float from_next = dpp_from_next_lane(gA[0]);
             if (ty >= 0 && ty < H) {
                 const size_t o = cplane + (size_t)ty * W + x;
-#if CSPN_TAIL_REBUILD_W
                 const float4 gs = sgn4(make_float4(gq[j][0], gq[j][1], gq[j][2], gq[j][3]));
                 const float gs_r = sgnf(gr[j]), gs_l = sgnf(gl[j]);
-#else
-                const float4 gs = sgn4(ld4(g + o));
-#endif
                 if (dx == 0) {
                     st4_ep(gg + o, make_float4(gs.x * gA[0], gs.y * gA[1], gs.z * gA[2], gs.w * gA[3]));
                 } else if (dx > 0) {
@@ -459,11 +421,7 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
                     } else {
                         st4_ep(gg + o, make_float4(gs.x * v0, gs.y * gA[0], gs.z * gA[1], gs.w * gA[2]));
                     }
-#if CSPN_TAIL_REBUILD_W
                     if (lane == 63 && qx < WQ - 1) st1(gg + o + 4, gs_r * gA[3]);
-#else
-                    if (lane == 63 && qx < WQ - 1) st1(gg + o + 4, sgnf(ld1(g + o + 4)) * gA[3]);
-#endif
                 } else {
                     const float v3 = (qx == WQ - 1) ? 0.f : from_next;         // column W-1 has no source
                     if (lane == 63 && qx < WQ - 1) {
@@ -471,11 +429,7 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
                     } else {
                         st4_ep(gg + o, make_float4(gs.x * gA[1], gs.y * gA[2], gs.z * gA[3], gs.w * v3));
                     }
-#if CSPN_TAIL_REBUILD_W
                     if (lane == 0 && qx > 0) st1(gg + o - 1, gs_l * gA[0]);
-#else
-                    if (lane == 0 && qx > 0) st1(gg + o - 1, sgnf(ld1(g + o - 1)) * gA[0]);
-#endif
                 }
             }
             // rows of this plane that no source row reaches: row 0 (dy=+1) / row H-1 (dy=-1)
@@ -524,10 +478,6 @@ template <> struct TailQuad<__half> {
     static __device__ __forceinline__ float4 f4(Q q) { return TailRaw<__half>::f4(q); }
 };
 
-#ifndef CSPN_TAIL5_UNR
-#define CSPN_TAIL5_UNR 2
-#endif
-
 template <int NT0, int CNT>
 __device__ __forceinline__ void load_tap_range_quad(const float* img, size_t p, size_t HW, float (&out)[CNT][4]) {
 #pragma unroll
@@ -556,7 +506,7 @@ template <typename DT, typename WT, int VARIANT, int HALF>
 __device__ __forceinline__ void tail5_half(const TailArgs& a, float4 (*xdot)[128]) {
     constexpr int K = 5, R = 2, NT = 24, NH = 12, RR = R + 1, WIN = 4 + 2 * R;
     constexpr int DY0 = HALF ? 0 : -R;                  // window row rr holds image row y + DY0 + rr
-    constexpr int UNR = CSPN_TAIL5_UNR;
+    constexpr int UNR = 2;                              // steps of loads in flight
     typedef TailQuad<DT> QD;
     typedef TailPair<DT> PR;
     const int H = a.H, W = a.W, T = a.T;
@@ -607,7 +557,7 @@ __device__ __forceinline__ void tail5_half(const TailArgs& a, float4 (*xdot)[128
             const int tc = t < T ? t : T - 1;           // a step past the end re-reads the last one; its G is zeroed below
             const DT* d = ((tc == 0) ? d0 : dh + (size_t)(tc - 1) * plane) + (size_t)b * HW;
             const float* gsrc = (tc == T - 1) ? a.g_T : a.ghist + (size_t)(T - 2 - tc) * plane;      // G_{t+1}
-            Gq[u] = (CSPN_TAIL_NT & 2) ? ld4_nt(gsrc + off) : ld4(gsrc + off);
+            Gq[u] = ld4_nt(gsrc + off);
 #pragma unroll
             for (int rr = 0; rr < RR; ++rr) {
                 const DT* rp = d + rowoff[rr];
@@ -729,11 +679,8 @@ bool tail5_split_enabled() {
 template <int K, typename DT, typename WT>
 int launch_tail(const TailArgs& a, int variant, hipStream_t st) {
     const size_t nquads = (size_t)a.B * a.H * (a.W / 4);
-#ifndef CSPN_TAIL_BLOCK
-#define CSPN_TAIL_BLOCK 256
-#endif
-    const int grid = (int)((nquads + 255) / 256);
-    const int grid3 = (int)((nquads + CSPN_TAIL_BLOCK - 1) / CSPN_TAIL_BLOCK);
+    constexpr int TAIL_BLOCK = 256;       // one quad per thread (cspn_grad_tail's __launch_bounds__)
+    const int grid = (int)((nquads + TAIL_BLOCK - 1) / TAIL_BLOCK);
     if constexpr (K == 5) {
         if ((variant == 0 || variant == 2) && tail5_split_enabled()) {
             const int grid5 = (int)((nquads + 127) / 128);
@@ -743,9 +690,9 @@ int launch_tail(const TailArgs& a, int variant, hipStream_t st) {
             return 1;
         }
     }
-    if (variant == 0) hipLaunchKernelGGL((cspn_grad_tail<K, DT, WT, 0>), dim3(grid), dim3(256), 0, st, a);
-    else if (variant == 2) hipLaunchKernelGGL((cspn_grad_tail<K, DT, WT, 2>), dim3(grid), dim3(256), 0, st, a);
-    else if constexpr (K == 3) hipLaunchKernelGGL((cspn_grad_tail<3, DT, WT, 1>), dim3(grid3), dim3(CSPN_TAIL_BLOCK), 0, st, a);
+    if (variant == 0) hipLaunchKernelGGL((cspn_grad_tail<K, DT, WT, 0>), dim3(grid), dim3(TAIL_BLOCK), 0, st, a);
+    else if (variant == 2) hipLaunchKernelGGL((cspn_grad_tail<K, DT, WT, 2>), dim3(grid), dim3(TAIL_BLOCK), 0, st, a);
+    else if constexpr (K == 3) hipLaunchKernelGGL((cspn_grad_tail<3, DT, WT, 1>), dim3(grid), dim3(TAIL_BLOCK), 0, st, a);
     else return fail("backward tail variant %d unsupported for K=%d", variant, K);
     HIP_OK(hipGetLastError());
     return 1;
@@ -853,9 +800,6 @@ int cspn3_backward_tail(const void* d0, const void* dhist, const float* g_T, con
                         void* grad_guidance, float* gd0, int dtype, int B, int H, int W, int T, cspn_stream_t stream) {
     if (!d0 || !g_T || !guidance || !s || !grad_guidance || !gd0 || (T > 1 && !dhist) || (T > 0 && !ghist))
         return fail("cspn3_backward_tail: NULL pointer");
-#if !CSPN_TAIL_REBUILD_W
-    if (!w8) return fail("cspn3_backward_tail: this build reads the tap volume (CSPN_TAIL_REBUILD_W=0): w8 is required");
-#endif
     TailArgs a{};
     a.d0 = d0; a.dhist = dhist; a.g_T = g_T; a.ghist = ghist; a.sparse = sparse; a.w = w8; a.S = s; a.guidance = guidance;
     a.gout = grad_guidance; a.gd0 = gd0; a.g_bs = bs; a.g_cs = cs; a.B = B; a.H = H; a.W = W; a.T = T; a.C = C;

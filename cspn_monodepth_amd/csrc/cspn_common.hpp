@@ -24,9 +24,8 @@ int resident_pac3_f32(const void* guided, const void* x0, const void* sparse, vo
                       int nslots, const cspn_resident_plan* plan, void* stream);
 // cspnk_d2.hip: the K = 5 fp16 form with the state packed as fp16 pairs in LDS and v_dot2_f32_f16 steps (launched by cspnk_forward_resident)
 int kres_d2_row_stride(int wo);
-size_t kres_d2_lds_bytes(int dr, int ls, int threads, int npf);
-int kres_d2_prefetch_channels(int dr, int ls, int threads, int rounds);      // guidance channels staged through LDS (0 or 8)
-int kres_d2_launch(const void* kres_args, int threads, int grid, size_t lds_bytes, int blend, int mode, int clean, int npf, void* stream);   // mode 0 plain, 1 scored, 2 history
+size_t kres_d2_lds_bytes(int dr, int ls, int threads);
+int kres_d2_launch(const void* kres_args, int threads, int grid, size_t lds_bytes, int blend, int mode, int clean, void* stream);   // mode 0 plain, 1 scored, 2 history
 // pac_conv2d_s2.hip: the pixel-adaptive convolution and its gradients for stride 2 x 2, dilation 1, K in {3, 5}, padding K / 2,
 // W % 8 == 0 (launched by the cspn_pac_conv2d* entry points of pac_conv2d.hip when every base pointer is 16-byte aligned)
 struct PacS2Args {
@@ -133,11 +132,10 @@ __device__ __forceinline__ float4 sgn4(float4 v) { return make_float4(sgnf(v.x),
 // quotients (it divides the weighted SUM by S every step, CSPN_new.py:124-127), so neither rounding is "the" reference
 // one: measured against it on full frames the refined depth moves from 4.6e-7 to 5.7e-7 max relative error (bar: 1e-5)
 // while the derive launch loses 9 us of division sequences (v_div_scale / v_div_fmas / v_div_fixup + two residual
-// corrections per quotient: 43 operations, kept below under CSPN_IEEE_NORMALISE for A/B runs).
+// corrections per quotient: 43 operations, kept as tools/probes/ieee_normalise.patch for A/B runs).
 // S = 0 (all gates zero, also every padding pixel) needs no branch: rcp(0) = inf, the Newton step makes it NaN and
 // 0 * NaN = NaN = 0 / 0.  Only a denormal-range or huge S — where v_rcp_f32 flushes — takes the true division.
 __device__ __forceinline__ void div8_shared_reciprocal(const float (&a)[8], float S, float (&q)[8]) {
-#ifndef CSPN_IEEE_NORMALISE
     const bool okr = (S <= 0x1p+100f) && (S >= 0x1p-100f || S == 0.f);
     if (okr) {
         float r = __builtin_amdgcn_rcpf(S);
@@ -149,28 +147,14 @@ __device__ __forceinline__ void div8_shared_reciprocal(const float (&a)[8], floa
 #pragma unroll
         for (int k = 0; k < 8; ++k) q[k] = a[k] / S;
     }
-#else
-    // bit-identical to IEEE division: the compiler's fp32 division sequence with the divisor-only part shared
-    bool fast = (S >= 0x1p-60f) && (S <= 0x1p+60f);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) fast = fast && (a[k] == 0.f || a[k] >= S * 0x1p-40f);
-    if (fast) {
-        float r = __builtin_amdgcn_rcpf(S);
-        const float e = fmaf(-S, r, 1.0f);
-        r = fmaf(e, r, r);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float qq = a[k] * r;
-            const float e2 = fmaf(-S, qq, a[k]);
-            qq = fmaf(e2, r, qq);
-            const float e3 = fmaf(-S, qq, a[k]);
-            q[k] = fmaf(e3, r, qq);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) q[k] = a[k] / S;
-    }
-#endif
+}
+// The reciprocal of that recipe on its own: 1 / S refined by one Newton step, with the true division outside [2^-100, 2^100] unless
+// S is 0 — what the reverse sweep (cspn3_resident MODE 4) and the guard (cspn_repair.hip) multiply |g_j| by to rebuild the forward's gates.
+__device__ __forceinline__ float reciprocal_as_forward(float S) {
+    const bool okr = (S <= 0x1p+100f) && (S >= 0x1p-100f || S == 0.f);
+    float r = __builtin_amdgcn_rcpf(S);
+    r = fmaf(fmaf(-S, r, 1.0f), r, r);
+    return okr ? r : 1.0f / S;
 }
 // The same for the four pixels of a quad, in place (w[k][e]: gate k of pixel e -> its quotient), with the true division behind ONE
 // wave-uniform test (a ballot over the wavefront) per quad.  In the per-pixel form above the compiler gives each of the 8 quotients
@@ -188,7 +172,6 @@ __device__ __forceinline__ float reciprocal_newton(float S) {
     return fmaf(e, r, r);
 }
 __device__ __forceinline__ void div8_quad_shared_reciprocal(float (&w)[8][4], const float (&S)[4], bool keep = true) {
-#ifndef CSPN_IEEE_NORMALISE
     float r[4];
     bool okr[4], bad = false;
 #pragma unroll
@@ -208,17 +191,6 @@ __device__ __forceinline__ void div8_quad_shared_reciprocal(float (&w)[8][4], co
 #pragma unroll
             for (int k = 0; k < 8; ++k) w[k][e] *= r[e];
     }
-#else
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float av[8], qv[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) av[k] = w[k][e];
-        div8_shared_reciprocal(av, S[e], qv);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) w[k][e] = keep ? qv[k] : 0.f;
-    }
-#endif
 }
 
 // exp(x) for x <= 0 (the max-subtracted logits) on the hardware exponential: v_exp_f32 is 2^t to 1 ulp; the product
@@ -322,19 +294,16 @@ template <> struct Taps<__half> {
     }
 };
 
-#ifndef CSPN_DPP_BOUND_CTRL
-#define CSPN_DPP_BOUND_CTRL true
-#endif
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef const volatile __attribute__((address_space(3))) v4f* lds_cv4f_ptr;   // LDS (addrspace 3) volatile b128
 
 // Wavefront-level halo exchange: value held by lane-1 / lane+1 (DPP wave shift, VALU only).  Lanes without
 // a source (0 / 63) or with an exec-masked source get 0 (bound_ctrl) and are patched from LDS by the caller.
 __device__ __forceinline__ float dpp_from_prev_lane(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, CSPN_DPP_BOUND_CTRL));
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, true));
 }
 __device__ __forceinline__ float dpp_from_next_lane(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, CSPN_DPP_BOUND_CTRL));
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, true));
 }
 
 // Sum of v over the 64 lanes of a wavefront, valid in lane 63.  VALU only (DPP row shifts + the gfx9 row broadcasts):

@@ -23,10 +23,7 @@
 
 namespace {
 
-#ifndef CSPN_MAX8_ROWS
-#define CSPN_MAX8_ROWS 6
-#endif
-constexpr int M8_R = CSPN_MAX8_ROWS;          // rows per lane
+constexpr int M8_R = 6;                       // rows per lane
 constexpr int M8_WAVES = 8;
 constexpr int M8_THREADS = 64 * M8_WAVES;     // 512: two wavefronts per SIMD, up to 256 VGPRs each
 constexpr int M8_REGION = 64;                 // region width = the 64 lanes

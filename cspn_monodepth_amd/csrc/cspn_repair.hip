@@ -32,14 +32,6 @@ struct RepArgs {
     int B, H, W, Wv, T, tiles_x, tiles_y;
 };
 
-// the forward's refined reciprocal of the normaliser (div8_shared_reciprocal's recipe), as cspn3_resident MODE 4 forms it
-__device__ __forceinline__ float rcp_as_forward(float S) {
-    const bool okr = (S <= 0x1p+100f) && (S >= 0x1p-100f || S == 0.f);
-    float r = __builtin_amdgcn_rcpf(S);
-    r = fmaf(fmaf(-S, r, 1.0f), r, r);
-    return okr ? r : 1.0f / S;
-}
-
 // MODE 0: inference (refined depth -> out).  MODE 1: inference with the depth metrics fused — the launch that gave up has scored the
 // tiles that finished and poisoned the others, so the re-computation adds the metric terms of exactly the pixels it finds poisoned
 // (summation order differs from the fused epilogue's: the sums agree to ~1e-7, the refined depth to the bit).  MODE 2: the training forward — every step's state goes to its history plane, the
@@ -97,7 +89,7 @@ __global__ __launch_bounds__(REP_THREADS) void cspn3_resident_repair(const RepAr
                         for (int j = 0; j < 8; ++j) {
                             const int lin = j < 4 ? j : j + 1, yy = y + lin / 3 - 1, xx = x + lin % 3 - 1;
                             const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < Wv;
-                            const float rs = ok ? rcp_as_forward(sib[(size_t)yy * W + xx]) : 0.f;
+                            const float rs = ok ? reciprocal_as_forward(sib[(size_t)yy * W + xx]) : 0.f;
                             qv[j] = fabsf(gb[(size_t)j * a.g_cs + (size_t)y * W + x]) * rs;
                         }
                     } else if (TRANS) {

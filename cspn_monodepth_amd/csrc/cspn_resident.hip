@@ -115,32 +115,21 @@ __device__ __forceinline__ void st4(gptr p, float4 v) {
 // written once and read by a LATER kernel: stored non-temporally they do not push the guidance / exchange lines out of the L2
 // while the launch runs, and the tail that streams them afterwards runs faster as well — same-box A/B, two alternating
 // repetitions: tail 95.2-97.1 -> 86.8-87.3 us, sparse training forward 69.7-70.3 -> 64.9-65.4, sparse reverse sweep 75.4-76.9 ->
-// 72.4-73.7, the plain forward / sweep -0 / -1.4 us (-DCSPN_RES_HIST_NT=0 for A/B).
-#ifndef CSPN_RES_HIST_NT
-#define CSPN_RES_HIST_NT 1
-#endif
+// 72.4-73.7, the plain forward / sweep -0 / -1.4 us (the other side of the A/B: the plain store of st4 above).
+__device__ __forceinline__ void st4_hist(gptr p, float4 v) {
+    const v4f w = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(w, reinterpret_cast<GLB v4f*>(p));
+}
 // Round 6, measured and NOT the default (NEGATIVE_RESULTS #53-#55; profiles/r06_step_pipe_ab.txt): the step's LDS round trips.  A step is
 //   barrier -> ds_read of the two halo rows -> wait -> DPP of all rows -> exec-masked ds_read of the strip-end lanes' columns -> wait -> FMAs
 //   -> ds_write -> wait -> barrier:  two LDS read latencies in series behind every barrier.
-// -DCSPN_RES_STEP_PIPE=1 takes the own rows' neighbour columns (DPP: registers of the neighbouring lanes, no LDS) BEFORE the barrier, from the rows
+// tools/probes/res_step_pipe.patch takes the own rows' neighbour columns (DPP: registers of the neighbouring lanes, no LDS) BEFORE the barrier, from the rows
 // just computed, in the shadow of the ds_write latency, and issues EVERY LDS read of the step right behind the barrier (the halo rows' strip-end
 // columns into temporaries, merged with one select after the halo rows' DPP): one read latency instead of two, bit-identical — and SLOWER on every
-// shape (config 2 +1.6 us, shards +1.0 / +1.2 us).  The two perf-only experiments below say why nothing of this kind can pay: without ANY
+// shape (config 2 +1.6 us, shards +1.0 / +1.2 us).  The two perf-only experiments of tools/probes/res_step_bounds.patch (wrong results, timing only) say why nothing of this kind can pay: without ANY
 // strip-end read the forward is no faster (+-0.3 us), and without ANY step barrier it gains 2.3 us at config 2, 0.4 us at NYU B = 3, 1.4 us at
 // KITTI B = 1 — the step is bound by VALU issue (one instruction per wavefront every ~5 cycles, 2.5 per SIMD with its two wavefronts:
 // tools/probes/vgpr_bank_probe.hip), not by its barrier or its LDS latency, so "two steps per barrier" (+20..100 % FMAs for half of that) loses.
-#ifndef CSPN_RES_STEP_PIPE
-#define CSPN_RES_STEP_PIPE 0
-#endif
-#ifndef CSPN_RES_PUBLISH_ALL
-#define CSPN_RES_PUBLISH_ALL 1      // 0: only the quads a neighbour will read are published — 6 MB less traffic per forward at config 2 but
-                                    // NOT faster (same-box A/B, profiles/r05_publish_ab.txt: 48.0 vs 47.8 us, sparse 53.9 vs 53.1): kept for A/B runs
-#endif
-__device__ __forceinline__ void st4_hist(gptr p, float4 v) {
-    const v4f w = {v.x, v.y, v.z, v.w};
-    if (CSPN_RES_HIST_NT) __builtin_nontemporal_store(w, reinterpret_cast<GLB v4f*>(p));
-    else *reinterpret_cast<GLB v4f*>(p) = w;
-}
 __device__ __forceinline__ float4 ld4_dev(gptr p) {
     const unsigned long long lo = __hip_atomic_load(reinterpret_cast<const GLB unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long hi = __hip_atomic_load(reinterpret_cast<const GLB unsigned long long*>(p) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -224,7 +213,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
 
     const int tid = threadIdx.x;
     const int tiles_per_img = a.tiles_x * a.tiles_y;
-    // A launch may hold several ROUNDS of nb images (-DCSPN_RES_ONE_LAUNCH=1; by default a launch is one round): rounds x (nb x tiles)
+    // A launch may hold several ROUNDS of nb images (RES_ROUNDS_PER_LAUNCH; the host launches one round at a time): rounds x (nb x tiles)
     // workgroups, round 0's — images b0 .. b0 + nb - 1, at most one workgroup per CU — resident at once, those of round r + 1 dispatched
     // in blockIdx order as round r's finish.  Flags and exchange planes are per image, so the rounds share nothing.  (cspnk_resident's
     // reverse sweep runs that way: cspnk_resident.hip.)
@@ -453,17 +442,11 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
         for (int m = 0; m < NQ + 2; ++m) {
             const int ys = yq0 - 1 + m;
             const bool v = x_in && ys >= 0 && ys < H;
-            auto rcp_fwd = [](float S) -> float {
-                const bool okr = (S <= 0x1p+100f) && (S >= 0x1p-100f || S == 0.f);
-                float r = __builtin_amdgcn_rcpf(S);
-                r = fmaf(fmaf(-S, r, 1.0f), r, r);
-                return okr ? r : 1.0f / S;
-            };
 #pragma unroll
-            for (int e = 0; e < 4; ++e) srow[m][e] = (v && e < nval) ? rcp_fwd(srow[m][e]) : 0.f;
+            for (int e = 0; e < 4; ++e) srow[m][e] = (v && e < nval) ? reciprocal_as_forward(srow[m][e]) : 0.f;
             const float nl = dpp_from_prev_lane(srow[m][3]), nr = dpp_from_next_lane(srow[m][0]);
-            srow[m][4] = fix_left ? ((v && xq >= 1) ? rcp_fwd(srow[m][4]) : 0.f) : nl;
-            srow[m][5] = fix_right ? ((v && xq + 4 < a.Wv) ? rcp_fwd(srow[m][5]) : 0.f) : nr;
+            srow[m][4] = fix_left ? ((v && xq >= 1) ? reciprocal_as_forward(srow[m][4]) : 0.f) : nl;
+            srow[m][5] = fix_right ? ((v && xq + 4 < a.Wv) ? reciprocal_as_forward(srow[m][5]) : 0.f) : nr;
         }
     }
 #pragma unroll
@@ -607,7 +590,6 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
     const int n_phase = (a.T + a.S - 1) / a.S;
     const int tile_global = b * tiles_per_img + trem;
     float own[NQ][4];
-    float nbl[NQ], nbr[NQ];                    // -DCSPN_RES_STEP_PIPE=1: columns xq-1 / xq+4 of the own rows as the neighbouring lanes hold them (DPP)
 
     for (int p = 0; p < n_phase; ++p) {
         const int steps = (a.T - p * a.S) < a.S ? (a.T - p * a.S) : a.S;
@@ -681,10 +663,6 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
             const v4f mid = *(lds_cv4f_ptr)(cur + drow * ls + cb);
             own[i][0] = mid.x; own[i][1] = mid.y; own[i][2] = mid.z; own[i][3] = mid.w;
         }
-        if (CSPN_RES_STEP_PIPE) {
-#pragma unroll
-            for (int i = 0; i < NQ; ++i) { nbl[i] = dpp_from_prev_lane(own[i][3]); nbr[i] = dpp_from_next_lane(own[i][0]); }
-        }
         if (BLEND && !TRANS && p == 0) {           // private slots: m -> m * d0 (own = d0 here)
 #pragma unroll
             for (int i = 0; i < NQ; ++i) {
@@ -719,44 +697,6 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
                     drow = drow < dr ? drow : dr - 1;
                     return rd + drow * ls + cb;
                 };
-                if (CSPN_RES_STEP_PIPE) {
-                    // every LDS read of the step is issued right behind the barrier: the two halo rows' quads, then — exec-masked, strip-end /
-                    // wave-edge lanes only — the own rows' neighbour columns (straight into the window, over the DPP values taken before the
-                    // barrier) and the halo rows' (into temporaries: the DPP of a halo row has to wait for its quad, the read need not)
-                    v4f hq[2 * R];
-                    float tl[2 * R], tr[2 * R];
-#pragma unroll
-                    for (int h = 0; h < 2 * R; ++h) {
-                        hq[h] = *(lds_cv4f_ptr)(row_ptr(h < R ? h : NQ + h));
-                        tl[h] = 0.f; tr[h] = 0.f;
-                    }
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i) {
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) win[i + R][R + c] = own[i][c];
-                        win[i + R][0] = nbl[i]; win[i + R][5] = nbr[i];
-                    }
-                    if (fix_left) {
-#pragma unroll
-                        for (int i = 0; i < NQ; ++i) win[i + R][0] = row_ptr(i + R)[-1];
-#pragma unroll
-                        for (int h = 0; h < 2 * R; ++h) tl[h] = row_ptr(h < R ? h : NQ + h)[-1];
-                    }
-                    if (fix_right) {
-#pragma unroll
-                        for (int i = 0; i < NQ; ++i) win[i + R][5] = row_ptr(i + R)[4];
-#pragma unroll
-                        for (int h = 0; h < 2 * R; ++h) tr[h] = row_ptr(h < R ? h : NQ + h)[4];
-                    }
-#pragma unroll
-                    for (int h = 0; h < 2 * R; ++h) {
-                        const int rr = h < R ? h : NQ + h;
-                        win[rr][1] = hq[h].x; win[rr][2] = hq[h].y; win[rr][3] = hq[h].z; win[rr][4] = hq[h].w;
-                        const float dl = dpp_from_prev_lane(hq[h].w), dr2 = dpp_from_next_lane(hq[h].x);
-                        win[rr][0] = fix_left ? tl[h] : dl;
-                        win[rr][5] = fix_right ? tr[h] : dr2;
-                    }
-                } else {
 #pragma unroll
                 for (int rr = 0; rr < NQ + 2 * R; ++rr) {
                     float m4[4];
@@ -775,22 +715,13 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
                 }
                 // strip-end / wave-edge lanes patch their halo column from LDS: exec-masked ds_read straight into the window
                 // registers (a merged block with selects costs 28 v_mov per step and measured 7 % slower)
-#ifdef CSPN_RES_EXPERIMENT_NOFIX      // perf experiment ONLY (wrong results): what do the masked 4-byte reads cost?
-                if (false) {
-#else
                 if (fix_left) {
-#endif
 #pragma unroll
                     for (int rr = 0; rr < NQ + 2 * R; ++rr) win[rr][0] = row_ptr(rr)[-1];
                 }
-#ifdef CSPN_RES_EXPERIMENT_NOFIX
-                if (false) {
-#else
                 if (fix_right) {
-#endif
 #pragma unroll
                     for (int rr = 0; rr < NQ + 2 * R; ++rr) win[rr][5] = row_ptr(rr)[4];
-                }
                 }
 #pragma unroll
                 for (int i = 0; i < NQ; ++i) {
@@ -840,17 +771,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
                 }
             }
             if (HIST) hist_step += plane;
-            if (CSPN_RES_STEP_PIPE && !FINAL && decltype(on_c)::value) {
-                // the next step's neighbour columns of the own rows, in the shadow of the ds_write latency (pinned in front of the barrier)
-#pragma unroll
-                for (int i = 0; i < NQ; ++i) {
-                    nbl[i] = dpp_from_prev_lane(own[i][3]); nbr[i] = dpp_from_next_lane(own[i][0]);
-                    asm volatile("" : "+v"(nbl[i]), "+v"(nbr[i]));
-                }
-            }
-#ifndef CSPN_RES_EXPERIMENT_NOBARRIER  // perf experiment ONLY (wrong results): what do the step barriers cost?
             if (!FINAL) __syncthreads();
-#endif
         };
         stamp();                               // depth staged
         const int plain_steps = last_phase ? steps - 1 : steps;
@@ -882,28 +803,16 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
                 // registers the step loop needs — they would be spilled and reloaded from scratch every phase)
                 unsigned o0 = (unsigned)(yq0L * W + xqL);
                 asm volatile("" : "+v"(o0));
-                // -DCSPN_RES_PUBLISH_ALL=0 (round 5 experiment, not faster): only what a neighbour will READ is published — the columns / rows of this
+                // Every interior quad is published.  tools/probes/res_publish_borders_only.patch (round 5 experiment): only what a neighbour
+                // will READ is published — the columns / rows of this
                 // tile that lie inside an adjacent tile's depth region (its weight region + the 1-pixel ring), worked out from the
                 // neighbours' region origins exactly as they work them out themselves.  Corner neighbours read the intersection of
                 // a column band and a row band, so the union of the four bands covers all eight.  At config 2 that is 57 % of the
-                // interior quads: fewer device-scope stores to wait for before the flag, 6 MB less write traffic per forward.
-#if !CSPN_RES_PUBLISH_ALL
-                auto reg_x0 = [&](int t) { return res_region_x0(t, a.tw, a.hxw, wq, W, true); };
-                auto reg_y0 = [&](int t) { return res_region_y0<UNEVEN>(t, a.th0, a.th, a.hyw, wr, H, true); };
-                const int pubL = tx > 0 ? reg_x0(tx - 1) + 4 * wq + 1 : -(1 << 30);            // columns x < pubL are read by the tiles on the left
-                const int pubR = tx + 1 < a.tiles_x ? reg_x0(tx + 1) - 1 : (1 << 30);          // columns x >= pubR by the tiles on the right
-                const int pubT = ty > 0 ? reg_y0(ty - 1) + wr + 1 : -(1 << 30);                // rows y < pubT by the tiles above
-                const int pubB = ty + 1 < a.tiles_y ? reg_y0(ty + 1) - 1 : (1 << 30);          // rows y >= pubB by the tiles below
-                const bool col_read = (xqL < pubL) || (xqL + 3 >= pubR);
-#endif
+                // interior quads: fewer device-scope stores to wait for before the flag, 6 MB less write traffic per forward — but
+                // NOT faster (same-box A/B, profiles/r05_publish_ab.txt: 48.0 vs 47.8 us, sparse 53.9 vs 53.1).
 #pragma unroll
                 for (int i = 0; i < NQ; ++i) {
-#if !CSPN_RES_PUBLISH_ALL
-                    const bool read = col_read || (yq0L + i < pubT) || (yq0L + i >= pubB);
-#else
-                    const bool read = true;
-#endif
-                    if (((interior >> i) & 1u) && read) st4_dev(xout, o0 + (unsigned)(i * W), own[i][0], own[i][1], own[i][2], own[i][3]);
+                    if ((interior >> i) & 1u) st4_dev(xout, o0 + (unsigned)(i * W), own[i][0], own[i][1], own[i][2], own[i][3]);
                 }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this thread's device-scope stores have landed
@@ -1005,15 +914,12 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
 // ------------------------------------------------------------------------------------------------ host side
 constexpr int RES_MAX_NQ = 5;
 
-constexpr int RES_MAX_ROUNDS = 8;       // rounds of images_per_launch images in one launch (-DCSPN_RES_ONE_LAUNCH=1)
-// Rounds in one launch: measured, NOT the default (same box, three alternating passes, profiles/r05_rounds_ab.txt): KITTI B = 8 (2 rounds of
+// Rounds of images_per_launch images in one launch: the kernel takes any number (the A/B ran 8), the host loop launches one.  Measured, NOT the default (same box, three alternating passes, profiles/r05_rounds_ab.txt): KITTI B = 8 (2 rounds of
 // 4 images on 256 workgroups) 92.4-93.4 us per scored forward against 92.2-93.7 with one launch per round, NYU B = 48 91.7-92.1 against
 // 90.4-90.9 (slower), only a ragged third round gains (KITTI B = 9: 121-123 against 126-127).  A round-1 workgroup starts when a CU is freed,
 // but its neighbours start as scattered as round 0's workgroups finish: the neighbour waits pay what the drain and the launch gap cost.
 // The K = 5 reverse sweep (cspnk_resident.hip) does gain (2 x 45.7 + gap -> 88.5 us) and runs its rounds in one launch.
-#ifndef CSPN_RES_ONE_LAUNCH
-#define CSPN_RES_ONE_LAUNCH 0
-#endif
+constexpr int RES_ROUNDS_PER_LAUNCH = 1;
 struct ResGeom {
     int S, tiles_x, tiles_y, tw, th, nq, wq, wr, hxw, hyw, dr, ls;
     int imgs_per_launch, launches;
@@ -1043,16 +949,12 @@ size_t res_lds_bytes(int dr, int ls, int nq, int blend, int threads = RES_THREAD
     return ((size_t)RES_PP + (size_t)dr * ls + (size_t)(blend ? 1 : 0) * threads * nq * 4 + 16 * 10) * sizeof(float);
 }
 
-// Row stride (floats) of a depth buffer in LDS: 4 wq + 8 at least ([4 pad incl. ring][wq quads][ring + pad]).  Round 5 (-DCSPN_RES_LS_SWIZZLE=0
-// for A/B; same-box, profiles/r05_swizzle_ab.txt: NYU B = 3 20.8 -> 20.1 us per scored forward, the other shapes within noise): the smallest such stride for which the next strip of a thread column (NQ rows further down) continues the bank
+// Row stride (floats) of a depth buffer in LDS: 4 wq + 8 at least ([4 pad incl. ring][wq quads][ring + pad]).  Round 5 (against
+// the plain 4 wq + 8; same-box, profiles/r05_swizzle_ab.txt: NYU B = 3 20.8 -> 20.1 us per scored forward, the other shapes within noise): the smallest such stride for which the next strip of a thread column (NQ rows further down) continues the bank
 // sequence of this one inside a wavefront — NQ ls = 4 wq (mod 64 dwords) — so that the 16 lanes of a ds_read_b128 / ds_write_b128
 // pass that straddle two strips do not share banks (SQ counters of round 4: 16.5 % of the LDS cycles were bank conflicts).
-#ifndef CSPN_RES_LS_SWIZZLE
-#define CSPN_RES_LS_SWIZZLE 1
-#endif
 int res_row_stride(int wq, int nq, int dr) {
     const int lo = 4 * wq + 8;
-    if (!CSPN_RES_LS_SWIZZLE) return lo;
     for (int cand = lo; cand < lo + 64; cand += 4)
         if ((((nq * cand - 4 * wq) % 64) + 64) % 64 == 0 && (size_t)dr * cand <= (size_t)RES_PP) return cand;
     return lo;
@@ -1410,9 +1312,9 @@ int resident_launch(const void* guidance, long bs, long cs, const void* d0, cons
         }
     }
     if (!launch) return fail("cspn3_forward_resident: %d-thread workgroups serve the inference forms only", g.threads);
-    // one launch per round of images_per_launch images (-DCSPN_RES_ONE_LAUNCH=1: per RES_MAX_ROUNDS rounds — measured, not faster: see there)
+    // one launch per RES_ROUNDS_PER_LAUNCH rounds of images_per_launch images (more than one round: measured, not faster: see there)
     const int ipl = g.imgs_per_launch < B ? g.imgs_per_launch : B;
-    const int max_rounds = CSPN_RES_ONE_LAUNCH ? RES_MAX_ROUNDS : 1;
+    constexpr int max_rounds = RES_ROUNDS_PER_LAUNCH;
     for (int b0 = 0; b0 < B; b0 += ipl * max_rounds) {
         a.b0 = b0;
         a.nb = (B - b0) < ipl ? (B - b0) : ipl;

@@ -31,27 +31,21 @@ typedef const volatile __attribute__((address_space(3))) unsigned* lds_cu_ptr;
 //  cspnk_helpers.hpp: the guard's re-computation of this kernel, csrc/cspn_repair.hip, uses the same code and so produces the same bits)
 
 constexpr int D2_R = 2, D2_NT = 24;
-constexpr int D2_NPF = 8;           // guidance channels of a round that are staged through LDS (a third of the 24)
-#ifndef CSPN_D2_PREFETCH
-#define CSPN_D2_PREFETCH 0          // round 6, BUILT, measured and NOT the default (NEGATIVE_RESULTS #57): see cspnk_d2's NPF
-#endif
-#ifndef CSPN_D2_DPP_HALO
-#define CSPN_D2_DPP_HALO 0          // round 6, measured and NOT the default (1 for A/B): see the step
-#endif
 
 // MODE 0: inference; 1: inference + fused depth metrics; 2: the training forward — every step's state goes to its fp16 history
 // plane and the softmax taps are published once as the fp16 tap volume (pairs (2i, 2i+1) interleaved per quad: cspn_common.hpp
 // Taps<__half>) that cspn_transpose_kernel / cspn_grad_tail<5, __half, __half> stream in the backward.
-// NPF (round 6; 0 or D2_NPF): the first NPF guidance channels of a round reach the registers THROUGH LDS (global_load_lds_dwordx4: no
+// Guidance prefetch (round 6, BUILT, measured and NOT the default, NEGATIVE_RESULTS #57; tools/probes/d2_prefetch.patch): the first 8
+// guidance channels of a round reach the registers THROUGH LDS (global_load_lds_dwordx4: no
 // destination registers) — and those of round r + 1 are requested as soon as round r's taps are derived, so that they stream while round
 // r's steps run (VALU-bound, the memory system idle) instead of in front of round r + 1's softmax.  Round 4 priced this (NEGATIVE_RESULTS
 // #35: "40 % of the region fits the free LDS ... a second staging protocol"); round 4's register form of the idea spilled (#38).
-// BUILT in round 6 (-DCSPN_D2_PREFETCH=1: a third of the guidance, 96 KB per workgroup; parity suite green, same bits) and SLOWER: 69.9 ->
+// BUILT in round 6 (a third of the guidance, 96 KB per workgroup; parity suite green, same bits) and SLOWER: 69.9 ->
 // 72.6 us per scored forward (profiles/r06_d2_prefetch_ab.txt).  The in-kernel stamps of the second round say why (r06_d2_prefetch_stamps.txt):
 // parked + derive + the barrier behind them 11.1 us without, 11.6 us with the prefetch — what a round spends in front of its steps is NOT
 // the guidance stream but the softmax itself, 192 v_exp_f32 per thread at a quarter of the VALU rate with three wavefronts per SIMD taking
 // turns (the loads hide under the other wavefronts' exponentials); the staging through LDS only adds instructions and 5 spilled registers.
-template <int BLEND, int MODE, int CLEAN, int NTH, int NPF>
+template <int BLEND, int MODE, int CLEAN, int NTH>
 __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_d2(const KResArgs a) {
     constexpr int R = D2_R, NT = D2_NT;
     constexpr bool SCORE = MODE == 1, HIST = MODE == 2;
@@ -92,29 +86,22 @@ __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_d2(const KResArgs a) {
     const bool exch = a.T > a.S;
     const int rx0 = max(exch ? max(0, x0 - a.tw) : 0, min(x0 - a.hxw, W - 8 * wo));
     const int ry0 = max(exch ? max(0, y0 - a.th) : 0, min(y0 - a.hyw, H - wr));
-    // ... and the region row it owns.  -DCSPN_D2_HALO_ROWS_FIRST (an experiment that did not pay): the HALO rows (above
-    // and below the tile) come first in thread order, the tile's own rows after them; the last step of a phase is only needed on
+    // ... and the region row it owns.  tools/probes/d2_halo_rows_first.patch (an experiment that did not pay): the HALO rows
+    // (above and below the tile) come first in thread order, the tile's own rows after them; the last step of a phase is only needed on
     // the tile's rows (the halo is re-staged from the neighbours, or the forward is over), so the wavefronts that own nothing but
     // halo rows sit it out — at config 3 the 12 halo rows are the first four wavefronts, one per SIMD.  The step phases shrink
     // (4.22 -> 3.74 us) but the neighbour waits grow by as much: 71.3-72.3 vs 72.0-72.5 us per forward, B = 3 29.4 vs 28.5 us.
+    // (Only that patch reads the next two values.  They stay: dead as they are, the compiler allocates every instance's scalar registers
+    // differently without them, and this kernel's instruction stream is the measured one.)
     const int i0 = y0 - ry0;                                // first tile row inside the region
     const int th_in = min(a.th, ry0 + wr - y0);             // tile rows inside the region (the last tile may be cut short)
-#ifdef CSPN_D2_HALO_ROWS_FIRST
-    const int nh = wr - th_in;
-    const int sy = sp >= wr ? sp : (sp < nh ? (sp < i0 ? sp : sp + th_in) : i0 + (sp - nh));
-#else
     const int sy = sp;
-#endif
     const int xo = rx0 + 8 * sx;
     const int yo = ry0 + sy;
     const bool active = sy < wr;
     const bool in_img = active && xo < W && yo < H;        // W % 8 == 0: an oct is inside the image or outside as a whole
     const bool interior = in_img && yo >= y0 && yo < y0 + a.th && xo >= x0 && xo < x0 + a.tw;
     const unsigned off_own = in_img ? (unsigned)(yo * W + xo) : 0u;
-#if CSPN_D2_DPP_HALO
-    const bool fix_left = (sx == 0) || ((tid & 63) == 0), fix_right = (sx == wo - 1) || ((tid & 63) == 63);
-    const int colL = fix_left ? 4 * (sx + 1) - 1 : 0, colR = fix_right ? 4 * (sx + 1) + 4 : 0;      // dword 0 of a row: padding, one address per row
-#endif
 
     // LDS: two depth buffers of dr rows x ls dwords; a row is [3 pad][ring pair][wo octs x 4 dwords][ring pair][pad]: oct k at
     // dword 4 (k + 1) (16-byte aligned), the pixel pair left of the row at dword 3, the pair right of it at dword 4 (wo + 1)
@@ -123,17 +110,6 @@ __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_d2(const KResArgs a) {
     const int yd0 = ry0 - R;
     const int step_r = NTH / wo, step_q = NTH - step_r * wo;
     const int n_phase = (a.T + a.S - 1) / a.S;
-    // the prefetch area: behind the two depth buffers and the scoring's partial sums, [NPF channels][NTH lanes] x 16 bytes — lane l of
-    // wavefront w finds channel c of its own oct at slot c * NTH + 64 w + l (the DMA writes M0 + 16 x lane: a wavefront reads what it wrote)
-    unsigned* const pf_lds = ldsu + ((2 * pp + (NTH / 64) * 10 + 16 + 3) & ~3);
-    const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
-    auto prefetch = [&](int bimg, unsigned off) __attribute__((always_inline)) {
-        const __half* __restrict__ gbn = kuniform_ptr(static_cast<const __half*>(a.g) + (size_t)bimg * NT * HW);
-#pragma unroll
-        for (int c = 0; c < NPF; ++c)
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const GLB void*>(atb(gbn, ((unsigned)c * HW + off) * 2u)),
-                                             (__attribute__((address_space(3))) void*)(pf_lds + (c * NTH + wave_u * 64) * 4), 16, 0, 0);
-    };
 
     for (int round = 0; round < a.rounds; ++round) {
         const int b = a.b0 + round * a.nb + bl;
@@ -181,9 +157,8 @@ __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_d2(const KResArgs a) {
         // 64-bit pairs, spilled, and every scratch reload between the loads waits for the whole in-order stream)
         unsigned off_r = off_own;
         asm volatile("" : "+v"(off_r));
-        if (NPF > 0 && round == 0) prefetch(b, off_r);        // (later rounds: requested during the previous round's steps)
 #pragma unroll
-        for (int c = NPF; c < NT; ++c) graw[c] = ld16(atb(gb, ((unsigned)c * HW + off_r) * 2u));
+        for (int c = 0; c < NT; ++c) graw[c] = ld16(atb(gb, ((unsigned)c * HW + off_r) * 2u));
         // sparse blend operands of the owned oct, behind the guidance
         Oct spo, x0o;
         if (BLEND) { spo = IO::ld_oct(spb, off_r); x0o = IO::ld_oct(x0b, off_r); }
@@ -224,14 +199,6 @@ __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_d2(const KResArgs a) {
         stamp();                                              // depth region parked
 
         // ---- 2. softmax of the 8 owned pixels -> tap-pair registers -----------------------------------------------------
-        if (NPF > 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the DMA of this wavefront's slots has landed (the softmax needs every channel anyway)
-#pragma unroll
-            for (int c = 0; c < NPF; ++c) {
-                const v4uu v = *(lds_cv4u_ptr)(pf_lds + (c * NTH + tid) * 4);
-                graw[c] = make_uint4(v.x, v.y, v.z, v.w);
-            }
-        }
         unsigned wq[8][12];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -283,12 +250,6 @@ __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_d2(const KResArgs a) {
             }
         }
         stamp();                                              // weights derived
-        if (NPF > 0 && round + 1 < a.rounds) {
-            // the next round's first NPF channels stream into LDS while this round's steps run (the slots were read above; a workgroup's
-            // next image is b + nb, same tile, same offsets).  The phase boundaries' s_waitcnt vmcnt(0) also wait for them.
-            const int bn = b + a.nb;
-            if (bn < a.B) prefetch(bn, off_r);
-        }
 
         // ---- 3. phases of S steps; between phases the tile borders travel through the exchange planes --------------------
         __half* __restrict__ outb = HIST ? nullptr : kuniform_ptr(static_cast<__half*>(a.out) + (size_t)b * HW);
@@ -384,23 +345,14 @@ __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_d2(const KResArgs a) {
                     const unsigned* rowp = rd + drow * ls + 4 * (sx + 1);
                     unsigned D[6], U[5];
                     const v4uu d4 = *(lds_cv4u_ptr)(rowp);
-#if CSPN_D2_DPP_HALO
-                    // the pixel pairs left / right of the oct are the neighbouring lanes' d4.w / d4.x (DPP wave shift: VALU, no LDS); only the
-                    // strip-end / wave-edge lanes need LDS, and every other lane reads one dword per region row there (a broadcast) — the two
-                    // 4-byte reads per lane at a 16-byte stride are 4-way bank conflicts: 54 % of this kernel's LDS cycles (profiles/r05_sq_pac5.json).
-                    // MEASURED (NEGATIVE_RESULTS #56): SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.539 -> 0.059, LDS cycles halved — and the forward
+                    // The pixel pairs left / right of the oct: two 4-byte reads per lane at a 16-byte stride, 4-way bank conflicts that are 54 % of
+                    // this kernel's LDS cycles (profiles/r05_sq_pac5.json).  Taking them from the neighbouring lanes' d4.w / d4.x instead (DPP wave
+                    // shift, LDS only for the strip-end / wave-edge lanes: tools/probes/d2_dpp_halo.patch) was round 6, measured and NOT the default
+                    // (NEGATIVE_RESULTS #56): SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.539 -> 0.059, LDS cycles halved — and the forward
                     // 69.8 -> 74.4 us: the step is VALU-bound (v_dot2 / v_fma_mix issue at ~4.6 cycles), the conflicts hide under it, and the 10
                     // DPP moves + 10 selects per step are 13 % more VALU work (profiles/r06_d2_dpp_halo_ab.txt, r06_sq_pac5_dpp_halo.json)
-                    const unsigned* rowb = rd + drow * ls;
-                    const unsigned lfix = *(lds_cu_ptr)(rowb + colL), rfix = *(lds_cu_ptr)(rowb + colR);
-                    const unsigned ldpp = (unsigned)__builtin_amdgcn_update_dpp(0, (int)d4.w, 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
-                    const unsigned rdpp = (unsigned)__builtin_amdgcn_update_dpp(0, (int)d4.x, 0x130 /* wave_shl:1 */, 0xf, 0xf, true);
-                    D[0] = fix_left ? lfix : ldpp;
-                    D[5] = fix_right ? rfix : rdpp;
-#else
                     D[0] = *(lds_cu_ptr)(rowp - 1);
                     D[5] = *(lds_cu_ptr)(rowp + 4);
-#endif
                     D[1] = d4.x; D[2] = d4.y; D[3] = d4.z; D[4] = d4.w;
 #pragma unroll
                     for (int k = 0; k < 5; ++k) U[k] = __builtin_amdgcn_alignbit(D[k + 1], D[k], 16);      // pixels (2k - 1, 2k)
@@ -432,14 +384,9 @@ __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_d2(const KResArgs a) {
                 if (kind != 2 && active) *reinterpret_cast<uint4*>(wrb + (sy + R) * ls + 4 * (sx + 1)) = o;
             };
             const bool any = __ballot(active) != 0ull;       // wavefronts without a single owned row only keep the barriers company
-#ifdef CSPN_D2_HALO_ROWS_FIRST
-            const bool any_tile = __ballot(active && sy >= i0 && sy < i0 + th_in) != 0ull;      // ... without a tile row: the last step
-#else
-            const bool any_tile = any;
-#endif
             for (int s = 0; s < steps; ++s) {
                 const int kind = (s == steps - 1) ? (last_phase ? 2 : 1) : 0;
-                if (kind == 0 ? any : any_tile) step(kind, ldsu + (s & 1) * pp, ldsu + ((s + 1) & 1) * pp);
+                if (any) step(kind, ldsu + (s & 1) * pp, ldsu + ((s + 1) & 1) * pp);
                 if (HIST) hist_step += plane;
                 if (kind == 0) __syncthreads();
             }
@@ -522,10 +469,10 @@ __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_d2(const KResArgs a) {
     count_out();
 }
 
-template <int NTH, int NPF>
+template <int NTH>
 int d2_launch_nth(const KResArgs& a, int grid, size_t lds, int blend, int mode, int clean, hipStream_t st) {
 #define D2_CASE(BL, MD, CL) \
-    if (blend == BL && mode == MD && clean == CL) return launch_dynamic_lds<cspnk_d2<BL, MD, CL, NTH, NPF>>(grid, NTH, lds, st, a)
+    if (blend == BL && mode == MD && clean == CL) return launch_dynamic_lds<cspnk_d2<BL, MD, CL, NTH>>(grid, NTH, lds, st, a)
     D2_CASE(0, 0, 0); D2_CASE(0, 0, 1); D2_CASE(0, 1, 0); D2_CASE(0, 1, 1); D2_CASE(0, 2, 0); D2_CASE(0, 2, 1);
     D2_CASE(1, 0, 0); D2_CASE(1, 0, 1); D2_CASE(1, 1, 0); D2_CASE(1, 1, 1); D2_CASE(1, 2, 0); D2_CASE(1, 2, 1);
 #undef D2_CASE
@@ -548,28 +495,15 @@ int kres_d2_row_stride(int wo) {
     return best;
 }
 
-size_t kres_d2_lds_bytes(int dr, int ls, int threads, int npf) {
-    const size_t base = (((size_t)2 * dr * ls + (size_t)(threads / 64) * 10 + 16 + 3) & ~(size_t)3) * sizeof(unsigned);
-    return base + (size_t)npf * threads * 16;
+size_t kres_d2_lds_bytes(int dr, int ls, int threads) {
+    return (((size_t)2 * dr * ls + (size_t)(threads / 64) * 10 + 16 + 3) & ~(size_t)3) * sizeof(unsigned);
 }
 
-// Guidance channels that travel through LDS (cspnk_d2's NPF): D2_NPF when the launch has more than one round — only then is there a next
-// round to request early — and the prefetch area fits the 160 KB next to the depth buffers; else 0 (-DCSPN_D2_PREFETCH=0: never, for A/B).
-int kres_d2_prefetch_channels(int dr, int ls, int threads, int rounds) {
-    if (!CSPN_D2_PREFETCH || rounds < 2) return 0;
-    return kres_d2_lds_bytes(dr, ls, threads, D2_NPF) <= (size_t)160 * 1024 ? D2_NPF : 0;
-}
-
-int kres_d2_launch(const void* kres_args, int threads, int grid, size_t lds_bytes, int blend, int mode, int clean, int npf, void* stream) {
+int kres_d2_launch(const void* kres_args, int threads, int grid, size_t lds_bytes, int blend, int mode, int clean, void* stream) {
     const KResArgs& a = *static_cast<const KResArgs*>(kres_args);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (npf != 0 && npf != D2_NPF) return fail("cspnk_forward_resident (dot2 form): %d prefetched channels (0 or %d)", npf, D2_NPF);
-#if CSPN_D2_PREFETCH       // (the prefetching instances are only compiled into A/B builds)
-    if (npf && threads == 768) return d2_launch_nth<768, D2_NPF>(a, grid, lds_bytes, blend, mode, clean, st);
-    if (npf && threads == 512) return d2_launch_nth<512, D2_NPF>(a, grid, lds_bytes, blend, mode, clean, st);
-#endif
-    if (threads == 768) return d2_launch_nth<768, 0>(a, grid, lds_bytes, blend, mode, clean, st);
-    if (threads == 512) return d2_launch_nth<512, 0>(a, grid, lds_bytes, blend, mode, clean, st);
+    if (threads == 768) return d2_launch_nth<768>(a, grid, lds_bytes, blend, mode, clean, st);
+    if (threads == 512) return d2_launch_nth<512>(a, grid, lds_bytes, blend, mode, clean, st);
     return fail("cspnk_forward_resident (dot2 form): %d threads (512 or 768)", threads);
 }
 

@@ -56,15 +56,12 @@ __device__ __forceinline__ void st16(gptr p, uint4 v) {
     const v4u w = {v.x, v.y, v.z, v.w};
     *reinterpret_cast<GLB v4u*>(p) = w;
 }
-#ifndef CSPN_KRES_HIST_NT
-#define CSPN_KRES_HIST_NT 0     // A/B: 1 = non-temporal stores of the fp16 history planes / tap volume of the K x K training forms — measured
-                                // SLOWER (cspnk_d2 with history 83-85 -> 92-93 us, the transposed launches 44.4 -> 47.9 us), unlike the fp32 planes
-                                // of the 3 x 3 forms (cspn_resident.hip CSPN_RES_HIST_NT)
-#endif
+// The fp16 history planes / tap volume of the K x K training forms: a plain store.  Non-temporal (__builtin_nontemporal_store) measured
+// SLOWER (cspnk_d2 with history 83-85 -> 92-93 us, the transposed launches 44.4 -> 47.9 us), unlike the fp32 planes of the 3 x 3 forms
+// (cspn_resident.hip st4_hist)
 __device__ __forceinline__ void st16_hist(gptr p, uint4 v) {
     const v4u w = {v.x, v.y, v.z, v.w};
-    if (CSPN_KRES_HIST_NT) __builtin_nontemporal_store(w, reinterpret_cast<GLB v4u*>(p));
-    else *reinterpret_cast<GLB v4u*>(p) = w;
+    *reinterpret_cast<GLB v4u*>(p) = w;
 }
 __device__ __forceinline__ unsigned ld4u(gptr p) { return *reinterpret_cast<const GLB unsigned*>(p); }
 __device__ __forceinline__ uint2 ld8u(gptr p) {

@@ -615,10 +615,7 @@ __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_resident(const KResArgs 
 
 // ------------------------------------------------------------------------------------------------ host side
 constexpr int KRES_MAX_NO_K5 = 2;
-constexpr int KRES_T_MAX_ROUNDS = 8;    // rounds of the reverse sweep in one launch
-#ifndef CSPN_KT_ONE_LAUNCH
-#define CSPN_KT_ONE_LAUNCH 1
-#endif
+constexpr int KRES_T_ROUNDS_PER_LAUNCH = 8;    // rounds of the reverse sweep in one launch (1: one launch per round, the schedule up to round 4)
 constexpr int KRES_MAX_NO_K3 = 4;
 
 struct KGeom {
@@ -787,10 +784,9 @@ int kres_d2_whole_batch(const char* who, KResArgs& a, const KGeom& g, int B, int
     a.nb = g.imgs_per_launch < B ? g.imgs_per_launch : B;
     a.rounds = ceil_div(B, a.nb);
     a.last_chunk = 1;
-    const int npf = cspn_detail::kres_d2_prefetch_channels(g.dr, a.ls, g.threads, a.rounds);
-    const size_t ldsb = cspn_detail::kres_d2_lds_bytes(g.dr, a.ls, g.threads, npf);
+    const size_t ldsb = cspn_detail::kres_d2_lds_bytes(g.dr, a.ls, g.threads);
     if (ldsb > 160 * 1024) return fail("%s: the dot-product form needs %zu bytes of LDS", who, ldsb);
-    return cspn_detail::kres_d2_launch(&a, g.threads, a.nb * g.tiles_x * g.tiles_y, ldsb, blend, mode, kregions_inside_image(g, H, W, T) ? 1 : 0, npf, stream);
+    return cspn_detail::kres_d2_launch(&a, g.threads, a.nb * g.tiles_x * g.tiles_y, ldsb, blend, mode, kregions_inside_image(g, H, W, T) ? 1 : 0, stream);
 }
 
 template <int K, int NO, typename ST, int NTH, typename GT = __half>
@@ -956,10 +952,10 @@ int cspnk_transposed_resident(const void* wk, int w_dtype, int K, const void* g_
     const int tr = in_dtype == CSPN_F16 ? 2 : 1;
     const bool clean = kregions_inside_image(g, H, W, T);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // ONE launch for the whole batch (KRES_T_MAX_ROUNDS rounds of images_per_launch images at most per launch: the bounded neighbour wait
-    // is sized for launches of a few hundred microseconds).  -DCSPN_KT_ONE_LAUNCH=0: one launch per round, the schedule up to round 4.
+    // ONE launch for the whole batch (KRES_T_ROUNDS_PER_LAUNCH rounds of images_per_launch images at most per launch: the bounded neighbour
+    // wait is sized for launches of a few hundred microseconds).
     const int ipl = g.imgs_per_launch < B ? g.imgs_per_launch : B;
-    const int max_rounds = CSPN_KT_ONE_LAUNCH ? KRES_T_MAX_ROUNDS : 1;
+    constexpr int max_rounds = KRES_T_ROUNDS_PER_LAUNCH;
     for (int b0 = 0; b0 < B; b0 += ipl * max_rounds) {
         a.b0 = b0;
         a.nb = (B - b0) < ipl ? (B - b0) : ipl;

@@ -25,10 +25,6 @@ std::atomic<int>& force_generic_flag() {
     return flag;
 }
 
-#ifndef CSPN_PAC_NT
-#define CSPN_PAC_NT 0          // developer A/B: 1 = non-temporal stores of the tiled kernels' results
-#endif
-
 struct ConvArgs {
     int B, C, CK, H, W, Ho, Wo, WQ;      // WQ = ceil(Wo / 4) output quads per row
     int kh, kw, sh, sw, ph, pw, dh, dw;
@@ -304,11 +300,6 @@ __global__ __launch_bounds__(256, (K > 5 && (CB <= 4 || NBUF == 1) ? 2 : 1)) voi
     };
     auto store_dst = [&](int c, const float (&acc)[4]) {
         T* op = dst + ((size_t)b * a.C + c) * dplane + dpix;
-#if CSPN_PAC_NT & 1
-        if constexpr (std::is_same<T, float>::value) {
-            if (a.dst_vec) { const v4f v = {acc[0], acc[1], acc[2], acc[3]}; __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(op)); return; }
-        }
-#endif
         if (a.dst_vec) store_quad<T, true>(op, x0, a.dst_w, acc);
         else store_quad<T, false>(op, x0, a.dst_w, acc);
     };

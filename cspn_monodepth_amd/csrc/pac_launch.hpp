@@ -6,13 +6,6 @@
 #include <algorithm>
 #include <utility>
 
-#ifndef CSPN_PAC_WANT_WGS
-#define CSPN_PAC_WANT_WGS 1024
-#endif
-#ifndef CSPN_S2_WANT
-#define CSPN_S2_WANT 1024
-#endif
-
 namespace {
 
 // ------------------------------------------------------------------------------------------------ workgroup targets
@@ -21,13 +14,13 @@ namespace {
 // 57 / 47 / 54 us.  The LDS-tiled square kernels share it: every channel chunk re-reads the kernel planes, so only split as far as
 // filling the chip needs (~4 x 256 groups).
 // GK_ANY_TAPGROUP_WANT_WGS: tap groups of the any-geometry dL/dkernel with a shared kernel.  Same row, 1 / 2 tap groups: 58 / 88 us.
-constexpr size_t ANY_WANT_WGS = CSPN_PAC_WANT_WGS, GK_ANY_TAPGROUP_WANT_WGS = 256;
+constexpr size_t ANY_WANT_WGS = 1024, GK_ANY_TAPGROUP_WANT_WGS = 256;
 constexpr size_t PERCH_WANT_FACTOR = 4;      // tiled forward / dL/dinput with a per-channel kernel: nothing is re-read, split 4 x further
 constexpr size_t H8_WANT_WGS = 1024;         // fp16 eight-pixel forward
 constexpr size_t GK_WANT_WGS = 4096;         // outer-product dL/dkernel (per-channel kernel: a pure store stream)
 constexpr size_t GK_ANY_WANT_WGS = 1024;     // ... of the any-geometry kernel (channel chunks of a per-channel kernel)
 constexpr size_t GENERIC_WANT_WGS = 2048;    // generic one-quad kernels: enough workgroups to fill 256 CUs a few times over
-constexpr size_t S2_WANT_WGS = CSPN_S2_WANT; // stride-2 chunked launches
+constexpr size_t S2_WANT_WGS = 1024;         // stride-2 chunked launches
 
 // Channels per workgroup of a launch that has `have` workgroups before any split and wants `want`: the channels go to
 // min(ceil(want / have), ceil(C / granule)) chunks of equal size, rounded up to the granule (the kernel's channel batch).

@@ -128,6 +128,19 @@ def test_code_digest_covers_the_benchmarked_files_only():
     assert _lib._source_digest(["x"]) != _lib._source_digest(["x"], code_only=True)
 
 
+def test_kernel_sources_carry_no_compile_time_switches():
+    """csrc/ holds one form of every kernel: no conditional compilation and no object-like CSPN_* macro a -D could override.  A finished
+    experiment lives as a patch under tools/probes/ (its README lists them); CSPN_PRELAUNCH, CSPN_PRE and HIP_OK are function-like."""
+    conditional = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b")
+    switch = re.compile(r"^\s*#\s*define\s+CSPN_[A-Z0-9_]+\s+\S")
+    paths = [os.path.join(_lib.CSRC, f) for f in _lib.SOURCES] + [p for p in _lib.BUILD_HEADERS if os.path.dirname(p) == _lib.CSRC]
+    assert len(paths) == len(_lib.SOURCES) + 5
+    for path in paths:
+        with open(path, encoding="utf-8") as fh:
+            hits = [(no, ln.rstrip()) for no, ln in enumerate(fh, 1) if conditional.match(ln) or switch.match(ln)]
+        assert not hits, (os.path.basename(path), hits)
+
+
 def test_ctypes_signatures_match_the_recorded_ones():
     """Every exported function carries the restype and argtypes recorded in tests/golden/g26_ctypes_signatures.json
     (tools/dump_ctypes_signatures.py, written when every declaration was still a hand-written line)."""

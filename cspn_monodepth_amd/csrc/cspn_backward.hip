@@ -65,8 +65,7 @@ __global__ void cspn3_grad_guidance_kernel(const GT* __restrict__ g, long bs, lo
         const int y = q / W, x = q - y * W;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int lin = j < 4 ? j : j + 1;
-            const int dy = lin / 3 - 1, dx = lin % 3 - 1;
+            const int dy = tap_dy<3>(j), dx = tap_dx<3>(j);
             const int yy = y - dy, xx = x - dx;       // p = q - off_j
             float val = 0.f;
             if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
@@ -355,8 +354,7 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
         float gq[8][4], gl[8], gr[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int lin = j < 4 ? j : j + 1;
-            const int dy = lin / 3 - 1, dx = lin % 3 - 1;
+            const int dy = tap_dy<3>(j), dx = tap_dx<3>(j);
             const int ty = y + dy;
             const bool tok = ty >= 0 && ty < H;
             const size_t o = (size_t)(7 - j) * a.g_cs + (size_t)(tok ? ty : 0) * W + x;
@@ -375,8 +373,7 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
         float dot[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int lin = j < 4 ? j : j + 1;
-            const int dx = lin % 3 - 1;
+            const int dx = tap_dx<3>(j);
             float ax[4];
             if (dx == 0) {
 #pragma unroll
@@ -395,8 +392,7 @@ __global__ __launch_bounds__(256) void cspn_grad_tail(const TailArgs a) {
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int lin = j < 4 ? j : j + 1;
-            const int dy = lin / 3 - 1, dx = lin % 3 - 1;
+            const int dy = tap_dy<3>(j), dx = tap_dx<3>(j);
             const size_t cplane = (size_t)(7 - j) * a.g_cs;
             const int ty = y + dy;
             float gA[4];
@@ -604,10 +600,8 @@ __device__ __forceinline__ void tail5_half(const TailArgs& a, float4 (*xdot)[128
             }
 #pragma unroll
             for (int jl = 0; jl < NH; ++jl) {
-                constexpr int KK2 = (K * K) / 2;
                 const int j = HALF * NH + jl;
-                const int lin = j < KK2 ? j : j + 1;
-                const int dy = lin / K - R, dx = lin % K - R;
+                const int dy = tap_dy<K>(j), dx = tap_dx<K>(j);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[jl][e] = fmaf(g4[e], win[dy - DY0][e + dx + R], acc[jl][e]);
             }

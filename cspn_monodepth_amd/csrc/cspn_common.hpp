@@ -239,6 +239,49 @@ template <> __device__ __forceinline__ float softmax_exp<__half>(float d) {
     return __builtin_amdgcn_exp2f(d * 1.44269502162933349609375f);
 }
 
+// The softmax weights of one pixel (CSPN_ours.py:35), in place: raw logits in, the values a tap volume of type WT holds out.
+// Maximum, softmax_exp<WT>, the sum in channel order from 0, one refined reciprocal, softmax_weight<WT>: the arithmetic of every
+// producer of softmax taps, and the one copy of it behind the guard kernels of cspn_repair.hip.
+// Remaining copies — hot kernels whose device code changes when they call this (another schedule; in the quad kernel commuted
+// v_add_f32 operands), which therefore keep the five operations spelled out and are held to them by the guard tests' bit
+// comparisons: cspn_pac_prepare_kernel and cspn_pac_prepare_vec_kernel (cspn_prepare.hip), the PAC derive of cspn3_resident
+// (cspn_resident.hip), the fp32 derive of cspnk_resident (cspnk_resident.hip).
+template <typename WT, int NT>
+__device__ __forceinline__ void softmax_in_channel_order(float (&v)[NT]) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < NT; ++c) mx = fmaxf(mx, v[c]);
+    float den = 0.f;
+#pragma unroll
+    for (int c = 0; c < NT; ++c) { v[c] = softmax_exp<WT>(v[c] - mx); den += v[c]; }
+    const float inv = reciprocal_refined(den);
+#pragma unroll
+    for (int c = 0; c < NT; ++c) v[c] = softmax_weight<WT>(v[c], inv);
+}
+
+// The taps of a K x K stencil are its pixels in row-major order without the centre: tap j reads the pixel at (tap_dy, tap_dx).
+template <int K> constexpr int tap_lin(int j) { return j < (K * K - 1) / 2 ? j : j + 1; }
+template <int K> constexpr int tap_dy(int j) { return tap_lin<K>(j) / K - K / 2; }
+template <int K> constexpr int tap_dx(int j) { return tap_lin<K>(j) % K - K / 2; }
+
+// The 3x3 gates of pixel (y, x): a[j] = |g_{7-j}[p + off_j]| (the reference's shifts, CSPN_new.py:29-70; 0 outside rows [0, H) and
+// columns [0, W)), and their sum S in the reference's channel order k = 0..7, i.e. tap 7..0 (CSPN_new.py:124-127): what the guard of
+// the 3x3 resident launch (cspn_repair.hip) normalises by.  gb: channel 0 of the image.  Remaining copy: cspn3_prepare_kernel (its
+// device code changes when it calls this).
+template <typename GT>
+__device__ __forceinline__ float abs_gates8(const GT* gb, long cs, int y, int x, int H, int W, float (&a)[8]) {
+    float S = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int j = 7 - k, yy = y + tap_dy<3>(j), xx = x + tap_dx<3>(j);
+        float v = 0.f;
+        if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = fabsf(ld1(gb + (size_t)k * cs + (size_t)yy * W + xx));
+        a[j] = v;
+        S = (k == 0) ? v : S + v;
+    }
+    return S;
+}
+
 // The 10 masked terms of Result.evaluate (libs/metrics.py:49-83) for one pixel, added to f[0..9]:
 // {inv^2, inv, diff^2, diff, diff/t, |log10 o - log10 t|, #(r<1.25), #(r<1.25^2), #(r<1.25^3), 1} over t > 0.
 // Algebraically equal forms that avoid cancellation and redundant divisions:

@@ -25,9 +25,7 @@ __global__ void cspn3_prepare_kernel(const GT* __restrict__ g, long bs, long cs,
         for (int k = 0; k < 8; ++k) {
             // reference plane k samples at o_k = -(off of tap k) ... tap j = 7-k, off_j row-major
             const int j = 7 - k;
-            const int lin = j < 4 ? j : j + 1;
-            const int dy = lin / 3 - 1, dx = lin % 3 - 1;
-            const int yy = y + dy, xx = x + dx;
+            const int yy = y + tap_dy<3>(j), xx = x + tap_dx<3>(j);
             float v = 0.f;
             if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = fabsf(ld1(gb + (size_t)k * cs + (size_t)yy * W + xx));
             a[j] = v;

@@ -129,8 +129,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<K, NQ>::value)) void cspn_prop_
             float lq[NT][R], rq[NT][R];      // lq[j][c] = column xq-R+c, rq[j][c] = column xq+4+c of the source row
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                const int lin = j < NT / 2 ? j : j + 1;
-                const int dy = lin / K - R;
+                const int dy = tap_dy<K>(j);
                 const int row = y + dy;
                 const bool rok = ok && row >= 0 && row < H;
                 const float4 v = rok ? ld4(wg + Taps<WT>::idx(NT - 1 - j, (size_t)(rok ? row : 0) * W + xq, HW)) : z4;
@@ -144,8 +143,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<K, NQ>::value)) void cspn_prop_
             if (fix_left) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    const int lin = j < NT / 2 ? j : j + 1;
-                    const int dy = lin / K - R, dx = lin % K - R;
+                    const int dy = tap_dy<K>(j), dx = tap_dx<K>(j);
                     const int row = y + dy;
                     if (dx < 0) {
 #pragma unroll
@@ -160,8 +158,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<K, NQ>::value)) void cspn_prop_
             if (fix_right) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    const int lin = j < NT / 2 ? j : j + 1;
-                    const int dy = lin / K - R, dx = lin % K - R;
+                    const int dy = tap_dy<K>(j), dx = tap_dx<K>(j);
                     const int row = y + dy;
                     if (dx > 0) {
 #pragma unroll
@@ -175,8 +172,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<K, NQ>::value)) void cspn_prop_
             }
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                const int lin = j < NT / 2 ? j : j + 1;
-                const int dx = lin % K - R;
+                const int dx = tap_dx<K>(j);
                 // window of the source row: [xq-R, xq+4+R) = lq | own quad | rq; tap value e = window[R + e + dx]
                 float win[4 + 2 * R];
 #pragma unroll
@@ -194,8 +190,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<K, NQ>::value)) void cspn_prop_
             float left[NT], right[NT];
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                const int lin = j < 4 ? j : j + 1;
-                const int dy = lin / 3 - 1, dx = lin % 3 - 1;
+                const int dy = tap_dy<3>(j), dx = tap_dx<3>(j);
                 const int row = y + dy;
                 const bool rok = ok && row >= 0 && row < H;
                 const WT* src = gq + (size_t)(7 - j) * a.g_cs + (size_t)(rok ? row : 0) * W;
@@ -208,8 +203,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<K, NQ>::value)) void cspn_prop_
             if (fix_left) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    const int lin = j < 4 ? j : j + 1;
-                    const int dy = lin / 3 - 1, dx = lin % 3 - 1;
+                    const int dy = tap_dy<3>(j), dx = tap_dx<3>(j);
                     if (dx < 0) {
                         const int row = y + dy;
                         const bool c = ok && row >= 0 && row < H && xq >= 1;
@@ -220,8 +214,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<K, NQ>::value)) void cspn_prop_
             if (fix_right) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    const int lin = j < 4 ? j : j + 1;
-                    const int dy = lin / 3 - 1, dx = lin % 3 - 1;
+                    const int dy = tap_dy<3>(j), dx = tap_dx<3>(j);
                     if (dx > 0) {
                         const int row = y + dy;
                         const bool c = ok && row >= 0 && row < H && xq + 4 < W;
@@ -232,8 +225,7 @@ __global__ __launch_bounds__(NTHREADS, (MinWaves<K, NQ>::value)) void cspn_prop_
             // a_j[e] = |g_{7-j}[p_e + off_j]|
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                const int lin = j < 4 ? j : j + 1;
-                const int dx = lin % 3 - 1;
+                const int dx = tap_dx<3>(j);
                 const float q0 = wreg[i][j][0], q1 = wreg[i][j][1], q2 = wreg[i][j][2], q3 = wreg[i][j][3];
                 if (dx < 0) { wreg[i][j][0] = fabsf(left[j]); wreg[i][j][1] = fabsf(q0); wreg[i][j][2] = fabsf(q1); wreg[i][j][3] = fabsf(q2); }
                 else if (dx > 0) { wreg[i][j][0] = fabsf(q1); wreg[i][j][1] = fabsf(q2); wreg[i][j][2] = fabsf(q3); wreg[i][j][3] = fabsf(right[j]); }

@@ -1,20 +1,22 @@
-// cspn_repair.hip — the guard behind a weight-resident inference launch (include/cspn_hip.h: cspn_resident_plan.guard).
+// cspn_repair.hip — the guard behind a weight-resident launch (include/cspn_hip.h: cspn_resident_plan.guard).
 //
 // A resident launch whose workgroups could not all become co-resident in time (the GPU shared with a tenant that holds CUs for
 // seconds) gives up: its abort word receives the call's sequence number and the tiles that gave up leave the poison NaN.  The host
 // repairs that where the package is the next consumer (functional.py: journal) — but the reference module is plain ATen
-// (network/libs/post_process/CSPN_new.py:80-92): whatever consumes its output ON THE GPU sees the finished tensor.  This kernel
+// (network/libs/post_process/CSPN_new.py:80-92): whatever consumes its output ON THE GPU sees the finished tensor.  A guard kernel
 // restores that property from the stream: launched behind the resident launch(es) of a call, every workgroup reads the abort word and
 // returns at once when it is not this call's sequence number (the success path: one empty launch, priced in DESIGN.md §4.1b);
-// otherwise the whole batch is re-computed here — slowly, but with the resident kernel's arithmetic, operation for operation
-// (|g| gathered with the reference's shifts, S summed in channel order, div8_shared_reciprocal, the blend folded into the taps,
-// the eight FMAs in tap order from 0, + m * d0), so the repaired result is bit-identical to both schedules.
+// otherwise the whole batch is re-computed here — slowly, but with the guarded kernel's arithmetic, operation for operation, so the
+// repaired result is bit-identical to a clean call's.
 //
-// Re-computation: a workgroup takes a 32 x 32 output tile and the T-pixel halo its T steps depend on ((32 + 2T)^2 floats twice in
-// LDS: T <= 54), and advances the region step by step; the taps of a pixel are rebuilt from the guidance at every step (no
-// register residency, no exchange between workgroups — nothing here can wait for anybody).
+// Re-computation (guard_tiles): a workgroup takes a 32 x 32 output tile and the T * (K / 2) pixel halo its T steps depend on (two
+// planes of (32 + 2 halo)^2 floats in LDS: halo <= 54), and advances the region step by step; the taps of a pixel are rebuilt from
+// the guidance at every step (no register residency, no exchange between workgroups — nothing here can wait for anybody).  The four
+// kernels differ in what a pixel starts as, what it becomes at a step and what is stored; the weight derives they share with the
+// guarded kernels are functions of cspn_common.hpp (softmax_in_channel_order, abs_gates8, div8_shared_reciprocal) and
+// cspnk_helpers.hpp (softmax_to_pairs: the dot-product form, shared with cspnk_d2.hip).
 #include "cspn_common.hpp"
-#include "cspnk_helpers.hpp"      // the dot-product form's arithmetic (shared with cspnk_d2.hip: the same code, the same bits)
+#include "cspnk_helpers.hpp"
 
 #include <array>
 #include <utility>
@@ -23,15 +25,78 @@ namespace {
 
 constexpr int REP_TILE = 32, REP_THREADS = 256;
 
+// what every guard kernel's arguments begin with (tiles_x / tiles_y: guard_launch)
+struct GuardGeom {
+    const unsigned* abort_word; unsigned seq;
+    int B, H, W, T, tiles_x, tiles_y;
+};
+// the call finished: nothing to do
+__device__ __forceinline__ bool guard_idle(const GuardGeom& t) {
+    return __hip_atomic_load(t.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != t.seq;
+}
+
+// The region of one tile: region pixel (ry, rx) is pixel (y(ry), x(rx)) of image b; the tile itself is the REP_TILE^2 pixels behind
+// the halo.
+struct Region {
+    int b, ty, tx, ry0, rx0, R, HALO, H, W;
+    __device__ int y(int ry) const { return ry0 + ry; }
+    __device__ int x(int rx) const { return rx0 + rx; }
+    __device__ bool own(int ry, int rx) const { return ry >= HALO && ry < HALO + REP_TILE && rx >= HALO && rx < HALO + REP_TILE; }
+    __device__ bool image(int y, int x) const { return y >= 0 && y < H && x >= 0 && x < W; }
+};
+
+// The tile loop of every guard kernel: the tiles of the batch over the workgroups, a tile's region staged into `cur` (the second
+// plane zeroed: its border is never computed and must read as 0), T steps of which step s advances the pixels whose stencil
+// inputs are still exact — the window shrinks by RK = K / 2 per step — and at the end the tile's own pixels.
+//   start(region, ry, rx)            -> what a region pixel starts as
+//   step(region, s, ry, rx, centre)  -> what it becomes at step s; centre points at its state in `cur` (row stride region.R)
+//   finish(region, y, x, v)          <- the final state v of the tile pixel at image position (y, x), which may lie past the image
+// Everything a form stores on the way (history planes, published taps, padding columns) is its callables' own business.
+template <int RK, typename Start, typename Step, typename Finish>
+__device__ __forceinline__ void guard_tiles(const GuardGeom& t, float* lds, Start start, Step step, Finish finish) {
+    const int HALO = t.T * RK, R = REP_TILE + 2 * HALO;
+    float* cur = lds;
+    float* nxt = lds + (size_t)R * R;
+    const int tiles = t.tiles_x * t.tiles_y;
+    for (int k = blockIdx.x; k < t.B * tiles; k += gridDim.x) {
+        const int b = k / tiles, tr = k - b * tiles, ty = tr / t.tiles_x, tx = tr - ty * t.tiles_x;
+        const Region r{b, ty, tx, ty * REP_TILE - HALO, tx * REP_TILE - HALO, R, HALO, t.H, t.W};
+        __syncthreads();                                                   // (the previous tile's readers are done)
+        for (int i = threadIdx.x; i < R * R; i += REP_THREADS) {
+            const int ry = i / R, rx = i - ry * R;
+            cur[i] = start(r, ry, rx);
+            nxt[i] = 0.f;
+        }
+        __syncthreads();
+        for (int s = 1; s <= t.T; ++s) {
+            // after step s the pixels within (T - s) * RK of the tile are exact: only those are advanced
+            const int lo = s * RK, n = R - 2 * lo;
+            for (int i = threadIdx.x; i < n * n; i += REP_THREADS) {
+                const int ry = lo + i / n, rx = lo + i % n;
+                nxt[ry * R + rx] = step(r, s, ry, rx, cur + ry * R + rx);
+            }
+            __syncthreads();
+            float* tmp = cur; cur = nxt; nxt = tmp;
+        }
+        for (int i = threadIdx.x; i < REP_TILE * REP_TILE; i += REP_THREADS) {
+            const int ly = i / REP_TILE, lx = i - ly * REP_TILE;
+            finish(r, ty * REP_TILE + ly, tx * REP_TILE + lx, cur[(HALO + ly) * R + HALO + lx]);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the 3 x 3 forms (cspn3_resident)
 struct RepArgs {
+    GuardGeom t;
     const float* g; long g_bs, g_cs;
     const float* d0; const float* sparse; float* out;
     float* hist; float* s_out; float* w_out; const float* s_in;
     const float* target; double* macc; int nslots;      // MODE 1: the fused depth metrics of the pixels the failed launch did not score
-    const unsigned* abort_word; unsigned seq;
-    int B, H, W, Wv, T, tiles_x, tiles_y;
+    int Wv;
 };
 
+// The arithmetic of cspn3_resident, operation for operation: |g| gathered with the reference's shifts and S summed in channel order
+// (abs_gates8), div8_shared_reciprocal, the blend folded into the taps, the eight FMAs in tap order from 0, + m * d0.
 // MODE 0: inference (refined depth -> out).  MODE 1: inference with the depth metrics fused — the launch that gave up has scored the
 // tiles that finished and poisoned the others, so the re-computation adds the metric terms of exactly the pixels it finds poisoned
 // (summation order differs from the fused epilogue's: the sums agree to ~1e-7, the refined depth to the bit).  MODE 2: the training forward — every step's state goes to its history plane, the
@@ -39,166 +104,114 @@ struct RepArgs {
 // the taps |g_j[p]| / S[p + off_j]; d0 is G_T, the history receives G_{T-1} .. G_0, (1-m) G travels.  MODE 3: the same sweep on taps
 // gathered from a forward tap volume (a.g = [B,8,H,W]): tap j = w_{7-j}[p + off_j].
 // PAC = 1 (MODE 0 / 2): the K = 3 softmax form of CSPN_ours.py:35-41 — tap j = softmax over the 8 guidance channels at the pixel
-// itself, with the arithmetic of cspn3_resident's PAC instances (maximum, two-piece exponential, sum in channel order, one refined
-// reciprocal); MODE 2 publishes the taps (no S).
+// itself (softmax_in_channel_order<float>, as cspn3_resident's PAC instances and cspn_pac_prepare_kernel); MODE 2 publishes the taps
+// (no S).
 template <int BLEND, int MODE, int PAC>
 __global__ __launch_bounds__(REP_THREADS) void cspn3_resident_repair(const RepArgs a) {
-    if (__hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.seq) return;      // the call finished: nothing to do
+    if (guard_idle(a.t)) return;
     constexpr bool TRANSG = MODE == 4, TRANS = MODE == 3 || MODE == 4, HIST = MODE >= 2, SCORE = MODE == 1;
     float mf[10];
 #pragma unroll
     for (int k = 0; k < 10; ++k) mf[k] = 0.f;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int T = a.T, R = REP_TILE + 2 * T, H = a.H, W = a.W, Wv = a.Wv;
-    float* cur = lds;
-    float* nxt = lds + (size_t)R * R;
-    const int tiles = a.tiles_x * a.tiles_y;
-    const size_t HW = (size_t)H * W, plane = (size_t)a.B * HW;
-    for (int t = blockIdx.x; t < a.B * tiles; t += gridDim.x) {
-        const int b = t / tiles, tr = t - b * tiles, ty = tr / a.tiles_x, tx = tr - ty * a.tiles_x;
-        const int ry0 = ty * REP_TILE - T, rx0 = tx * REP_TILE - T;       // image coordinates of region (0, 0)
-        const float* __restrict__ gb = a.g + (size_t)b * a.g_bs;
-        const float* __restrict__ db = a.d0 + b * HW;
-        const float* __restrict__ sb = BLEND ? a.sparse + b * HW : nullptr;
-        const float* __restrict__ sib = TRANSG ? a.s_in + b * HW : nullptr;
-        __syncthreads();                                                   // (the previous tile's readers are done)
-        for (int i = threadIdx.x; i < R * R; i += REP_THREADS) {
-            const int ry = i / R, rx = i - ry * R, y = ry0 + ry, x = rx0 + rx;
-            const bool in = y >= 0 && y < H && x >= 0 && x < Wv;
-            float v = in ? db[(size_t)y * W + x] : 0.f;
-            if (TRANS && BLEND && in) v *= 1.f - sgnf(sb[(size_t)y * W + x]);      // the sweep starts from (1-m) G_T
-            cur[i] = v;
-            nxt[i] = 0.f;
-        }
-        __syncthreads();
-        for (int s = 1; s <= T; ++s) {
-            // after step s the pixels within T - s of the tile are exact: only those are advanced
-            const int lo = s, n = R - 2 * s;
-            float* const hp = HIST ? a.hist + (size_t)(s - 1) * plane + b * HW : nullptr;
-            for (int i = threadIdx.x; i < n * n; i += REP_THREADS) {
-                const int ry = lo + i / n, rx = lo + i % n, y = ry0 + ry, x = rx0 + rx;
-                float keep = 0.f;
-                if (y >= 0 && y < H && x >= 0 && x < Wv) {
-                    const bool mine = ry >= T && ry < T + REP_TILE && rx >= T && rx < T + REP_TILE;      // a pixel of the tile itself
-                    float qv[8];
-                    float m = 0.f;
-                    if (BLEND) m = sgnf(sb[(size_t)y * W + x]);
-                    if (TRANSG) {
-                        // tap j = |channel j at p| x 1 / S[p + off_j] (the forward's refined reciprocal), 0 where p + off_j is outside
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const int lin = j < 4 ? j : j + 1, yy = y + lin / 3 - 1, xx = x + lin % 3 - 1;
-                            const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < Wv;
-                            const float rs = ok ? reciprocal_as_forward(sib[(size_t)yy * W + xx]) : 0.f;
-                            qv[j] = fabsf(gb[(size_t)j * a.g_cs + (size_t)y * W + x]) * rs;
-                        }
-                    } else if (TRANS) {
-                        // tap j = w_{7-j}[p + off_j] from the forward's tap volume, 0 outside the image
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const int lin = j < 4 ? j : j + 1, yy = y + lin / 3 - 1, xx = x + lin % 3 - 1;
-                            const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
-                            qv[j] = ok ? gb[(size_t)(7 - j) * a.g_cs + (size_t)yy * W + xx] : 0.f;
-                        }
-                    } else if (PAC) {
-                        float mx = -INFINITY, den = 0.f;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) { qv[j] = gb[(size_t)j * a.g_cs + (size_t)y * W + x]; mx = fmaxf(mx, qv[j]); }
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) { qv[j] = softmax_exp<float>(qv[j] - mx); den += qv[j]; }
-                        const float inv = reciprocal_refined(den);
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) qv[j] = softmax_weight<float>(qv[j], inv);
-                        if (MODE == 2 && mine && s == 1) {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) a.w_out[((size_t)b * 8 + j) * HW + (size_t)y * W + x] = qv[j];
-                        }
-                        if (BLEND) {
-                            const float om = 1.f - m;
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) qv[j] *= om;
-                        }
-                    } else {
-                        // taps as cspn3_resident derives them: tap j (row-major without the centre) = |channel 7-j| at p + off_j, 0
-                        // outside the image (rows: [0, H); columns: [0, W) — the row padding [Wv, W) holds the caller's zeros)
-                        float av[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const int lin = j < 4 ? j : j + 1, yy = y + lin / 3 - 1, xx = x + lin % 3 - 1;
-                            const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
-                            av[j] = ok ? fabsf(gb[(size_t)(7 - j) * a.g_cs + (size_t)yy * W + xx]) : 0.f;
-                        }
-                        float S = av[7];
-#pragma unroll
-                        for (int k = 1; k < 8; ++k) S += av[7 - k];          // the reference's channel order (CSPN_new.py:124-127)
-                        div8_shared_reciprocal(av, S, qv);
-                        if (MODE == 2 && mine && s == 1) {                      // published before the blend is folded in
-                            a.s_out[b * HW + (size_t)y * W + x] = S;
-                            if (a.w_out) {
-#pragma unroll
-                                for (int j = 0; j < 8; ++j) a.w_out[((size_t)b * 8 + j) * HW + (size_t)y * W + x] = qv[j];
-                            }
-                        }
-                        if (BLEND) {
-                            const float om = 1.f - m;                          // 0, 1 or 2: exact
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) qv[j] *= om;
-                        }
-                    }
-                    float u = 0.f;
+    const int H = a.t.H, W = a.t.W, Wv = a.Wv;
+    const size_t HW = (size_t)H * W, plane = (size_t)a.t.B * HW;
+    // a pixel the launch computes (rows [0, H), columns [0, Wv)), and a row-padding column inside the last valid quad: the resident
+    // launch stores (and, giving up, poisons) that quad as a whole, with zeros in its padding columns
+    auto valid = [&](int y, int x) { return y >= 0 && y < H && x >= 0 && x < Wv; };
+    auto padding = [&](int y, int x) { return y >= 0 && y < H && x >= Wv && x < W && (x & ~3) < Wv; };
+    guard_tiles<1>(a.t, lds,
+        [&](const Region& r, int ry, int rx) -> float {
+            const int y = r.y(ry), x = r.x(rx);
+            if (!valid(y, x)) return 0.f;
+            const size_t p = r.b * HW + (size_t)y * W + x;
+            float v = a.d0[p];
+            if (TRANS && BLEND) v *= 1.f - sgnf(a.sparse[p]);      // the sweep starts from (1-m) G_T
+            return v;
+        },
+        [&](const Region& r, int s, int ry, int rx, const float* c) -> float {
+            const int b = r.b, y = r.y(ry), x = r.x(rx);
+            const bool mine = r.own(ry, rx);
+            const size_t p = b * HW + (size_t)y * W + x;      // (an index only where (y, x) is valid or padding)
+            const float* __restrict__ gb = a.g + (size_t)b * a.g_bs;
+            float* const hp = HIST ? a.hist + (size_t)(s - 1) * plane : nullptr;
+            float keep = 0.f;
+            if (valid(y, x)) {
+                float qv[8];
+                float m = 0.f;
+                if (BLEND) m = sgnf(a.sparse[p]);
+                if (TRANSG) {
+                    // tap j = |channel j at p| x 1 / S[p + off_j] (the forward's refined reciprocal), 0 where p + off_j is outside
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        const int lin = j < 4 ? j : j + 1;
-                        u = fmaf(qv[j], cur[(ry + lin / 3 - 1) * R + rx + lin % 3 - 1], u);
+                        const int yy = y + tap_dy<3>(j), xx = x + tap_dx<3>(j);
+                        const float rs = valid(yy, xx) ? reciprocal_as_forward(a.s_in[b * HW + (size_t)yy * W + xx]) : 0.f;
+                        qv[j] = fabsf(gb[(size_t)j * a.g_cs + (size_t)y * W + x]) * rs;
                     }
-                    if (TRANS) {
-                        keep = BLEND ? __fmul_rn(1.f - m, u) : u;              // (1-m) G travels, G itself goes to the history
-                    } else {
-                        // + m * d0: a product rounded on its own, then an addition (the resident kernel keeps m * d0 in LDS) — never one FMA
-                        if (BLEND) u = __fadd_rn(u, __fmul_rn(m, db[(size_t)y * W + x]));
-                        keep = u;
-                    }
-                    if (HIST && mine) hp[(size_t)y * W + x] = u;
-                }
-                else if (MODE == 2 && !PAC && s == 1 && y >= 0 && y < H && x >= Wv && x < W && (x & ~3) < Wv && ry >= T && ry < T + REP_TILE && rx >= T && rx < T + REP_TILE) {
-                    // row padding inside the last valid quad: the resident launch stores that quad's S (and zero taps) as a whole
-                    float S = 0.f;
+                } else if (TRANS) {
+                    // tap j = w_{7-j}[p + off_j] from the forward's tap volume, 0 outside the image
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const int j = 7 - k, lin = j < 4 ? j : j + 1, yy = y + lin / 3 - 1, xx = x + lin % 3 - 1;
-                        const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
-                        const float av = ok ? fabsf(gb[(size_t)(7 - j) * a.g_cs + (size_t)yy * W + xx]) : 0.f;
-                        S = k == 0 ? av : S + av;
+                    for (int j = 0; j < 8; ++j) {
+                        const int yy = y + tap_dy<3>(j), xx = x + tap_dx<3>(j);
+                        qv[j] = r.image(yy, xx) ? gb[(size_t)(7 - j) * a.g_cs + (size_t)yy * W + xx] : 0.f;
                     }
-                    a.s_out[b * HW + (size_t)y * W + x] = S;
-                    if (a.w_out) {
+                } else if (PAC) {
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) a.w_out[((size_t)b * 8 + j) * HW + (size_t)y * W + x] = 0.f;
+                    for (int j = 0; j < 8; ++j) qv[j] = gb[(size_t)j * a.g_cs + (size_t)y * W + x];
+                    softmax_in_channel_order<float>(qv);
+                } else {
+                    // (rows: [0, H); columns: [0, W) — the row padding [Wv, W) holds the caller's zeros)
+                    float av[8];
+                    const float S = abs_gates8(gb, a.g_cs, y, x, H, W, av);
+                    div8_shared_reciprocal(av, S, qv);
+                    if (MODE == 2 && mine && s == 1) a.s_out[p] = S;
+                }
+                if (!TRANS) {
+                    if (MODE == 2 && mine && s == 1 && (PAC || a.w_out)) {      // published before the blend is folded in
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) a.w_out[((size_t)b * 8 + j) * HW + (size_t)y * W + x] = qv[j];
+                    }
+                    if (BLEND) {
+                        const float om = 1.f - m;                          // 0, 1 or 2: exact
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) qv[j] *= om;
                     }
                 }
-                // row padding inside the last valid quad: the resident launch stores (and, giving up, poisons) that quad as a whole, with
-                // zeros in its padding columns — a C-API reader of the repaired history plane must find them again
-                if (HIST && y >= 0 && y < H && x >= Wv && x < W && (x & ~3) < Wv && ry >= T && ry < T + REP_TILE && rx >= T && rx < T + REP_TILE)
-                    hp[(size_t)y * W + x] = 0.f;
-                nxt[ry * R + rx] = keep;
+                float u = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) u = fmaf(qv[j], c[tap_dy<3>(j) * r.R + tap_dx<3>(j)], u);
+                if (TRANS) {
+                    keep = BLEND ? __fmul_rn(1.f - m, u) : u;              // (1-m) G travels, G itself goes to the history
+                } else {
+                    // + m * d0: a product rounded on its own, then an addition (the resident kernel keeps m * d0 in LDS) — never one FMA
+                    if (BLEND) u = __fadd_rn(u, __fmul_rn(m, a.d0[p]));
+                    keep = u;
+                }
+                if (HIST && mine) hp[p] = u;
+            } else if (MODE == 2 && !PAC && s == 1 && mine && padding(y, x)) {
+                // the resident launch stores the padding columns' S (and zero taps) with their quad
+                float av[8];
+                a.s_out[p] = abs_gates8(gb, a.g_cs, y, x, H, W, av);
+                if (a.w_out) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) a.w_out[((size_t)b * 8 + j) * HW + (size_t)y * W + x] = 0.f;
+                }
             }
-            __syncthreads();
-            float* tmp = cur; cur = nxt; nxt = tmp;
-        }
-        if (!HIST) {
-            float* __restrict__ ob = a.out + b * HW;
-            for (int i = threadIdx.x; i < REP_TILE * REP_TILE; i += REP_THREADS) {
-                const int ly = i / REP_TILE, lx = i - ly * REP_TILE, y = ty * REP_TILE + ly, x = tx * REP_TILE + lx;
+            // ... and zeros in the history: a C-API reader of the repaired plane must find them again
+            if (HIST && mine && padding(y, x)) hp[p] = 0.f;
+            return keep;
+        },
+        [&](const Region& r, int y, int x, float v) {
+            if constexpr (!HIST) {
+                const size_t p = r.b * HW + (size_t)y * W + x;
                 if (y < H && x < Wv) {
-                    const float v = cur[(T + ly) * R + T + lx];
-                    if (SCORE && __float_as_uint(ob[(size_t)y * W + x]) == CSPN_POISON_F32) metric_terms(v, a.target[b * HW + (size_t)y * W + x], mf);
-                    ob[(size_t)y * W + x] = v;
-                } else if (y < H && x < W && (x & ~3) < Wv) {
-                    ob[(size_t)y * W + x] = 0.f;      // padding columns of the last valid quad: zeros, as the clean launch stores them
+                    if (SCORE && __float_as_uint(a.out[p]) == CSPN_POISON_F32) metric_terms(v, a.target[p], mf);
+                    a.out[p] = v;
+                } else if (padding(y, x)) {
+                    a.out[p] = 0.f;      // zeros, as the clean launch stores them
                 }
             }
-        }
-    }
+        });
     if (SCORE) {
         __syncthreads();
         float* part = lds;
@@ -219,19 +232,16 @@ __global__ __launch_bounds__(REP_THREADS) void cspn3_resident_repair(const RepAr
 
 
 // ------------------------------------------------------------------------------------------------ K x K softmax forms (CSPN_ours)
-// The guard of cspnk_forward_resident's unscored inference calls (round 5): same structure — 32 x 32 output tiles with the T * (K / 2)
-// pixel halo of T steps in LDS, nothing to wait for — with the arithmetic of the FMA kernel cspnk_resident: softmax over the K*K-1
-// channels at the pixel itself (fp16 guidance: float(half) - max, 2^(d log2 e), sum in channel order, refined reciprocal, ONE rounding
-// to half; fp32 guidance: the two-piece exponential), (1-m) folded into the taps, one FMA per tap in row-major tap order from 0,
-// + m * x0, the state rounded to the plane dtype where that kernel rounds it: after every `round_every` steps (its phase length) and
-// at the end.  For the FMA step form the re-computed depth is therefore the multi-launch schedule's bits, whatever its phase length.
+// The guard of cspnk_forward_resident's unscored inference calls: the arithmetic of the FMA kernel cspnk_resident (kxk_fma_pixel),
+// the state rounded to the plane dtype where that kernel rounds it: after every `round_every` steps (its phase length) and at the
+// end.  For the FMA step form the re-computed depth is therefore the multi-launch schedule's bits, whatever its phase length.
 // The dot-product form (cspnk_d2: state rounded after EVERY step, two taps per v_dot2_f32_f16) is re-computed with its own arithmetic
-// (D2 below).  Which of the two is re-computed is the launch site's explicit step_form argument, never inferred from round_every: an FMA
+// (d2_pixel).  Which of the two is re-computed is the launch site's explicit step_form argument, never inferred from round_every: an FMA
 // launch of phase length 1 (T = 1) rounds after every step as well, and must still get the FMA arithmetic.
 struct KRepArgs {
+    GuardGeom t;
     const void* g; const void* x0; const void* sparse; void* out;
-    const unsigned* abort_word; unsigned seq;
-    int B, H, W, T, round_every, tiles_x, tiles_y;
+    int round_every;
 };
 template <typename T> __device__ __forceinline__ float ldf(const void* p, size_t i);
 template <> __device__ __forceinline__ float ldf<float>(const void* p, size_t i) { return static_cast<const float*>(p)[i]; }
@@ -242,197 +252,152 @@ template <> __device__ __forceinline__ float round_to<__half>(float v) { return 
 __device__ __forceinline__ void stf(float* p, size_t i, float v) { p[i] = v; }
 __device__ __forceinline__ void stf(__half* p, size_t i, float v) { p[i] = __float2half_rn(v); }
 
-// D2 = 1 (K = 5, fp16 guidance, fp16 planes; round 6): the re-computation of the DOT-PRODUCT form (cspnk_d2.hip) with that kernel's own
-// arithmetic — the softmax as softmax_to_pairs forms it (max folded into the exponent's scale, v_exp_f32, sum in channel order, refined
+// a region pixel of a [B,H,W] plane of type ST, 0 outside the image: what the K x K forward forms start from
+template <typename ST>
+__device__ __forceinline__ float plane_pixel(const Region& r, const void* plane, int ry, int rx) {
+    const int y = r.y(ry), x = r.x(rx);
+    return r.image(y, x) ? ldf<ST>(plane, ((size_t)r.b * r.H + y) * r.W + x) : 0.f;
+}
+
+// One pixel of one K x K FMA step, as cspnk_resident (and cspn_pac_prepare + cspn_propagate) compute it: the softmax over the K*K-1
+// channels at the pixel itself (softmax_in_channel_order<GT>: for fp16 guidance ONE rounding to half), (1-m) folded into the taps
+// (1-m in {0, 1, 2}: exact in either tap dtype), one FMA per tap in row-major tap order from 0, + m * x0 as a product, then a sum;
+// `publish` sees the taps before the fold, `round_now` rounds the state to the plane dtype.  p: the pixel's index in its image,
+// gbase / pbase: the image's first element in the guidance / in a plane; centre: the pixel's state (row stride R).
+template <int K, typename GT, typename ST, int BLEND, typename Publish>
+__device__ __forceinline__ float kxk_fma_pixel(const void* g, const void* x0, const void* sparse, size_t gbase, size_t pbase, size_t p, size_t HW,
+                                               const float* centre, int R, bool round_now, Publish publish) {
+    constexpr int NT = K * K - 1;
+    float w[NT];
+#pragma unroll
+    for (int c = 0; c < NT; ++c) w[c] = ldf<GT>(g, gbase + (size_t)c * HW + p);
+    softmax_in_channel_order<GT>(w);
+    publish(w);
+    float m = 0.f;
+    if (BLEND) {
+        m = sgnf(ldf<ST>(sparse, pbase + p));
+#pragma unroll
+        for (int c = 0; c < NT; ++c) w[c] = round_to<GT>(w[c] * (1.f - m));
+    }
+    float u = 0.f;
+#pragma unroll
+    for (int c = 0; c < NT; ++c) u = fmaf(w[c], centre[tap_dy<K>(c) * R + tap_dx<K>(c)], u);
+    if (BLEND) u = __fadd_rn(u, __fmul_rn(m, ldf<ST>(x0, pbase + p)));
+    // (opaque: left to the compiler, the last FMA and the conversion fuse into ONE v_fma_mixlo_f16 — a single rounding of
+    // the exact sum where cspnk_resident rounds twice, fp32 then half: 2e-4 of the pixels differed by a half ulp)
+    asm volatile("" : "+v"(u));
+    return round_now ? round_to<ST>(u) : u;
+}
+
+// One pixel of one step of the DOT-PRODUCT form (cspnk_d2.hip: K = 5, fp16 guidance, fp16 planes) with that kernel's own arithmetic —
+// the softmax as softmax_to_pairs forms it (max folded into the exponent's scale, v_exp_f32, sum in channel order, refined
 // reciprocal, numerator x 1 / sum rounded by v_cvt_pk_f16_f32), the taps as tap PAIRS, a window row as dot2(pair dx -2 -1), dot2(pair dx 0 +1)
 // [centre row: dx +1 +2], then the single dx +2 tap as v_fma_mix_f32, rows top to bottom, + m x0 as the sum's start value, one v_cvt_pk_f16_f32
-// per step — so that a timed-out call of config 3's shape returns the BITS of a clean one (until round 5 "within its
-// fp16 tolerance").
-template <int K, typename GT, typename ST, int BLEND, int D2 = 0>
-__global__ __launch_bounds__(REP_THREADS) void cspnk_resident_repair(const KRepArgs a) {
-    if (__hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.seq) return;      // the call finished: nothing to do
-    constexpr int RK = K / 2, NT = K * K - 1;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int T = a.T, HALO = T * RK, R = REP_TILE + 2 * HALO, H = a.H, W = a.W;
-    float* cur = lds;
-    float* nxt = lds + (size_t)R * R;
-    const int tiles = a.tiles_x * a.tiles_y;
-    const size_t HW = (size_t)H * W;
-    for (int t = blockIdx.x; t < a.B * tiles; t += gridDim.x) {
-        const int b = t / tiles, tr = t - b * tiles, ty = tr / a.tiles_x, tx = tr - ty * a.tiles_x;
-        const int ry0 = ty * REP_TILE - HALO, rx0 = tx * REP_TILE - HALO;
-        const size_t gbase = (size_t)b * NT * HW, pbase = (size_t)b * HW;
-        __syncthreads();
-        for (int i = threadIdx.x; i < R * R; i += REP_THREADS) {
-            const int ry = i / R, rx = i - ry * R, y = ry0 + ry, x = rx0 + rx;
-            const bool in = y >= 0 && y < H && x >= 0 && x < W;
-            cur[i] = in ? ldf<ST>(a.x0, pbase + (size_t)y * W + x) : 0.f;
-            nxt[i] = 0.f;
-        }
-        __syncthreads();
-        for (int s = 1; s <= T; ++s) {
-            const int lo = s * RK, n = R - 2 * lo;
-            const bool round_now = (s % a.round_every) == 0 || s == T;
-            for (int i = threadIdx.x; i < n * n; i += REP_THREADS) {
-                const int ry = lo + i / n, rx = lo + i % n, y = ry0 + ry, x = rx0 + rx;
-                float u = 0.f;
-                if constexpr (D2 != 0) {
-                    if (y >= 0 && y < H && x >= 0 && x < W) {
-                        const size_t p = (size_t)y * W + x;
-                        unsigned gw[24], tp[12];
-                        unsigned mx2 = 0xfc00fc00u;
+// per step — so that a timed-out call of config 3's shape returns the BITS of a clean one.
+template <int BLEND>
+__device__ __forceinline__ float d2_pixel(const KRepArgs& a, size_t gbase, size_t pbase, size_t p, size_t HW, const float* centre, int R) {
+    unsigned gw[24], tp[12];
+    unsigned mx2 = 0xfc00fc00u;
 #pragma unroll
-                        for (int c = 0; c < 24; ++c) {
-                            gw[c] = (unsigned)__half_as_ushort(static_cast<const __half*>(a.g)[gbase + (size_t)c * HW + p]);
-                            mx2 = pk_max_f16(mx2, gw[c] | 0xfc000000u);           // (the high half stays -inf)
-                        }
-                        constexpr float L2E = 1.44269502162933349609375f;
-                        softmax_to_pairs<0>(gw, -h2f_lo(mx2) * L2E, tp);
-                        float acc = 0.f;
-                        if (BLEND) {
-                            const float m = sgnf(ldf<ST>(a.sparse, pbase + p));
-                            acc = m * ldf<ST>(a.x0, pbase + p);
-                            const unsigned om = pack_h2(1.f - m, 1.f - m);
+    for (int c = 0; c < 24; ++c) {
+        gw[c] = (unsigned)__half_as_ushort(static_cast<const __half*>(a.g)[gbase + (size_t)c * HW + p]);
+        mx2 = pk_max_f16(mx2, gw[c] | 0xfc000000u);           // (the high half stays -inf)
+    }
+    constexpr float L2E = 1.44269502162933349609375f;
+    softmax_to_pairs<0>(gw, -h2f_lo(mx2) * L2E, tp);
+    float acc = 0.f;
+    if (BLEND) {
+        const float m = sgnf(ldf<__half>(a.sparse, pbase + p));
+        acc = m * ldf<__half>(a.x0, pbase + p);
+        const unsigned om = pack_h2(1.f - m, 1.f - m);
 #pragma unroll
-                            for (int t = 0; t < 12; ++t) tp[t] = pk_mul_f16(tp[t], om);
-                        }
-                        asm volatile("" : "+v"(tp[10]), "+v"(tp[11]));        // (as the step loop of cspnk_d2: see mix_hh)
+        for (int t = 0; t < 12; ++t) tp[t] = pk_mul_f16(tp[t], om);
+    }
+    asm volatile("" : "+v"(tp[10]), "+v"(tp[11]));        // (as the step loop of cspnk_d2: see mix_hh)
 #pragma unroll
-                        for (int rr = 0; rr < 5; ++rr) {
-                            const float* row = cur + (ry + rr - 2) * R + rx;
-                            const unsigned pm = pack_h2(row[-2], row[-1]);       // the state is half-rounded every step: packing is exact
-                            if (rr == 2) {
-                                acc = dot2(tp[4], pm, acc);
-                                acc = dot2(tp[5], pack_h2(row[1], row[2]), acc);
-                            } else {
-                                const int s0 = rr < 2 ? 2 * rr : 6 + 2 * (rr - 3);
-                                acc = dot2(tp[s0], pm, acc);
-                                acc = dot2(tp[s0 + 1], pack_h2(row[0], row[1]), acc);
-                                const unsigned ps = pack_h2(row[2], 0.f);
-                                if (rr == 0) acc = mix_hh<0, 0>(tp[10], ps, acc);
-                                if (rr == 1) acc = mix_hh<1, 0>(tp[10], ps, acc);
-                                if (rr == 3) acc = mix_hh<0, 0>(tp[11], ps, acc);
-                                if (rr == 4) acc = mix_hh<1, 0>(tp[11], ps, acc);
-                            }
-                        }
-                        u = h2f_lo(cvt_pk_f16(acc, 0.f));
-                    }
-                } else
-                if (y >= 0 && y < H && x >= 0 && x < W) {
-                    const size_t p = (size_t)y * W + x;
-                    float w[NT];
-                    float mx = -INFINITY, den = 0.f;
-#pragma unroll
-                    for (int c = 0; c < NT; ++c) { w[c] = ldf<GT>(a.g, gbase + (size_t)c * HW + p); mx = fmaxf(mx, w[c]); }
-#pragma unroll
-                    for (int c = 0; c < NT; ++c) { w[c] = softmax_exp<GT>(w[c] - mx); den += w[c]; }
-                    const float inv = reciprocal_refined(den);
-                    float m = 0.f;
-                    if (BLEND) m = sgnf(ldf<ST>(a.sparse, pbase + p));
-#pragma unroll
-                    for (int c = 0; c < NT; ++c) {
-                        w[c] = softmax_weight<GT>(w[c], inv);
-                        if (BLEND) w[c] = round_to<GT>(w[c] * (1.f - m));      // 1-m in {0, 1, 2}: exact in either tap dtype
-                    }
-#pragma unroll
-                    for (int c = 0; c < NT; ++c) {
-                        const int lin = c < NT / 2 ? c : c + 1, dy = lin / K - RK, dx = lin % K - RK;
-                        u = fmaf(w[c], cur[(ry + dy) * R + rx + dx], u);
-                    }
-                    if (BLEND) u = __fadd_rn(u, __fmul_rn(m, ldf<ST>(a.x0, pbase + p)));
-                    // (opaque: left to the compiler, the last FMA and the conversion fuse into ONE v_fma_mixlo_f16 — a single rounding of
-                    // the exact sum where cspnk_resident rounds twice, fp32 then half: 2e-4 of the pixels differed by a half ulp)
-                    asm volatile("" : "+v"(u));
-                    if (round_now) u = round_to<ST>(u);
-                }
-                nxt[ry * R + rx] = u;
-            }
-            __syncthreads();
-            float* tmp = cur; cur = nxt; nxt = tmp;
-        }
-        ST* ob = static_cast<ST*>(a.out) + pbase;
-        for (int i = threadIdx.x; i < REP_TILE * REP_TILE; i += REP_THREADS) {
-            const int ly = i / REP_TILE, lx = i - ly * REP_TILE, y = ty * REP_TILE + ly, x = tx * REP_TILE + lx;
-            if (y < H && x < W) stf(ob, (size_t)y * W + x, cur[(HALO + ly) * R + HALO + lx]);
+    for (int rr = 0; rr < 5; ++rr) {
+        const float* row = centre + (rr - 2) * R;
+        const unsigned pm = pack_h2(row[-2], row[-1]);       // the state is half-rounded every step: packing is exact
+        if (rr == 2) {
+            acc = dot2(tp[4], pm, acc);
+            acc = dot2(tp[5], pack_h2(row[1], row[2]), acc);
+        } else {
+            const int s0 = rr < 2 ? 2 * rr : 6 + 2 * (rr - 3);
+            acc = dot2(tp[s0], pm, acc);
+            acc = dot2(tp[s0 + 1], pack_h2(row[0], row[1]), acc);
+            const unsigned ps = pack_h2(row[2], 0.f);
+            if (rr == 0) acc = mix_hh<0, 0>(tp[10], ps, acc);
+            if (rr == 1) acc = mix_hh<1, 0>(tp[10], ps, acc);
+            if (rr == 3) acc = mix_hh<0, 0>(tp[11], ps, acc);
+            if (rr == 4) acc = mix_hh<1, 0>(tp[11], ps, acc);
         }
     }
+    return h2f_lo(cvt_pk_f16(acc, 0.f));
+}
+
+// D2 = 1: the dot-product form (K = 5, GT = ST = __half)
+template <int K, typename GT, typename ST, int BLEND, int D2 = 0>
+__global__ __launch_bounds__(REP_THREADS) void cspnk_resident_repair(const KRepArgs a) {
+    if (guard_idle(a.t)) return;
+    constexpr int NT = K * K - 1;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int H = a.t.H, W = a.t.W, T = a.t.T;
+    const size_t HW = (size_t)H * W;
+    guard_tiles<K / 2>(a.t, lds,
+        [&](const Region& r, int ry, int rx) -> float { return plane_pixel<ST>(r, a.x0, ry, rx); },
+        [&](const Region& r, int s, int ry, int rx, const float* c) -> float {
+            const int y = r.y(ry), x = r.x(rx);
+            if (!r.image(y, x)) return 0.f;
+            const size_t gbase = (size_t)r.b * NT * HW, pbase = (size_t)r.b * HW, p = (size_t)y * W + x;
+            if constexpr (D2 != 0) {
+                return d2_pixel<BLEND>(a, gbase, pbase, p, HW, c, r.R);
+            } else {
+                const bool round_now = (s % a.round_every) == 0 || s == T;
+                return kxk_fma_pixel<K, GT, ST, BLEND>(a.g, a.x0, a.sparse, gbase, pbase, p, HW, c, r.R, round_now, [](const float (&)[NT]) {});
+            }
+        },
+        [&](const Region& r, int y, int x, float v) {
+            if (y < H && x < W) stf(static_cast<ST*>(a.out) + (size_t)r.b * HW, (size_t)y * W + x, v);
+        });
 }
 
 
-// ---- the K = 5 fp16 training forms (BASELINE config 3's shape; round 5) ------------------------------------------------------------
+// ---- the K = 5 fp16 training forms (BASELINE config 3's shape) -----------------------------------------------------------------------
 // Guard of cspnk_forward_resident_history's dot-product launch (cspnk_d2<HIST>): history [T,B,H,W] receives x_1 .. x_T, the state rounded
-// to the plane dtype after EVERY step, wk_out the softmax taps BEFORE the blend is folded in, in the Taps<__half> layout — the arithmetic
-// of cspn_pac_prepare + cspn_propagate (history) at one step per launch (one FMA per tap), i.e. what the multi-launch training path
-// stores; the dot-product kernel's own bits are within the fp16 tolerance of it, and the backward differentiates whichever history and
-// taps it is handed.
+// to the plane dtype after EVERY step, wk_out the softmax taps BEFORE the blend is folded in, in the Taps<__half> layout — kxk_fma_pixel
+// rounding every step, i.e. the arithmetic of cspn_pac_prepare + cspn_propagate (history) at one step per launch: what the multi-launch
+// training path stores; the dot-product kernel's own bits are within the fp16 tolerance of it, and the backward differentiates whichever
+// history and taps it is handed.
 struct KHistRepArgs {
+    GuardGeom t;
     const void* g; const void* x0; const void* sparse; void* hist; void* wk_out;
-    const unsigned* abort_word; unsigned seq;
-    int B, H, W, T, tiles_x, tiles_y;
 };
 
 template <int K, typename GT, typename ST, int BLEND>
 __global__ __launch_bounds__(REP_THREADS) void cspnk_history_repair(const KHistRepArgs a) {
-    if (__hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.seq) return;
-    constexpr int RK = K / 2, NT = K * K - 1;
+    if (guard_idle(a.t)) return;
+    constexpr int NT = K * K - 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int T = a.T, HALO = T * RK, R = REP_TILE + 2 * HALO, H = a.H, W = a.W;
-    float* cur = lds;
-    float* nxt = lds + (size_t)R * R;
-    const int tiles = a.tiles_x * a.tiles_y;
-    const size_t HW = (size_t)H * W, plane = (size_t)a.B * HW;
-    for (int t = blockIdx.x; t < a.B * tiles; t += gridDim.x) {
-        const int b = t / tiles, tr = t - b * tiles, ty = tr / a.tiles_x, tx = tr - ty * a.tiles_x;
-        const int ry0 = ty * REP_TILE - HALO, rx0 = tx * REP_TILE - HALO;
-        const size_t gbase = (size_t)b * NT * HW, pbase = (size_t)b * HW;
-        GT* const wkb = static_cast<GT*>(a.wk_out) + (size_t)b * Taps<GT>::image_elems(NT, HW);
-        __syncthreads();
-        for (int i = threadIdx.x; i < R * R; i += REP_THREADS) {
-            const int ry = i / R, rx = i - ry * R, y = ry0 + ry, x = rx0 + rx;
-            const bool in = y >= 0 && y < H && x >= 0 && x < W;
-            cur[i] = in ? ldf<ST>(a.x0, pbase + (size_t)y * W + x) : 0.f;
-            nxt[i] = 0.f;
-        }
-        __syncthreads();
-        for (int s = 1; s <= T; ++s) {
-            const int lo = s * RK, n = R - 2 * lo;
-            for (int i = threadIdx.x; i < n * n; i += REP_THREADS) {
-                const int ry = lo + i / n, rx = lo + i % n, y = ry0 + ry, x = rx0 + rx;
-                float u = 0.f;
-                if (y >= 0 && y < H && x >= 0 && x < W) {
-                    const size_t p = (size_t)y * W + x;
-                    const bool own = ry >= HALO && ry < HALO + REP_TILE && rx >= HALO && rx < HALO + REP_TILE;
-                    float w[NT];
-                    float mx = -INFINITY, den = 0.f;
+    const int W = a.t.W;
+    const size_t HW = (size_t)a.t.H * W, plane = (size_t)a.t.B * HW;
+    guard_tiles<K / 2>(a.t, lds,
+        [&](const Region& r, int ry, int rx) -> float { return plane_pixel<ST>(r, a.x0, ry, rx); },
+        [&](const Region& r, int s, int ry, int rx, const float* c) -> float {
+            const int y = r.y(ry), x = r.x(rx);
+            if (!r.image(y, x)) return 0.f;
+            const size_t gbase = (size_t)r.b * NT * HW, pbase = (size_t)r.b * HW, p = (size_t)y * W + x;
+            const bool own = r.own(ry, rx);
+            GT* const wkb = static_cast<GT*>(a.wk_out) + (size_t)r.b * Taps<GT>::image_elems(NT, HW);
+            const float u = kxk_fma_pixel<K, GT, ST, BLEND>(a.g, a.x0, a.sparse, gbase, pbase, p, HW, c, r.R, true, [&](const float (&w)[NT]) {
+                if (s == 1 && own) {
 #pragma unroll
-                    for (int c = 0; c < NT; ++c) { w[c] = ldf<GT>(a.g, gbase + (size_t)c * HW + p); mx = fmaxf(mx, w[c]); }
-#pragma unroll
-                    for (int c = 0; c < NT; ++c) { w[c] = softmax_exp<GT>(w[c] - mx); den += w[c]; }
-                    const float inv = reciprocal_refined(den);
-                    float m = 0.f;
-                    if (BLEND) m = sgnf(ldf<ST>(a.sparse, pbase + p));
-#pragma unroll
-                    for (int c = 0; c < NT; ++c) {
-                        w[c] = softmax_weight<GT>(w[c], inv);
-                        if (s == 1 && own) stf(wkb, Taps<GT>::idx(c, p, HW), w[c]);      // the published taps: before the fold
-                        if (BLEND) w[c] = round_to<GT>(w[c] * (1.f - m));
-                    }
-#pragma unroll
-                    for (int c = 0; c < NT; ++c) {
-                        const int lin = c < NT / 2 ? c : c + 1, dy = lin / K - RK, dx = lin % K - RK;
-                        u = fmaf(w[c], cur[(ry + dy) * R + rx + dx], u);
-                    }
-                    if (BLEND) u = __fadd_rn(u, __fmul_rn(m, ldf<ST>(a.x0, pbase + p)));
-                    asm volatile("" : "+v"(u));                  // (no fma + cvt fusion: cspnk_resident_repair has the note)
-                    u = round_to<ST>(u);
-                    if (own) stf(static_cast<ST*>(a.hist) + (size_t)(s - 1) * plane + pbase, p, u);
+                    for (int j = 0; j < NT; ++j) stf(wkb, Taps<GT>::idx(j, p, HW), w[j]);
                 }
-                nxt[ry * R + rx] = u;
-            }
-            __syncthreads();
-            float* tmp = cur; cur = nxt; nxt = tmp;
-        }
-    }
+            });
+            if (own) stf(static_cast<ST*>(a.hist) + (size_t)(s - 1) * plane + pbase, p, u);
+            return u;
+        },
+        [](const Region&, int, int, float) {});
 }
 
 // Guard of cspnk_transposed_resident: G_t = stencil^T((1-m) G_{t+1}) with the transposed taps w_{NT-1-j}[p + off_j] read from the forward's
@@ -440,72 +405,58 @@ __global__ __launch_bounds__(REP_THREADS) void cspnk_history_repair(const KHistR
 // receives G_{T-1} .. G_0 (the UNMASKED G_t; what travels is (1-m) G_t), g32_out — when given — G_T as fp32.  The arithmetic of
 // cspnk_resident<TRANS>, i.e. of cspn_transpose_weights + cspn_propagate (history, CSPN_BLEND_PREMASK), bit for bit.
 struct KSweepRepArgs {
+    GuardGeom t;
     const void* wk; const void* g_T; const void* sparse; float* g32_out; float* hist;
-    const unsigned* abort_word; unsigned seq;
-    int B, H, W, T, tiles_x, tiles_y;
 };
 
 template <int K, typename WT, typename INT, int PREMASK>
 __global__ __launch_bounds__(REP_THREADS) void cspnk_sweep_repair(const KSweepRepArgs a) {
-    if (__hip_atomic_load(a.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.seq) return;
-    constexpr int RK = K / 2, NT = K * K - 1;
+    if (guard_idle(a.t)) return;
+    constexpr int NT = K * K - 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int T = a.T, HALO = T * RK, R = REP_TILE + 2 * HALO, H = a.H, W = a.W;
-    float* cur = lds;
-    float* nxt = lds + (size_t)R * R;
-    const int tiles = a.tiles_x * a.tiles_y;
-    const size_t HW = (size_t)H * W, plane = (size_t)a.B * HW;
-    for (int t = blockIdx.x; t < a.B * tiles; t += gridDim.x) {
-        const int b = t / tiles, tr = t - b * tiles, ty = tr / a.tiles_x, tx = tr - ty * a.tiles_x;
-        const int ry0 = ty * REP_TILE - HALO, rx0 = tx * REP_TILE - HALO;
-        const size_t pbase = (size_t)b * HW;
-        const WT* const wkb = static_cast<const WT*>(a.wk) + (size_t)b * Taps<WT>::image_elems(NT, HW);
-        __syncthreads();
-        for (int i = threadIdx.x; i < R * R; i += REP_THREADS) {
-            const int ry = i / R, rx = i - ry * R, y = ry0 + ry, x = rx0 + rx;
-            const bool in = y >= 0 && y < H && x >= 0 && x < W;
-            float v = 0.f;
-            if (in) {
-                const size_t p = (size_t)y * W + x;
-                v = ldf<INT>(a.g_T, pbase + p);
-                if (a.g32_out && ry >= HALO && ry < HALO + REP_TILE && rx >= HALO && rx < HALO + REP_TILE) a.g32_out[pbase + p] = v;
-                if (PREMASK) v = __fmul_rn(v, 1.f - sgnf(ldf<INT>(a.sparse, pbase + p)));
-            }
-            cur[i] = v;
-            nxt[i] = 0.f;
-        }
-        __syncthreads();
-        for (int s = 1; s <= T; ++s) {
-            const int lo = s * RK, n = R - 2 * lo;
-            for (int i = threadIdx.x; i < n * n; i += REP_THREADS) {
-                const int ry = lo + i / n, rx = lo + i % n, y = ry0 + ry, x = rx0 + rx;
-                float u = 0.f;
-                if (y >= 0 && y < H && x >= 0 && x < W) {
-                    const size_t p = (size_t)y * W + x;
+    const int W = a.t.W;
+    const size_t HW = (size_t)a.t.H * W, plane = (size_t)a.t.B * HW;
+    guard_tiles<K / 2>(a.t, lds,
+        [&](const Region& r, int ry, int rx) -> float {
+            const int y = r.y(ry), x = r.x(rx);
+            if (!r.image(y, x)) return 0.f;
+            const size_t p = (size_t)r.b * HW + (size_t)y * W + x;
+            float v = ldf<INT>(a.g_T, p);
+            if (a.g32_out && r.own(ry, rx)) a.g32_out[p] = v;
+            if (PREMASK) v = __fmul_rn(v, 1.f - sgnf(ldf<INT>(a.sparse, p)));
+            return v;
+        },
+        [&](const Region& r, int s, int ry, int rx, const float* c) -> float {
+            const int y = r.y(ry), x = r.x(rx);
+            if (!r.image(y, x)) return 0.f;
+            const size_t p = (size_t)r.b * HW + (size_t)y * W + x;
+            const WT* const wkb = static_cast<const WT*>(a.wk) + (size_t)r.b * Taps<WT>::image_elems(NT, HW);
+            float u = 0.f;
 #pragma unroll
-                    for (int c = 0; c < NT; ++c) {
-                        const int lin = c < NT / 2 ? c : c + 1, dy = lin / K - RK, dx = lin % K - RK;
-                        const int ys = y + dy, xs = x + dx;
-                        const bool tin = ys >= 0 && ys < H && xs >= 0 && xs < W;
-                        const float wt = tin ? ldf<WT>(wkb, Taps<WT>::idx(NT - 1 - c, (size_t)ys * W + xs, HW)) : 0.f;
-                        u = fmaf(wt, cur[(ry + dy) * R + rx + dx], u);
-                    }
-                    if (ry >= HALO && ry < HALO + REP_TILE && rx >= HALO && rx < HALO + REP_TILE) a.hist[(size_t)(s - 1) * plane + pbase + p] = u;
-                    if (PREMASK) u = __fmul_rn(1.f - sgnf(ldf<INT>(a.sparse, pbase + p)), u);
-                }
-                nxt[ry * R + rx] = u;
+            for (int j = 0; j < NT; ++j) {
+                const int ys = y + tap_dy<K>(j), xs = x + tap_dx<K>(j);
+                const float wt = r.image(ys, xs) ? ldf<WT>(wkb, Taps<WT>::idx(NT - 1 - j, (size_t)ys * W + xs, HW)) : 0.f;
+                u = fmaf(wt, c[tap_dy<K>(j) * r.R + tap_dx<K>(j)], u);
             }
-            __syncthreads();
-            float* tmp = cur; cur = nxt; nxt = tmp;
-        }
-    }
+            if (r.own(ry, rx)) a.hist[(size_t)(s - 1) * plane + p] = u;
+            if (PREMASK) u = __fmul_rn(1.f - sgnf(ldf<INT>(a.sparse, p)), u);
+            return u;
+        },
+        [](const Region&, int, int, float) {});
 }
 
 }  // namespace
 
 namespace cspn_detail {
 
-bool resident_repair_fits(int T) { return T >= 1 && (size_t)2 * (REP_TILE + 2 * T) * (REP_TILE + 2 * T) * sizeof(float) <= 160 * 1024; }
+// The guard's LDS: two fp32 planes of the region, R = tile + 2 halo pixels wide, within the 160 KB of a CU; 0 where there is no fit.
+static size_t repair_lds_bytes(int K, int T) {
+    const long R = REP_TILE + 2L * T * (K / 2);
+    const size_t bytes = T >= 1 && R <= 1024 ? (size_t)2 * R * R * sizeof(float) : 0;      // (R bounded first: no overflow for any T)
+    return bytes <= 160 * 1024 ? bytes : 0;
+}
+bool resident_repair_fits(int T) { return repair_lds_bytes(3, T) != 0; }
+bool kres_repair_fits(int K, int T) { return (K == 3 || K == 5) && repair_lds_bytes(K, T) != 0; }
 
 // A few workgroups that loop over the tiles: the success path — every launch of a healthy deployment — is `grid` workgroups
 // that read one word and return, and its cost is their dispatch (rocprofv3, config 2's training step: 5.1 us with one workgroup
@@ -515,12 +466,23 @@ static int guard_grid(int n_tiles, int n_cu) {
     return n_tiles > cap ? cap : n_tiles;
 }
 
+static GuardGeom guard_geom(const unsigned* abort_word, unsigned seq, int B, int H, int W, int T) { return {abort_word, seq, B, H, W, T, 0, 0}; }
+
+// the launch of a guard kernel for K x K stencils: the tiling, the grid and the LDS of a.t
+template <int K, auto Kern, typename Args>
+static int guard_launch(Args a, int n_cu, void* stream) {
+    a.t.tiles_x = ceil_div(a.t.W, REP_TILE);
+    a.t.tiles_y = ceil_div(a.t.H, REP_TILE);
+    const int grid = guard_grid(a.t.B * a.t.tiles_x * a.t.tiles_y, n_cu);
+    return launch_dynamic_lds<Kern>(grid, REP_THREADS, repair_lds_bytes(K, a.t.T), static_cast<hipStream_t>(stream), a);
+}
+
 // the guard's instance per (blend, form); null where it has none (resident_form_guarded)
-using RepLaunchFn = int (*)(int, int, size_t, hipStream_t, const RepArgs&);
+using RepLaunchFn = int (*)(RepArgs, int, void*);
 template <int BLEND, int F>
 constexpr RepLaunchFn rep_instance() {
     constexpr ResidentForm f = static_cast<ResidentForm>(F);
-    if constexpr (resident_form_guarded(f)) return &launch_dynamic_lds<cspn3_resident_repair<BLEND, resident_form_mode(f), resident_form_pac(f)>, RepArgs>;
+    if constexpr (resident_form_guarded(f)) return &guard_launch<3, cspn3_resident_repair<BLEND, resident_form_mode(f), resident_form_pac(f)>, RepArgs>;
     else return nullptr;
 }
 template <int BLEND, int... F>
@@ -534,21 +496,14 @@ int resident_repair_launch(const float* g, long bs, long cs, const float* d0, co
     if (!resident_repair_fits(T)) return fail("cspn3_forward_resident: the guard re-computes at most 54 steps (T=%d)", T);
     const RepLaunchFn launch = form < ResidentForm::Count ? instances[blend ? 1 : 0][(int)form] : nullptr;
     if (!launch) return fail("cspn3_forward_resident: the guard has no form for this launch");
-    RepArgs a{g, bs, cs, d0, sparse, out, hist, s_out, w_out, s_in, target, acc, nslots > 0 ? nslots : 1, abort_word, seq, B, H, W, Wv, T, ceil_div(W, REP_TILE), ceil_div(H, REP_TILE)};
-    const size_t lds = (size_t)2 * (REP_TILE + 2 * T) * (REP_TILE + 2 * T) * sizeof(float);
-    return launch(guard_grid(B * a.tiles_x * a.tiles_y, n_cu), REP_THREADS, lds, static_cast<hipStream_t>(stream), a);
-}
-
-
-bool kres_repair_fits(int K, int T) {
-    const int R = REP_TILE + 2 * T * (K / 2);
-    return T >= 1 && (K == 3 || K == 5) && (size_t)2 * R * R * sizeof(float) <= 160 * 1024;
+    return launch(RepArgs{guard_geom(abort_word, seq, B, H, W, T), g, bs, cs, d0, sparse, out, hist, s_out, w_out, s_in, target, acc, nslots > 0 ? nslots : 1, Wv},
+                  n_cu, stream);
 }
 
 template <int K, typename GT, typename ST, int D2 = 0>
-static int kres_repair_launch_t(const KRepArgs& a, int blend, size_t lds, int grid, hipStream_t st) {
-    return blend ? launch_dynamic_lds<cspnk_resident_repair<K, GT, ST, 1, D2>>(grid, REP_THREADS, lds, st, a)
-                 : launch_dynamic_lds<cspnk_resident_repair<K, GT, ST, 0, D2>>(grid, REP_THREADS, lds, st, a);
+static int kres_repair_launch_t(const KRepArgs& a, int blend, int n_cu, void* stream) {
+    return blend ? guard_launch<K, cspnk_resident_repair<K, GT, ST, 1, D2>>(a, n_cu, stream)
+                 : guard_launch<K, cspnk_resident_repair<K, GT, ST, 0, D2>>(a, n_cu, stream);
 }
 
 int kres_repair_launch(const void* g, int g_dtype, int K, const void* x0, const void* sparse, void* out, int state_dtype,
@@ -556,49 +511,38 @@ int kres_repair_launch(const void* g, int g_dtype, int K, const void* x0, const 
                        void* stream) {
     if (!kres_repair_fits(K, T)) return fail("cspnk_forward_resident: the guard re-computes at most T * (K / 2) = 54 halo pixels (K=%d, T=%d)", K, T);
     if (step_form != CSPN_STEP_FMA && step_form != CSPN_STEP_DOT2) return fail("cspnk_forward_resident: the guard needs the launch's step form (%d)", step_form);
-    KRepArgs a{g, x0, sparse, out, abort_word, seq, B, H, W, T, round_every > 0 ? round_every : T, ceil_div(W, REP_TILE), ceil_div(H, REP_TILE)};
-    const int R = REP_TILE + 2 * T * (K / 2);
-    const size_t lds = (size_t)2 * R * R * sizeof(float);
-    const int grid = guard_grid(B * a.tiles_x * a.tiles_y, n_cu);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    const KRepArgs a{guard_geom(abort_word, seq, B, H, W, T), g, x0, sparse, out, round_every > 0 ? round_every : T};
     const bool gh = g_dtype == CSPN_F16, sh = state_dtype == CSPN_F16;
     if (!gh && sh) return fail("cspnk_forward_resident: fp32 guidance with fp16 planes has no kernel");
     if (step_form == CSPN_STEP_DOT2 && !(K == 5 && gh && sh)) return fail("cspnk_forward_resident: the dot-product form is K = 5 with fp16 guidance and planes");
     if (K == 3) {
-        if (gh) return sh ? kres_repair_launch_t<3, __half, __half>(a, blend, lds, grid, st) : kres_repair_launch_t<3, __half, float>(a, blend, lds, grid, st);
-        return kres_repair_launch_t<3, float, float>(a, blend, lds, grid, st);
+        if (gh) return sh ? kres_repair_launch_t<3, __half, __half>(a, blend, n_cu, stream) : kres_repair_launch_t<3, __half, float>(a, blend, n_cu, stream);
+        // (cspnk_forward_resident hands K = 3 with fp32 guidance to the quad kernel, whose guard is resident_repair_launch's softmax form)
+        return fail("cspnk_forward_resident: K = 3 with fp32 guidance is guarded behind the quad kernel's launch");
     }
     // the dot-product form's launch (cspnk_d2.hip) is re-computed with ITS arithmetic; the FMA form's at phase length 1 (T = 1) is not
-    if (step_form == CSPN_STEP_DOT2) return kres_repair_launch_t<5, __half, __half, 1>(a, blend, lds, grid, st);
-    if (gh) return sh ? kres_repair_launch_t<5, __half, __half>(a, blend, lds, grid, st) : kres_repair_launch_t<5, __half, float>(a, blend, lds, grid, st);
-    return kres_repair_launch_t<5, float, float>(a, blend, lds, grid, st);
+    if (step_form == CSPN_STEP_DOT2) return kres_repair_launch_t<5, __half, __half, 1>(a, blend, n_cu, stream);
+    if (gh) return sh ? kres_repair_launch_t<5, __half, __half>(a, blend, n_cu, stream) : kres_repair_launch_t<5, __half, float>(a, blend, n_cu, stream);
+    return kres_repair_launch_t<5, float, float>(a, blend, n_cu, stream);
 }
 
 int kres_history_repair_launch(const void* g, const void* x0, const void* sparse, void* hist, void* wk_out, const unsigned* abort_word, unsigned seq,
                                int B, int H, int W, int T, int blend, int n_cu, void* stream) {
     if (!kres_repair_fits(5, T)) return fail("cspnk_forward_resident_history: the guard re-computes at most 27 steps of a 5 x 5 stencil (T=%d)", T);
-    KHistRepArgs a{g, x0, sparse, hist, wk_out, abort_word, seq, B, H, W, T, ceil_div(W, REP_TILE), ceil_div(H, REP_TILE)};
-    const int R = REP_TILE + 4 * T;
-    const size_t lds = (size_t)2 * R * R * sizeof(float);
-    const int grid = guard_grid(B * a.tiles_x * a.tiles_y, n_cu);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return blend ? launch_dynamic_lds<cspnk_history_repair<5, __half, __half, 1>>(grid, REP_THREADS, lds, st, a)
-                 : launch_dynamic_lds<cspnk_history_repair<5, __half, __half, 0>>(grid, REP_THREADS, lds, st, a);
+    const KHistRepArgs a{guard_geom(abort_word, seq, B, H, W, T), g, x0, sparse, hist, wk_out};
+    return blend ? guard_launch<5, cspnk_history_repair<5, __half, __half, 1>>(a, n_cu, stream)
+                 : guard_launch<5, cspnk_history_repair<5, __half, __half, 0>>(a, n_cu, stream);
 }
 
 int kres_sweep_repair_launch(const void* wk, const void* g_T, const void* sparse, int in_dtype, float* g32_out, float* hist, const unsigned* abort_word,
                              unsigned seq, int B, int H, int W, int T, int premask, int n_cu, void* stream) {
     if (!kres_repair_fits(5, T)) return fail("cspnk_transposed_resident: the guard re-computes at most 27 steps of a 5 x 5 stencil (T=%d)", T);
-    KSweepRepArgs a{wk, g_T, sparse, g32_out, hist, abort_word, seq, B, H, W, T, ceil_div(W, REP_TILE), ceil_div(H, REP_TILE)};
-    const int R = REP_TILE + 4 * T;
-    const size_t lds = (size_t)2 * R * R * sizeof(float);
-    const int grid = guard_grid(B * a.tiles_x * a.tiles_y, n_cu);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    const KSweepRepArgs a{guard_geom(abort_word, seq, B, H, W, T), wk, g_T, sparse, g32_out, hist};
     if (in_dtype == CSPN_F16)
-        return premask ? launch_dynamic_lds<cspnk_sweep_repair<5, __half, __half, 1>>(grid, REP_THREADS, lds, st, a)
-                       : launch_dynamic_lds<cspnk_sweep_repair<5, __half, __half, 0>>(grid, REP_THREADS, lds, st, a);
-    return premask ? launch_dynamic_lds<cspnk_sweep_repair<5, __half, float, 1>>(grid, REP_THREADS, lds, st, a)
-                   : launch_dynamic_lds<cspnk_sweep_repair<5, __half, float, 0>>(grid, REP_THREADS, lds, st, a);
+        return premask ? guard_launch<5, cspnk_sweep_repair<5, __half, __half, 1>>(a, n_cu, stream)
+                       : guard_launch<5, cspnk_sweep_repair<5, __half, __half, 0>>(a, n_cu, stream);
+    return premask ? guard_launch<5, cspnk_sweep_repair<5, __half, float, 1>>(a, n_cu, stream)
+                   : guard_launch<5, cspnk_sweep_repair<5, __half, float, 0>>(a, n_cu, stream);
 }
 
 }  // namespace cspn_detail

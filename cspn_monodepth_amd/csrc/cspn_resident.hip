@@ -379,8 +379,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            const int lin = j < 4 ? j : j + 1;
-            const int d = (PAC || TRANSG) ? 1 : lin / 3;              // PAC / MODE 4: channel j at the quad itself
+            const int d = (PAC || TRANSG) ? 1 : tap_dy<3>(j) + 1;              // PAC / MODE 4: channel j at the quad itself
             const int ch = (PAC || TRANSG) ? j : 7 - j;
             const float4 v = ld4(LEAN ? at32(gq + (size_t)ch * a.g_cs, orow[d]) : at32(gq, (unsigned)ch * ucs + orow[d]));
             wreg[i][j][0] = rokv[d] ? v.x : 0.f; wreg[i][j][1] = rokv[d] ? v.y : 0.f;
@@ -393,8 +392,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
             for (int t = 0; t < 6; ++t) {
                 const bool lft = t < 3;
                 const int j = lft ? (t == 0 ? 0 : (t == 1 ? 3 : 5)) : (t == 3 ? 2 : (t == 4 ? 4 : 7));
-                const int lin = j < 4 ? j : j + 1;
-                const int d = lin / 3;
+                const int d = tap_dy<3>(j) + 1;
                 const int xx = lft ? xq - 1 : xq + 4;
                 const bool c = rokv[d] && (lft ? fix_left : fix_right) && xx >= 0 && xx < W;
                 // raw value only: consuming it here would make this block wait for the quad's loads (in-order return)
@@ -455,8 +453,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
         if constexpr (TRANSG) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                const int lin = j < 4 ? j : j + 1;
-                const int m = i + lin / 3, dx = lin % 3 - 1;
+                const int m = i + tap_dy<3>(j) + 1, dx = tap_dx<3>(j);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int c = e + dx;
@@ -469,7 +466,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
         // does edge[i][t] hold a pixel inside the image?  (recomputed: a bit mask built while the loads are issued is one
         // more live register there)
         auto edge_in = [&](int j, bool lft) -> bool {
-            const int lin = j < 4 ? j : j + 1;
+            const int lin = j < 4 ? j : j + 1;        // (tap_dy<3>(j), spelled out: a call inside this lambda changes the kernel's code)
             const int row = yq0 + i + lin / 3 - 1;
             return ok && row >= 0 && row < H && (lft ? xq - 1 >= 0 : xq + 4 < W);
         };
@@ -494,8 +491,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            const int lin = j < 4 ? j : j + 1;
-            const int dx = lin % 3 - 1;
+            const int dx = tap_dx<3>(j);
             const float q0 = wreg[i][j][0], q1 = wreg[i][j][1], q2 = wreg[i][j][2], q3 = wreg[i][j][3];
             if (dx < 0) {
                 const int t = j == 0 ? 0 : (j == 3 ? 1 : 2);

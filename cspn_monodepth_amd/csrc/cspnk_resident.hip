@@ -177,8 +177,7 @@ __global__ __launch_bounds__(NTH, NTH / 256) void cspnk_resident(const KResArgs 
                 // ([NT/2][HW/4][2][4] halfs): the 8 pixels x+dx .. x+dx+7 of a tap are pieces of two or three quads (8 bytes
                 // each), put together by dword selects (dx even) or 16-bit funnel shifts (dx odd).  Branch-free: safe addresses
                 // + selects, all requested before they are used.
-                const int lin = c < NT / 2 ? c : c + 1;
-                const int dy = lin / K - R, dx = lin % K - R;
+                const int dy = tap_dy<K>(c), dx = tap_dx<K>(c);
                 const int cs = NT - 1 - c;
                 const int ys = y + dy;
                 const bool rok = ok && ys >= 0 && ys < H;

@@ -468,7 +468,10 @@ def test_unet_ours_configuration_is_guarded_on_the_device(B, H, W, T, sparse, c_
 
 
 KGUARD = [(5, 24, 228, 304, 12, "f16", None), (5, 24, 228, 304, 12, "f16", torch.float32), (5, 3, 228, 304, 12, "f16", None),
-          (3, 4, 60, 72, 24, "f16", None), (5, 2, 40, 64, 9, "f32", None), (5, 1, 352, 1216, 12, "f16", None), (3, 2, 37, 40, 6, "f16", torch.float32)]
+          (3, 4, 60, 72, 24, "f16", None), (5, 2, 40, 64, 9, "f32", None), (5, 1, 352, 1216, 12, "f16", None), (3, 2, 37, 40, 6, "f16", torch.float32),
+          # (the fp32-guidance and the K = 3 fp32-plane instances of the guard at sizes where one poll does make the launch give up: at
+          #  2 x 40 x 64 and 2 x 37 x 40 the neighbours' flags are usually there at the first look, and the call finishes on its own)
+          (5, 3, 228, 304, 12, "f32", None), (3, 4, 60, 72, 24, "f16", torch.float32)]
 
 
 @pytest.mark.parametrize("K,B,H,W,T,gd,state", KGUARD, ids=["%dx%dx%dx%dx%d_%s_%s" % (c[0], c[1], c[2], c[3], c[4], c[5], "s32" if c[6] is not None else "s") for c in KGUARD])

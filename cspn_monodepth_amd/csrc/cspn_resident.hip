@@ -25,6 +25,13 @@
 // 2 x (2.6 us exchange + 1.35 us halo staging), fused metrics 3.6 us + launch ~2 us: 46 us per scored forward against 73 us for
 // the three S=8 launches, with 2.3x less HBM traffic.
 //
+// The 768-thread instances (config 2 today: 3 quads per thread on clipped regions, three wavefronts per SIMD) publish their borders INSIDE
+// the last step of a phase: a peeled form of the step body stores every interior row to the exchange plane right behind the row's
+// ds_write, waits for vmcnt(0) in front of its closing barrier, and that barrier stands for "everybody's stores have landed" — no
+// separate publish pass, one barrier less per boundary, the store acknowledge under the FMAs of the rows that follow (exchange 2.5 ->
+// 1.45 us, the scored forward 40.0-40.2 -> 39.0-39.2 us, sparse 45.9-46.0 -> 43.5-43.8: profiles/r15_boundary_ab.txt).  The same
+// instances stamp their tail (target consumed, sums added) for tools/resident_stamps.py.  The 512- / 1024-thread instances keep their code.
+//
 // What keeps the 256-VGPR instances spill-free (each item was a measured regression before it was written this way):
 //   * every scratch reload inside the derive is an s_waitcnt vmcnt(0) in the middle of the in-order guidance stream, so
 //     the derive carries nothing it does not need: loads / stores go through an SGPR base + 32-bit byte offset in address
@@ -673,8 +680,18 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
         }
         // One propagation step on the LDS tile.  FINAL (the very last step of the forward) is peeled into its own copy so
         // that the target quads of the fused metrics are only live there, not across the hot loop.
-        auto step = [&](auto final_c, auto on_c, auto par_c, int final_par) __attribute__((always_inline)) {
-            constexpr bool FINAL = decltype(final_c)::value;
+        // PUBLISH (form 2, the 768-thread instances only): the last step of a phase that is not the last one, peeled as well.  It stores
+        // every interior row to the exchange plane right behind the row's ds_write, so that the device-scope acknowledge of row 0
+        // overlaps the FMAs of rows 1 .. NQ-1, and its closing barrier — behind s_waitcnt vmcnt(0) — IS "everybody's stores have
+        // landed": the separate publish pass, its wait and its barrier are gone.  Storing that early is safe by the argument the
+        // exchange already makes: a tile is in phase p only after all eight neighbours have flagged phase p - 1, so they have finished
+        // reading plane p & 1 (they read it while staging phase p - 1).
+        // (The exchange plane comes in as a trailing argument of that form alone: the lambda of the other instances then captures what it
+        // always did, and the 512- / 1024-thread instances compile to the code they had.)
+        auto step = [&](auto form_c, auto on_c, auto par_c, int final_par, float* xpub = nullptr) __attribute__((always_inline)) {
+            constexpr int FORM = (int)decltype(form_c)::value;  // 0 (std::false_type): plain, 1 (std::true_type): FINAL, 2: PUBLISH
+            constexpr bool FINAL = FORM == 1, PUBLISH = FORM == 2;
+            static_assert(!PUBLISH || (LEAN && !HIST), "the publishing step belongs to the 768-thread inference instances");
             constexpr int PAR = decltype(par_c)::value;       // buffer this step reads (the final step: `final_par`)
             if (decltype(on_c)::value) {
                 float win[NQ + 2 * R][WIN];
@@ -684,10 +701,11 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
                 // kept (spilled) across the hot loop
                 int r0x = r0L, yqx = yq0L;
                 if (FINAL) asm volatile("" : "+v"(r0x), "+v"(yqx));
+                if (PUBLISH) asm volatile("" : "+v"(yqx));      // (its rows are the hot loop's: only the pixel offset is formed here)
                 // ... and ONE pixel offset for its stores: formed per row from the strip coordinates, a spilled coordinate was reloaded from
                 // scratch — with a wait for the reload — in front of every row's store (5 x ~0.7 us in the blended scored instance: round 6)
                 unsigned o0x = 0u;
-                if (FINAL && !HIST) { o0x = (unsigned)(yqx * W + xqL); asm volatile("" : "+v"(o0x)); }
+                if ((FINAL && !HIST) || PUBLISH) { o0x = (unsigned)(yqx * W + xqL); asm volatile("" : "+v"(o0x)); }
                 auto row_ptr = [&](int rr) -> const float* {
                     int drow = r0x + rr;
                     drow = drow < dr ? drow : dr - 1;
@@ -763,14 +781,21 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
                         } else if (FINAL && ((interior >> i) & 1u)) {
                             st4(at32(dout, o0x + (unsigned)(i * W)), make_float4(u[0], u[1], u[2], u[3]));
                         }
+                        if constexpr (PUBLISH) {
+                            if ((interior >> i) & 1u) st4_dev(xpub, o0x + (unsigned)(i * W), keep[0], keep[1], keep[2], keep[3]);
+                        }
                     }
                 }
             }
             if (HIST) hist_step += plane;
+            // PUBLISH: this thread's device-scope stores have landed before it arrives, so behind the barrier everybody's have
+            if (PUBLISH) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (!FINAL) __syncthreads();
         };
         stamp();                               // depth staged
-        const int plain_steps = last_phase ? steps - 1 : steps;
+        // (768 threads: a phase that is not the last one ends in the peeled publishing step.  Such a phase has an even number of steps, so
+        // that step always reads buffer 1: pairs, one single step, then the peeled one)
+        const int plain_steps = (LEAN || last_phase) ? steps - 1 : steps;
         // Wavefronts without a single owned row (the tail of the last row group) only keep the barriers company.  The test is
         // wave-uniform (a scalar branch), and the step loop sits INSIDE it: a per-step `if (active)` makes every carried quad
         // a phi of "old" and "new" that is resolved with 20 v_mov per step.  Idle lanes of a working wavefront run the
@@ -778,6 +803,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
         // quads alternate between two register sets.
         using P0 = std::integral_constant<int, 0>;
         using P1 = std::integral_constant<int, 1>;
+        using PublishStep = std::integral_constant<int, 2>;
         if (__ballot(active) != 0ull) {
             int s = 0;
             for (; s + 1 < plain_steps; s += 2) {
@@ -786,13 +812,18 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
             }
             if (s < plain_steps) step(std::false_type{}, std::true_type{}, P0{}, 0);
             if (last_phase) step(std::true_type{}, std::true_type{}, P0{}, plain_steps & 1);
+            if constexpr (LEAN) {
+                if (!last_phase) step(PublishStep{}, std::true_type{}, P1{}, 0, uniform_ptr(a.xbuf + (size_t)(p & 1) * plane + (size_t)b * HW));
+            }
         } else {
             for (int s = 0; s < plain_steps; ++s) step(std::false_type{}, std::false_type{}, P0{}, 0);
             if (last_phase) step(std::true_type{}, std::false_type{}, P0{}, 0);
+            if constexpr (LEAN) { if (!last_phase) step(PublishStep{}, std::false_type{}, P1{}, 0); }
         }
         stamp();                               // steps of the phase done
         if (!last_phase) {
             // -- publish the interior quads (device scope), then the phase flag; wait for the 8 neighbouring tiles
+            if constexpr (!LEAN) {                 // (768 threads: published inside the phase's last step, see `step`)
             float* __restrict__ xout = uniform_ptr(a.xbuf + (size_t)(p & 1) * plane + (size_t)b * HW);
             if (active) {
                 // (opaque to the optimiser: the per-quad offsets are recomputed here, not hoisted out of the phase loop into
@@ -813,6 +844,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this thread's device-scope stores have landed
             __syncthreads();                                       // ... and so have everybody else's in the workgroup
+            }
             const unsigned want = a.seq + (unsigned)p + 1u;
             if (tid == 0) __hip_atomic_store(a.flags + tile_global, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (tid < 9 && tid != 4) {
@@ -868,7 +900,9 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
         for (int k = 0; k < 10; ++k) mf[k] = 0.f;
         if (active) {
             // the target quads are requested only now: the weight registers are dead, nothing spills, and the one exposed
-            // round trip costs less than carrying NQ quads through the final step did
+            // round trip costs less than carrying NQ quads through the final step did.  (Requested inside the peeled final step of the
+            // 768-thread instances, behind row 0 — 32 dead tap registers there — they do not stay inside that copy: the compiler carries
+            // the 12 registers around the phase loop whichever way the loop is left, 43-52 spilled VGPRs against 1: NEGATIVE_RESULTS #62.)
             float4 scored_t[NQ];
             const float* tgt_b = uniform_ptr(a.target + (size_t)b * HW);
             unsigned o0s = (unsigned)(yq0L * W + xqL);       // one offset for all rows (see the final step's stores)
@@ -889,6 +923,7 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
                 }
             }
         }
+        if constexpr (LEAN) stamp();           // target there (thread 0 has consumed its quads)
         float* part = lds + RES_PP + (size_t)a.dr * a.ls + (size_t)(BLEND ? 1 : 0) * NTHREADS * NQ * 4;
         const int wave = tid >> 6;
         __syncthreads();
@@ -902,6 +937,10 @@ __global__ __launch_bounds__(NTHREADS, NTHREADS / 256) void cspn3_resident(const
             double v = 0.0;
             for (int w = 0; w < NTHREADS / 64; ++w) v += (double)part[w * 10 + tid];
             if (v != 0.0) atomicAdd(a.macc + (size_t)(blockIdx.x % a.nslots) * 10 + tid, v);
+        }
+        if constexpr (LEAN) {
+            if (a.dbg) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the probe only: the stamp below is taken when the additions are acknowledged)
+            stamp();                           // sums added
         }
     }
     count_out();

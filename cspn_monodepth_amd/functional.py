@@ -57,6 +57,12 @@ def set_event_log(log):
     _EVENT_LOG = log
 
 
+def _sampled_log():
+    """The event log if there is one and it samples this call, else None: THE sampling decision — a call asks exactly once."""
+    log = _EVENT_LOG
+    return log if log is not None and log.take() else None
+
+
 _RESOLVED = {}       # (K,B,H,W,T,history,plan items) -> resolved plan dict (cspn_plan_resolve is pure)
 
 
@@ -313,9 +319,7 @@ def propagate(w, d0, sparse, K, T, blend, keep_history=False, plan=None, valid_w
         nbytes = L.cspn_propagate_workspace_bytes(B, H, W, T, _dt(d0), 0)
         if nbytes:
             work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    log = _EVENT_LOG
-    if log is not None and not log.take():
-        log = None
+    log = _sampled_log()
     with _device_guard(dev):
         if log is not None:
             ev0, ev1 = log.pair()
@@ -365,9 +369,7 @@ def propagate_scored(w, d0, sparse, K, T, blend, target, acc, plan=None, valid_w
     out = torch.empty((B, H, W), dtype=d0.dtype, device=dev)
     nbytes = L.cspn_propagate_workspace_bytes(B, H, W, int(T), _dt(d0), 0)
     work = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
-    log = _EVENT_LOG
-    if log is not None and not log.take():
-        log = None
+    log = _sampled_log()
     with _device_guard(dev):
         if log is not None:
             ev0, ev1 = log.pair()
@@ -435,9 +437,7 @@ def propagate_from_guidance(guidance, d0, sparse, T, blend, keep_history=False, 
         nbytes = L.cspn_propagate_workspace_bytes(B, H, W, T, _dt(d0), 0)
         if nbytes:
             work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    log = _EVENT_LOG
-    if log is not None and not log.take():
-        log = None
+    log = _sampled_log()
     with _device_guard(dev):
         if log is not None:
             ev0, ev1 = log.pair()
@@ -464,12 +464,14 @@ def propagate_from_guidance(guidance, d0, sparse, T, blend, keep_history=False, 
 # this module serialises them: a lock around (order after the previous resident launch's stream, launch), per device.
 #
 # Reader's map of the host protocol below (it is the largest part of this file; each piece has one job):
-#   _resident_state(dev)      per-device dict: launch lock, workspaces per shape, sequence number, the pinned error /
-#                             completion words the kernels write (host_err), the journal
-#   _resident_launch(...)     the ONE place a resident C entry is called from: error word looked at first (-> _recover),
-#                             workspace, stream ordering, sequence number, then either `guarded` (count only) or a journal entry
+#   _resident_state(dev)      per-device dict (_new_state: every key, with its neutral value): launch lock, workspaces per shape,
+#                             sequence number, the pinned error / completion words the kernels write (host_err), the journal
+#   _issue(...)               the ONE locked issue sequence: error word looked at first (-> _recover), workspace and stream ordering,
+#                             sequence number, event-log pair, the C call, then either a count (guarded) or a journal entry
+#   _resident_launch(...)     the general way into _issue: sampling decision, HIP-graph capture, lock, device switch, the check of
+#                             the C entry's answer.  _ScoredFast.issue (cspn3_refine_and_score) is the lean way in
 #   guard (plan.guard)        device side, csrc/cspn_repair.hip: a timed-out call is re-computed on the stream before anything can
-#                             read it — every unscored call; such launches leave NO host state behind
+#                             read it — every unscored call (_guard_default is the rule); such launches leave NO host state behind
 #   _JournalEntry / _journal_add / _recover    host side, for what carries no guard (the scored forward by default, anything with
 #                             set_resident_guard(False)): weak references to a call's tensors + how to redo it; _recover re-runs
 #                             exactly the entries whose output holds the poison pattern, or raises for training forms
@@ -477,7 +479,8 @@ def propagate_from_guidance(guidance, d0, sparse, T, blend, keep_history=False, 
 #                             the host-side touch-points where the error word is looked at (metric gather, graph replays, the
 #                             end of an UNGUARDED backward pass)
 #   forward_resident, transposed_resident(_guidance), pac_forward_resident(_history), pac_transposed_resident
-#                             one thin function per C entry: plan + guard decision, the launch closure, _resident_launch
+#                             one thin function per C entry: outputs, plan, the launch closure, one _resident_launch (_redo3: the
+#                             3x3 repair closure, also the lean path's; _kxk_workspace: the workspace of the K x K entries)
 _RESIDENT_MODE = os.environ.get("CSPN_RESIDENT", "auto")      # "auto" | "on" | "off"
 _RES = {}                 # device index -> state dict (each with its OWN launch lock: devices never serialise each other)
 _RES_NEW_LOCK = threading.Lock()      # guards the creation of a device's state only
@@ -522,12 +525,22 @@ _RESIDENT_SPIN_LIMIT = 0   # test hook: polls before a neighbour wait gives up (
 # gathers the metrics; it costs the headline path the same 1-2 us per call, which is why it is not the default.
 _RESIDENT_GUARD = {"0": False, "all": "all"}.get(os.environ.get("CSPN_RESIDENT_GUARD", "1"), True)
 _GUARD_MAX_T = 54
+_GUARDED_HISTORY_FORMS = frozenset(((3, torch.float32), (5, torch.float16)))      # (K, guidance dtype) of the K x K training forwards that have a guard kernel
 
 
 def set_resident_guard(enabled):
     """True (default): every unscored resident call carries the device-side guard; "all": the scored forward too; False: none."""
     global _RESIDENT_GUARD
     _RESIDENT_GUARD = "all" if enabled == "all" else bool(enabled)
+
+
+def _guard_default(halo, policy="plain"):
+    """Does a call carry the device-side guard when its caller does not say (1 / 0)?  halo: what the re-computation needs around a
+    tile, which must fit the guard kernel's LDS tile — T pixels for the 3x3 entries, T * (K // 2) for the K x K ones; policy: "plain"
+    = whenever the switch is on (every unscored call), "scored" = only under set_resident_guard("all") (the 3x3 scored forward),
+    "never" (the K x K scored forward, a history form outside _GUARDED_HISTORY_FORMS)."""
+    switch = _RESIDENT_GUARD
+    return int(bool(switch) and halo <= _GUARD_MAX_T and (policy == "plain" or (policy == "scored" and switch == "all")))
 
 
 def set_resident(mode):
@@ -567,17 +580,24 @@ def resident_plan(B, H, W, T, blend=0, n_cu=0, steps_per_phase=0, threads=0):
     return {name: getattr(rp, name) for name, _ in _lib.cspn_resident_plan._fields_}
 
 
+def _new_state(host_err, n_cu):
+    """A device's state: EVERY key this module uses, at its neutral value (needs no device: host_err is any int32 [4] tensor).
+    last_*: the newest launch; journal / lost / marks / mark_pool / jcount: _journal_add; guarded_pending: launches since the last
+    clean check that carried their own guard; need_bwd_check: an unguarded training-form launch awaits the end of backward."""
+    return dict(seq=_RES_SEQ_STEP, work={}, host_err=host_err, host_err_np=host_err.numpy(),
+                host_err_ptr=ctypes.c_void_p(host_err.data_ptr()), dirty=False, last_stream=None, last_raw=None, n_cu=n_cu,
+                lock=threading.RLock(), journal=[], lost=False, last_seq=None, last_reports=False, marks=[], mark_pool=[],
+                jcount=0, guarded_pending=0, need_bwd_check=False)
+
+
 def _resident_state(dev):
     st = _RES.get(dev.index)
     if st is None:
         with _RES_NEW_LOCK:
             st = _RES.get(dev.index)
             if st is None:
-                host_err = torch.zeros(4, dtype=torch.int32).pin_memory()
-                st = _RES[dev.index] = dict(seq=_RES_SEQ_STEP, work={}, host_err=host_err, host_err_np=host_err.numpy(),
-                                            host_err_ptr=ctypes.c_void_p(host_err.data_ptr()), dirty=False, last_stream=None,
-                                            n_cu=torch.cuda.get_device_properties(dev).multi_processor_count,
-                                            lock=threading.RLock(), journal=[], lost=False, last_seq=None, last_reports=False)
+                st = _RES[dev.index] = _new_state(torch.zeros(4, dtype=torch.int32).pin_memory(),
+                                                  torch.cuda.get_device_properties(dev).multi_processor_count)
     return st
 
 
@@ -609,9 +629,7 @@ POISON_F32, POISON_F16 = 0x7fc0dead, 0x7ead      # include/cspn_hip.h: CSPN_POIS
 def _holds_poison(t):
     """Does `t` hold the NaN pattern a tile that gave up writes (CSPN_POISON_*)?  Exact: no arithmetic produces that payload, so a
     NaN the recurrence itself produced (0/0 at an all-zero gate pixel, as in the reference) is not mistaken for a failed tile."""
-    if t.dtype == torch.float32:
-        return bool((t.view(torch.int32) == POISON_F32).any())
-    return bool((t.view(torch.int16) == POISON_F16).any())
+    return bool(_poison_mask(t).any())
 
 
 def _poison_mask(t):
@@ -705,15 +723,11 @@ def _recover(dev, st):
             last.synchronize()                     # every journaled launch has finished: its outputs may be rewritten
         st["host_err_np"][0] = 0
         st["dirty"] = False
-        journal, st["journal"] = st["journal"], []
-        lost, st["lost"] = st["lost"], False
-        st.setdefault("mark_pool", []).extend(ev for _, ev in st.get("marks", []))
-        st["marks"] = []
-        stale = []
-        training = False
         # launches that carried their own guard (cspn_resident_plan.guard) left no entry: if it was one of them, its guard kernel has
         # re-computed the result on the stream already
-        repaired, st["guarded_pending"] = st.get("guarded_pending", 0), 0
+        journal, lost, repaired = list(st["journal"]), st["lost"], st["guarded_pending"]
+        _journal_clear(st)
+        stale, training = [], False
         with _device_guard(dev):
             for e in journal:
                 if e.redo is None:
@@ -754,6 +768,30 @@ def _recover(dev, st):
 _JOURNAL_STRONG_BYTES = 256 << 20     # tensors of unchecked launches held strongly (the newest entries; at least the last two)
 
 
+def _journal_demote(j):
+    """Demote what the newest entries of journal `j` (a list, oldest first) push past _JOURNAL_STRONG_BYTES: a walk from the newest
+    entry back, up to the first inference entry an earlier walk demoted.  Training-form entries (redo None: weak from birth, holding
+    nothing) are passed over — one of them between strong inference entries must not end the walk and keep the older ones pinned."""
+    strong = 0
+    for k in range(len(j) - 1, -1, -1):
+        e = j[k]
+        if e.redo is None:
+            continue
+        if e.weak:
+            break
+        strong += e.nbytes
+        if k < len(j) - 2 and strong > _JOURNAL_STRONG_BYTES:
+            e.demote()
+
+
+def _journal_clear(st):
+    del st["journal"][:]
+    st["lost"] = False
+    st["guarded_pending"] = 0
+    st["mark_pool"].extend(ev for _, ev in st["marks"])
+    st["marks"] = []
+
+
 def _journal_add(dev, st, entry, stream):
     """Remember how to repair the launch just issued on `stream`.  The journal never loses an entry that may still fail: every
     16th launch records an event behind itself, every add drops what lies before the marks that have completed (a poll, no
@@ -764,18 +802,11 @@ def _journal_add(dev, st, entry, stream):
     per scored forward.)"""
     j = st["journal"]
     j.append(entry)
-    strong = 0
-    for k in range(len(j) - 1, -1, -1):            # newest first
-        e = j[k]
-        if e.weak:
-            break
-        strong += e.nbytes
-        if k < len(j) - 2 and strong > _JOURNAL_STRONG_BYTES:
-            e.demote()
-    st["jcount"] = n = st.get("jcount", 0) + 1
-    marks = st.setdefault("marks", [])
+    _journal_demote(j)
+    st["jcount"] = n = st["jcount"] + 1
+    marks = st["marks"]
     if n % 16 == 0:
-        pool = st.setdefault("mark_pool", [])
+        pool = st["mark_pool"]
         ev = pool.pop() if pool else torch.cuda.Event()
         ev.record(stream)
         marks.append([len(j), ev])
@@ -879,14 +910,6 @@ def resident_supported(guidance, d0, sparse, T, plan=None, target=None):
     return _resident_plan_cached(B, H, W, int(T), int(sparse is not None), guidance.device)[0]
 
 
-def _journal_clear(st):
-    del st["journal"][:]
-    st["lost"] = False
-    st["guarded_pending"] = 0
-    st.setdefault("mark_pool", []).extend(ev for _, ev in st.get("marks", []))
-    st["marks"] = []
-
-
 def check_resident_errors(dev=None):
     """If a resident launch on `dev` (default: every device used so far) gave up waiting for a neighbouring tile — its workgroups
     were not co-resident because something else held the GPU — repair the journaled inference calls in place (see the note at
@@ -915,7 +938,7 @@ def ensure_resident_ok(dev=None):
             st["dirty"] = False
         if st["host_err_np"][0] != 0:
             _recover(torch.device("cuda", idx), st)
-        elif st["journal"] or st.get("guarded_pending"):
+        elif st["journal"] or st["guarded_pending"]:
             with st["lock"]:
                 if st["host_err_np"][0] == 0 and not st["dirty"]:      # everything issued so far has finished cleanly
                     _journal_clear(st)
@@ -945,7 +968,7 @@ class _ResidentCheckpoint(object):
     def __init__(self, dev):
         self.dev = dev
         st = _resident_state(dev)
-        self.seq = st.get("last_seq")
+        self.seq = st["last_seq"]
         self.stream = st["last_stream"]
 
     def wait_and_check(self, budget_s=20.0):
@@ -979,13 +1002,70 @@ class _ResidentCheckpoint(object):
         check_resident_errors(self.dev)
 
 
-def _resident_launch(dev, B, H, W, T, launch, ws_kind="3", state_bytes=4, ws_bytes_fn=None, reports_done=False, redo=None,
-                     out=None, inputs=(), what="resident launch", guarded=False):
-    """The host protocol of every resident launch on `dev`: one at a time per device (the device's own lock; a launch from
-    another stream first waits for the previous one's stream), a zero-initialised workspace per (B,H,W), a growing flag sequence
-    number, the error word looked at before the call (a time-out of an earlier launch is repaired or raised there: _recover).
-    `launch(work, seq, host_err_ptr, stream_ptr)` makes the C call; `redo()` re-runs the call on the multi-launch schedule into
-    the same outputs (None: the launch cannot be repaired — training forms).
+def _issue(dev, st, raw, log, T, launch, args, reports_done, journal, work=None, ws=None):
+    """The locked issue sequence of every resident launch: the caller holds st["lock"] and has `dev` current; raw: the current
+    stream's handle; log: the event log if this call is sampled.  Error word first (a time-out of an earlier launch is repaired or
+    raised there: _recover); the workspace ws = (B, H, W, kind, state bytes, bytes_fn | None) and the stream order — unless the
+    caller hands in `work`: the lean path, whose bail-out test has settled both —; sequence number, event pair, the C call
+    `launch(work, seq, host_err_ptr, raw, *args)`; then what the host keeps: journal = the _JournalEntry arguments of a call without
+    the device-side guard, None for a guarded one (repaired on the stream: a count, no entry, no tensor kept alive)."""
+    if st["host_err_np"][0] != 0:
+        _recover(dev, st)                               # repairs the journaled calls, or raises
+    if work is not None:
+        cur = st["last_stream"]
+    else:
+        work = st["work"].get(ws[:5])
+        if work is None:
+            if len(st["work"]) > 16:                    # (more than 16 shapes: start the cache over — behind whatever still uses it)
+                if st["last_stream"] is not None:
+                    st["last_stream"].synchronize()
+                st["work"].clear()
+            nbytes = ws[5]() if ws[5] is not None else _lib.lib().cspn3_resident_workspace_bytes(*ws[:3])
+            work = st["work"][ws[:5]] = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+        if raw == st["last_raw"]:
+            cur = st["last_stream"]
+        else:
+            cur = torch.cuda.current_stream(dev)
+            last = st["last_stream"]
+            if last is not None and last != cur:
+                cur.wait_stream(last)                   # resident launches never overlap on a device
+        if st["seq"] > _RES_SEQ_MAX:                    # flag values wrap: start over on clean workspaces (zeroed on `cur`,
+            for w_ in st["work"].values():              # behind every earlier resident launch)
+                w_.zero_()
+            st["seq"] = _RES_SEQ_STEP
+            cur.synchronize()                           # (once per ~8 M calls) the completion word starts over as well
+            st["host_err_np"][1] = 0
+            st["last_seq"] = None                       # ... and a pending checkpoint of the old numbering waits the plain way
+    seq = st["seq"]
+    st["seq"] = seq + _RES_SEQ_STEP
+    if log is not None:
+        ev0, ev1 = log.pair()
+        ev0.record(cur)
+    ok = launch(work, seq, st["host_err_ptr"], raw, *args)
+    if log is not None:
+        ev1.record(cur)
+        log.append((ev0, ev1, 1, T))
+    if ok:                                              # (a call that failed at submit has enqueued nothing)
+        st["last_stream"] = cur
+        st["last_raw"] = raw
+        st["dirty"] = True
+        st["last_reports"] = reports_done
+        if reports_done:                                # training-form launches store `seq` to the completion word
+            st["last_seq"] = seq
+            if journal is not None:                     # ... and an unguarded one must be looked at by the end-of-backward check
+                st["need_bwd_check"] = True
+        if journal is None:
+            st["guarded_pending"] += 1
+        else:
+            _journal_add(dev, st, _JournalEntry(*journal), cur)
+    return ok
+
+
+def _resident_launch(dev, B, H, W, T, launch, name, ws=("3", 4, None), reports_done=False, redo=None, out=None, inputs=(), guarded=False):
+    """The general way into _issue, for the C entry `name`: one launch at a time per device (the device's own lock), on a
+    zero-initialised workspace per (B,H,W) and `ws` = (kind, bytes per state element, bytes_fn | None: the 3x3 engine's size).
+    `launch(work, seq, host_err_ptr, stream_ptr)` makes the C call — a falsy answer raises under `name` —; `redo()` re-runs the call
+    on the multi-launch schedule into the same outputs (None: the launch cannot be repaired — training forms).
 
     Under HIP-graph capture a replay cannot bring a new sequence number, so the capture records a memset of the
     workspace's control words (status + tile flags, a few KB behind the two exchange planes: include/cspn_hip.h) in front
@@ -993,77 +1073,30 @@ def _resident_launch(dev, B, H, W, T, launch, ws_kind="3", state_bytes=4, ws_byt
     the graph's private pool (it lives as long as the graph).  Replays are ordered by their stream like any launch; the
     caller must not replay two graphs holding resident launches concurrently on one device (they could not both be
     co-resident: the bounded wait would flag it)."""
-    log = _EVENT_LOG
-    if log is not None and not log.take():
-        log = None
+    log = _sampled_log()
     idx = dev.index
     if torch._C._cuda_isCurrentStreamCapturing():
-        nbytes = ws_bytes_fn() if ws_bytes_fn is not None else _lib.lib().cspn3_resident_workspace_bytes(B, H, W)
+        nbytes = ws[2]() if ws[2] is not None else _lib.lib().cspn3_resident_workspace_bytes(B, H, W)
         work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        work[(2 * B * H * W * state_bytes + 15) & ~15:].zero_()
+        work[(2 * B * H * W * ws[1] + 15) & ~15:].zero_()
         st = _resident_state(dev)
         with _device_guard(dev):
             cur = torch.cuda.current_stream(dev)
-            return launch(work, _RES_SEQ_STEP, st["host_err_ptr"], cur.cuda_stream)
+            return _lib.check(launch(work, _RES_SEQ_STEP, st["host_err_ptr"], cur.cuda_stream), name)
     st = _RES.get(idx) or _resident_state(dev)
+    journal = None if guarded else (redo, out, inputs, "%s %dx%dx%d" % (name, B, H, W))
     with st["lock"]:
-        if st["host_err_np"][0] != 0:
-            _recover(dev, st)                           # repairs the journaled calls, or raises
-        work = st["work"].get((B, H, W, ws_kind, state_bytes))
-        if work is None:
-            if len(st["work"]) > 16:                    # (more than 16 shapes: start the cache over — behind whatever still uses it)
-                if st["last_stream"] is not None:
-                    st["last_stream"].synchronize()
-                st["work"].clear()
-            nbytes = ws_bytes_fn() if ws_bytes_fn is not None else _lib.lib().cspn3_resident_workspace_bytes(B, H, W)
-            work = st["work"][(B, H, W, ws_kind, state_bytes)] = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
         # (this function is most of the host time of a small call: no context-manager object when `dev` is current already, raw
         #  stream handles, no journal entry for a launch that carries its own guard — tools/probes/r05_host_timing_train.py)
         ctx = None if torch._C._cuda_getDevice() == idx else torch.cuda.device(dev)
         if ctx is not None:
             ctx.__enter__()
         try:
-            raw = torch._C._cuda_getCurrentRawStream(idx)
-            if raw == st.get("last_raw"):
-                cur = st["last_stream"]
-            else:
-                cur = torch.cuda.current_stream(dev)
-                last = st["last_stream"]
-                if last is not None and last != cur:
-                    cur.wait_stream(last)               # resident launches never overlap on a device
-            if st["seq"] > _RES_SEQ_MAX:                # flag values wrap: start over on clean workspaces (zeroed on `cur`,
-                for w_ in st["work"].values():          # behind every earlier resident launch)
-                    w_.zero_()
-                st["seq"] = _RES_SEQ_STEP
-                cur.synchronize()                       # (once per ~8 M calls) the completion word starts over as well
-                st["host_err_np"][1] = 0
-                st["last_seq"] = None                   # ... and a pending checkpoint of the old numbering waits the plain way
-            seq = st["seq"]
-            st["seq"] = seq + _RES_SEQ_STEP
-            if log is not None:
-                ev0, ev1 = log.pair()
-                ev0.record(cur)
-            ok = launch(work, seq, st["host_err_ptr"], raw)
-            if log is not None:
-                ev1.record(cur)
-                log.append((ev0, ev1, 1, T))
-            if ok:                                      # (a call that failed at submit has enqueued nothing)
-                st["last_stream"] = cur
-                st["last_raw"] = raw
-                st["dirty"] = True
-                st["last_reports"] = reports_done
-                if reports_done:                        # training-form launches store `seq` to the completion word
-                    st["last_seq"] = seq
-                    if not guarded:                     # ... and an unguarded one must be looked at by the end-of-backward check
-                        st["need_bwd_check"] = True
-                if guarded:
-                    st["guarded_pending"] = st.get("guarded_pending", 0) + 1      # its guard kernel repairs it on the stream: no entry, no tensor kept alive
-                else:
-                    _journal_add(dev, st, _JournalEntry(redo, out, inputs, what), cur)
+            ok = _issue(dev, st, torch._C._cuda_getCurrentRawStream(idx), log, T, launch, (), reports_done, journal, None, (B, H, W) + ws)
         finally:
             if ctx is not None:
                 ctx.__exit__(None, None, None)
-    return ok
+    _lib.check(ok, name)
 
 
 def _with_spin_limit(cp, step_form=0, guard=0):
@@ -1091,46 +1124,57 @@ def _unscore_failed_launch(out, tg, acc):
     acc[0] -= part
 
 
-def transposed_resident(w8, g_T, sparse_f32, T, valid_w=0):
-    """Reverse sweep of the backward as one weight-resident launch per chunk: ghist [T,B,H,W] (G_{T-1} .. G_0)."""
-    dev = _require_device(w8, g_T, sparse_f32)
+def _redo3(B, H, W, T, blend, valid_w=0, acc=None):
+    """The repair of a 3x3 inference call: the same call on the multi-launch schedule, into the same tensors (bit-identical: DESIGN.md
+    §4.1b) — the journal hands them in (it may hold them weakly).  acc: the accumulator of a scored call, which is re-scored whole."""
+    def redo(out, guidance, d0, sparse, tg):
+        from . import evaluation
+        tgp = None if tg is None else tg.reshape(B, H, W)
+        if acc is not None:
+            _unscore_failed_launch(out, tgp, acc)
+        res, _ = propagate_from_guidance(guidance, d0.reshape(B, H, W), None if sparse is None else sparse.reshape(B, H, W), T, blend,
+                                         valid_w=valid_w)
+        out.copy_(res)
+        if acc is not None:
+            evaluation.metric_sums(out, tgp, out=acc)
+    return redo
+
+
+def _kxk_workspace(B, H, W, state_dt):
+    """`ws` of _resident_launch for the K x K entries; state_dt: the dtype code of the exchange planes."""
+    return "k", 2 if state_dt == CSPN_F16 else 4, lambda: _lib.lib().cspnk_resident_workspace_bytes(B, H, W, state_dt)
+
+
+# (the plan argument of the C entries is the ctypes plan itself, or None: ctypes passes a structure by reference where the
+#  signature says pointer, and None as NULL — the engine then finds its own plan)
+def _transposed3(name, head, dev, g_T, sparse_f32, T, valid_w, _plan=None):
+    """The 3x3 reverse sweep as one weight-resident launch per chunk, by the C entry `name`, whose arguments open with `head` (where
+    the taps come from): ghist [T,B,H,W] (G_{T-1} .. G_0).  _plan: CSPN3Function's fast path, with the guarded plan in hand."""
     B, H, W = g_T.shape
-    L = _lib.lib()
-    ghist = torch.empty((int(T), B, H, W), dtype=torch.float32, device=dev)
-    guard = int(_RESIDENT_GUARD and int(T) <= _GUARD_MAX_T)
-    rp = _with_spin_limit(_resident_plan_cached(B, H, W, int(T), int(sparse_f32 is not None), dev)[1], guard=guard)
+    T, premask = int(T), int(sparse_f32 is not None)
+    cfunc = getattr(_lib.lib(), name)
+    guard = 1 if _plan is not None else _guard_default(T)
+    rp = _plan if _plan is not None else _with_spin_limit(_resident_plan_cached(B, H, W, T, premask, dev)[1], guard=guard)
+    ghist = torch.empty((T, B, H, W), dtype=torch.float32, device=dev)
 
     def launch(work, seq, host_err_ptr, stream_ptr):
-        return L.cspn3_transposed_resident(_p(w8), _p(g_T), _p(sparse_f32), _p(ghist), _p(work), seq, host_err_ptr, B, H, W,
-                                           int(valid_w), int(T), int(sparse_f32 is not None),
-                                           None if rp is None else ctypes.byref(rp), stream_ptr)
+        return cfunc(*head, _p(g_T), _p(sparse_f32), _p(ghist), _p(work), seq, host_err_ptr, B, H, W, int(valid_w), T, premask, rp, stream_ptr)
 
-    ok = _resident_launch(dev, B, H, W, int(T), launch, reports_done=True, guarded=bool(guard), out=ghist[int(T) - 1])
-    _lib.check(ok, "cspn3_transposed_resident")
+    _resident_launch(dev, B, H, W, T, launch, name, reports_done=True, guarded=bool(guard), out=ghist[T - 1])
     return ghist
+
+
+def transposed_resident(w8, g_T, sparse_f32, T, valid_w=0):
+    """Reverse sweep of the backward as one weight-resident launch per chunk: ghist [T,B,H,W] (G_{T-1} .. G_0)."""
+    return _transposed3("cspn3_transposed_resident", (_p(w8),), _require_device(w8, g_T, sparse_f32), g_T, sparse_f32, T, valid_w)
 
 
 def transposed_resident_guidance(guidance, S, g_T, sparse_f32, T, valid_w=0, _plan=None):
     """The same reverse sweep without a tap volume: the transposed taps |g_j[p]| / S[p + off_j] are rebuilt from the raw guidance
     and the normaliser S the training forward published (include/cspn_hip.h cspn3_transposed_resident_guidance)."""
-    B, H, W = g_T.shape
-    L = _lib.lib()
-    if _plan is not None:                              # CSPN3Function's fast path: validated with the forward, guarded plan in hand
-        dev, guard, rp = guidance.device, 1, _plan
-    else:
-        dev = _require_device(guidance, S, g_T, sparse_f32)
-        guard = int(_RESIDENT_GUARD and int(T) <= _GUARD_MAX_T)
-        rp = _with_spin_limit(_resident_plan_cached(B, H, W, int(T), int(sparse_f32 is not None), dev)[1], guard=guard)
-    ghist = torch.empty((int(T), B, H, W), dtype=torch.float32, device=dev)
-
-    def launch(work, seq, host_err_ptr, stream_ptr):
-        return L.cspn3_transposed_resident_guidance(_p(guidance), guidance.stride(0), guidance.stride(1), _p(S), _p(g_T), _p(sparse_f32),
-                                                    _p(ghist), _p(work), seq, host_err_ptr, B, H, W, int(valid_w), int(T),
-                                                    int(sparse_f32 is not None), None if rp is None else ctypes.byref(rp), stream_ptr)
-
-    ok = _resident_launch(dev, B, H, W, int(T), launch, reports_done=True, guarded=bool(guard), out=ghist[int(T) - 1])
-    _lib.check(ok, "cspn3_transposed_resident_guidance")
-    return ghist
+    dev = guidance.device if _plan is not None else _require_device(guidance, S, g_T, sparse_f32)      # (fast path: validated with the forward)
+    return _transposed3("cspn3_transposed_resident_guidance", (_p(guidance), guidance.stride(0), guidance.stride(1), _p(S)), dev, g_T,
+                        sparse_f32, T, valid_w, _plan)
 
 
 def pac_transposed_resident(wk, g_T, sparse, T, debug_stamps=None):
@@ -1147,20 +1191,17 @@ def pac_transposed_resident(wk, g_T, sparse, T, debug_stamps=None):
     planes = torch.empty((int(T) + int(half_in), B, H, W), dtype=torch.float32, device=dev)
     g32, ghist = (planes[0], planes[1:]) if half_in else (g_T, planes)
     premask = int(sparse is not None)
-    guard = int(bool(_RESIDENT_GUARD) and 2 * int(T) <= _GUARD_MAX_T)
+    guard = _guard_default(int(T) * (5 // 2))
     rp = _with_spin_limit(_kres_plan_cached(5, B, H, W, int(T), premask, dev, 0, CSPN_F16)[1], guard=guard)
     if debug_stamps is not None and rp is not None:     # developer probe: in-kernel time stamps of round 0's workgroups [images_per_launch x tiles][16]
         rp = _plan_copy(rp, debug_stamps=debug_stamps.data_ptr())
 
     def launch(work, seq, host_err_ptr, stream_ptr):
         return L.cspnk_transposed_resident(_p(wk), CSPN_F16, 5, _p(g_T), _p(sparse), _dt(g_T), _p(g32) if half_in else None, _p(ghist),
-                                           _p(work), seq, host_err_ptr, B, H, W, int(T), premask,
-                                           None if rp is None else ctypes.byref(rp), stream_ptr)
+                                           _p(work), seq, host_err_ptr, B, H, W, int(T), premask, rp, stream_ptr)
 
-    ok = _resident_launch(dev, B, H, W, int(T), launch, ws_kind="k", state_bytes=4,
-                          ws_bytes_fn=lambda: L.cspnk_resident_workspace_bytes(B, H, W, CSPN_F32), reports_done=True, guarded=bool(guard),
-                          out=ghist[int(T) - 1])
-    _lib.check(ok, "cspnk_transposed_resident")
+    _resident_launch(dev, B, H, W, int(T), launch, "cspnk_transposed_resident", _kxk_workspace(B, H, W, CSPN_F32), reports_done=True,
+                     guarded=bool(guard), out=ghist[int(T) - 1])
     return g32, ghist
 
 
@@ -1184,47 +1225,28 @@ def forward_resident(guidance, d0, sparse, T, blend, score=None, valid_w=0, step
     else:
         out = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     tg, acc = score if score is not None else (None, None)
-    rp = None
-    if guard is None:
-        guard = int(bool(_RESIDENT_GUARD) and (score is None or _RESIDENT_GUARD == "all") and int(T) <= _GUARD_MAX_T)
-    guard = int(guard)
+    guard = _guard_default(int(T), "plain" if score is None else "scored") if guard is None else int(guard)
     if _plan is not None and not _RESIDENT_SPIN_LIMIT:
         rp = _plan                                     # the caller's cached (guarded) plan: CSPN3Function's fast path
     elif steps_per_phase or spin_limit or debug_stamps is not None or threads:
         rp = _plan_copy(steps_per_phase=int(steps_per_phase), threads=int(threads), spin_limit=int(spin_limit),
                         debug_stamps=None if debug_stamps is None else debug_stamps.data_ptr(), guard=guard)
     else:
-        # found once per shape: the C side skips its search
-        cp = _resident_plan_cached(B, H, W, int(T), int(blend), dev)[1]
+        cp = _resident_plan_cached(B, H, W, int(T), int(blend), dev)[1]      # found once per shape: the C side skips its search
         if score is not None and not keep_history and not valid_w:
             cp = _scored_plan(cp, B, H, W, int(T), int(blend), dev)
         rp = _with_spin_limit(cp, guard=guard)
+
     def launch(work, seq, host_err_ptr, stream_ptr):
         return L.cspn3_forward_resident(_p(guidance), guidance.stride(0), guidance.stride(1), _p(d0), _p(sparse), _p(out),
                                         _p(hist), _p(w8), _p(S_out), _p(work), seq, host_err_ptr, B, H, W, int(valid_w),
-                                        int(T), int(blend), _p(tg), _p(acc), 0 if acc is None else int(acc.shape[0]),
-                                        None if rp is None else ctypes.byref(rp), stream_ptr)
-
-    redo = None
-    if not keep_history:
-        scored = score is not None
-
-        def redo(out, guidance, d0, sparse, tg):       # the same call on the multi-launch schedule, into the same tensors (bit-identical:
-            from . import evaluation                   # §4.1b); the tensors are handed in by the journal (it may hold them weakly)
-            tgp = None if tg is None else tg.reshape(B, H, W)
-            if scored:
-                _unscore_failed_launch(out, tgp, acc)
-            res, _ = propagate_from_guidance(guidance, d0.reshape(B, H, W), None if sparse is None else sparse.reshape(B, H, W), T, blend,
-                                             valid_w=valid_w)
-            out.copy_(res)
-            if scored:
-                evaluation.metric_sums(out, tgp, out=acc)
+                                        int(T), int(blend), _p(tg), _p(acc), 0 if acc is None else int(acc.shape[0]), rp, stream_ptr)
 
     # (a training-form launch cannot be repaired after the fact: its entry keeps no inputs, and the plane a tile that gave up poisons weakly)
-    ok = _resident_launch(dev, B, H, W, int(T), launch, reports_done=bool(keep_history), redo=redo,
-                          out=hist[int(T) - 1] if keep_history else out, inputs=() if keep_history else (guidance, d0, sparse, tg),
-                          what="cspn3_forward_resident %dx%dx%d" % (B, H, W), guarded=bool(guard))
-    _lib.check(ok, "cspn3_forward_resident")
+    _resident_launch(dev, B, H, W, int(T), launch, "cspn3_forward_resident", reports_done=bool(keep_history),
+                     redo=None if keep_history or guard else _redo3(B, H, W, T, blend, valid_w, acc),
+                     out=hist[int(T) - 1] if keep_history else out, inputs=() if keep_history else (guidance, d0, sparse, tg),
+                     guarded=bool(guard))
     if keep_history:
         return hist[int(T) - 1], hist, w8, S_out
     return out
@@ -1307,9 +1329,7 @@ def pac_forward_resident(guided, x0, sparse, T, score=None, steps_per_phase=0, s
         form = _lib.STEP_AUTO                      # a process-wide "dot2" only pins the calls that have the kernel
     # every unscored K x K call carries the device-side guard (csrc/cspn_repair.hip: the softmax forms of the quad kernel for the K = 3 /
     # fp32-guidance model the reference's unet_ours runs, cspnk_resident_repair for the oct kernels); scored calls keep the host repair
-    if guard is None:
-        guard = int(bool(_RESIDENT_GUARD) and score is None and int(T) * (K // 2) <= _GUARD_MAX_T)
-    guard = int(guard)
+    guard = _guard_default(int(T) * (K // 2), "plain" if score is None else "never") if guard is None else int(guard)
     if steps_per_phase or spin_limit or debug_stamps is not None or threads:
         rp = _plan_copy(steps_per_phase=int(steps_per_phase), threads=int(threads), spin_limit=int(spin_limit),
                         debug_stamps=None if debug_stamps is None else debug_stamps.data_ptr(), step_form=form, guard=guard)
@@ -1318,8 +1338,7 @@ def pac_forward_resident(guided, x0, sparse, T, score=None, steps_per_phase=0, s
 
     def launch(work, seq, host_err_ptr, stream_ptr):
         return L.cspnk_forward_resident(_p(guided), _dt(guided), K, _p(x0), _p(sparse), _p(out), sdt, _p(work), seq, host_err_ptr, B, H, W,
-                                        int(T), int(blend), _p(tg), _p(acc), 0 if acc is None else int(acc.shape[0]),
-                                        None if rp is None else ctypes.byref(rp), stream_ptr)
+                                        int(T), int(blend), _p(tg), _p(acc), 0 if acc is None else int(acc.shape[0]), rp, stream_ptr)
 
     scored = score is not None
     # does this call run the dot-product form (cspnk_d2: K = 5, fp16 guidance and planes, one oct per thread)?  Its state is rounded to half
@@ -1345,10 +1364,8 @@ def pac_forward_resident(guided, x0, sparse, T, score=None, steps_per_phase=0, s
         if scored:
             evaluation.metric_sums(out, tg, out=acc)
 
-    ok = _resident_launch(dev, B, H, W, int(T), launch, ws_kind="k", state_bytes=x0.element_size(),
-                          ws_bytes_fn=lambda: L.cspnk_resident_workspace_bytes(B, H, W, sdt), redo=redo, out=out,
-                          inputs=(guided, x0, sparse, tg), what="cspnk_forward_resident %dx%dx%d" % (B, H, W), guarded=bool(guard))
-    _lib.check(ok, "cspnk_forward_resident")
+    _resident_launch(dev, B, H, W, int(T), launch, "cspnk_forward_resident", _kxk_workspace(B, H, W, sdt), redo=redo, out=out,
+                     inputs=(guided, x0, sparse, tg), guarded=bool(guard))
     return out
 
 
@@ -1365,21 +1382,16 @@ def pac_forward_resident_history(guided, x0, sparse, T):
     wk = _weight_buffer(B, C, H, W, guided.dtype, dev)
     blend = BLEND_SPARSE if sparse is not None else BLEND_NONE
     gdt = _dt(guided)
-    # the device-side guard (a launch that gave up is re-computed on the stream: csrc/cspn_repair.hip): the K = 3 fp32 form and the
-    # K = 5 fp16 form (BASELINE config 3's shape), while the T * (K // 2) halo of the re-computation fits its LDS tile
-    guard = int(bool(_RESIDENT_GUARD) and int(T) * (K // 2) <= _GUARD_MAX_T
-                and ((K == 3 and guided.dtype == torch.float32) or (K == 5 and guided.dtype == torch.float16)))
+    # the device-side guard (a launch that gave up is re-computed on the stream: csrc/cspn_repair.hip), for the forms that have one
+    guard = _guard_default(int(T) * (K // 2), "plain" if (K, guided.dtype) in _GUARDED_HISTORY_FORMS else "never")
     rp = _with_spin_limit(_kres_plan_cached(K, B, H, W, int(T), int(blend), dev, 0, gdt)[1], guard=guard)
 
     def launch(work, seq, host_err_ptr, stream_ptr):
         return L.cspnk_forward_resident_history(_p(guided), gdt, K, _p(x0), _p(sparse), _p(hist), _p(wk), _p(work), seq, host_err_ptr,
-                                                B, H, W, int(T), int(blend), None if rp is None else ctypes.byref(rp), stream_ptr)
+                                                B, H, W, int(T), int(blend), rp, stream_ptr)
 
-    sdt = _dt(x0)
-    ok = _resident_launch(dev, B, H, W, int(T), launch, ws_kind="k", state_bytes=x0.element_size(),
-                          ws_bytes_fn=lambda: L.cspnk_resident_workspace_bytes(B, H, W, sdt), reports_done=True, guarded=bool(guard),
-                          out=hist[int(T) - 1])
-    _lib.check(ok, "cspnk_forward_resident_history")
+    _resident_launch(dev, B, H, W, int(T), launch, "cspnk_forward_resident_history", _kxk_workspace(B, H, W, _dt(x0)), reports_done=True,
+                     guarded=bool(guard), out=hist[int(T) - 1])
     return hist[int(T) - 1], hist, wk
 
 
@@ -1391,6 +1403,17 @@ def transpose_weights(w, K, H, W):
         ok = _lib.lib().cspn_transpose_weights(_p(w), _p(wT), _dt(w), B, H, W, int(K), _stream(dev))
     _lib.check(ok, "cspn_transpose_weights")
     return wT
+
+
+def _resident_sweep_plan(K, plan, B, H, W, T, premask, dev):
+    """What every weight-resident form of the reverse sweep asks: mode not "off", no launch plan given or set as default, no HIP-graph
+    capture — and then, last (it may create the device's state), the cached plan dict (K = 3: the 3x3 engine's, K = 5: the fp16 oct
+    kernel's; None where the shape has none)."""
+    if _RESIDENT_MODE == "off" or plan is not None or _DEFAULT_PLANS.get(K) is not None or torch.cuda.is_current_stream_capturing():
+        return None
+    if K == 3:
+        return _resident_plan_cached(B, H, W, int(T), int(premask), dev)[0]
+    return _kres_plan_cached(5, B, H, W, int(T), int(premask), dev, 0, CSPN_F16)[0]
 
 
 def _reverse_sweep(w, K, T, sparse, grad_out, plan, valid_w=0, guidance_S=None):
@@ -1410,19 +1433,17 @@ def _reverse_sweep(w, K, T, sparse, grad_out, plan, valid_w=0, guidance_S=None):
             g32 = g32.clone()
         if (K == 3 and T > 0 and gd.dtype == torch.float32 and W % 4 == 0 and gd.data_ptr() % 16 == 0 and gd.stride(0) % 4 == 0
                 and gd.stride(1) % 4 == 0 and gd.stride(1) < (1 << 27) and gd.stride(3) == 1 and gd.stride(2) == W
-                and (sp32 is None or sp32.data_ptr() % 16 == 0) and _RESIDENT_MODE != "off" and plan is None
-                and _DEFAULT_PLANS.get(3) is None and H * W < (1 << 27) and not torch.cuda.is_current_stream_capturing()
-                and _resident_plan_cached(B, H, W, int(T), int(sp32 is not None), dev)[0] is not None):
+                and (sp32 is None or sp32.data_ptr() % 16 == 0) and H * W < (1 << 27)
+                and _resident_sweep_plan(3, plan, B, H, W, T, sp32 is not None, dev) is not None):
             return g32, transposed_resident_guidance(gd, S, g32, sp32, T, valid_w)
         w = cspn3_prepare(gd, want_s=False, valid_w=valid_w)[0]
     if g_T.data_ptr() % 16:
         g_T = g_T.clone()
     ghist = None
     if (T > 0 and K == 5 and w.dtype == torch.float16 and w.dim() == 3 and W % 8 == 0 and not valid_w
-            and (sparse is None or sparse.data_ptr() % 16 == 0) and _RESIDENT_MODE != "off" and plan is None
-            and _DEFAULT_PLANS.get(5) is None and 24 * H * W < (1 << 30) and not torch.cuda.is_current_stream_capturing()
+            and (sparse is None or sparse.data_ptr() % 16 == 0) and 24 * H * W < (1 << 30)
             and os.environ.get("CSPN_REVERSE_SWEEP", "auto") == "auto"
-            and (_kres_plan_cached(5, B, H, W, int(T), int(sparse is not None), dev, 0, CSPN_F16)[0] or {}).get("quads_per_thread") == 1):
+            and (_resident_sweep_plan(5, plan, B, H, W, T, sparse is not None, dev) or {}).get("quads_per_thread") == 1):
         # weight-resident reverse sweep on the forward's fp16 volume; half cotangent / sparse planes go in as they are
         if g_T.dtype == torch.float16 and (sparse is None or sparse.dtype == torch.float16):
             return pac_transposed_resident(w, g_T, sparse, T)
@@ -1432,9 +1453,8 @@ def _reverse_sweep(w, K, T, sparse, grad_out, plan, valid_w=0, guidance_S=None):
         sp32 = None if sparse is None else sparse.float()
         L = _lib.lib()
         if (K == 3 and w.dtype == torch.float32 and w.dim() == 4 and W % 4 == 0 and w.data_ptr() % 16 == 0 and g_T.data_ptr() % 16 == 0
-                and (sp32 is None or sp32.data_ptr() % 16 == 0) and _RESIDENT_MODE != "off" and plan is None
-                and _DEFAULT_PLANS.get(3) is None and H * W < (1 << 27) and not torch.cuda.is_current_stream_capturing()
-                and _resident_plan_cached(B, H, W, int(T), int(sp32 is not None), dev)[0] is not None):
+                and (sp32 is None or sp32.data_ptr() % 16 == 0) and H * W < (1 << 27)
+                and _resident_sweep_plan(3, plan, B, H, W, T, sp32 is not None, dev) is not None):
             # weight-resident reverse sweep: the transposed taps are gathered once and stay in registers for all T steps
             return g_T, transposed_resident(w, g_T, sp32, T, valid_w)
         ghist = torch.empty((T, B, H, W), dtype=torch.float32, device=dev)
@@ -1494,11 +1514,11 @@ def _check_resident_at_end_of_backward(dev):
     st = _RES.get(dev.index)
     if st is None or not st["dirty"] or torch.cuda.is_current_stream_capturing() or _BWD_CHECK_OFF:
         return                     # (CSPN_BWD_CHECK=off: A/B switch for measurements; the next resident launch still raises)
-    if not st.get("need_bwd_check"):
+    if not st["need_bwd_check"]:
         return                     # every training-form launch since the last check carried its device-side guard (round 5): whatever
     st["need_bwd_check"] = False   # the loss and the optimiser read is complete by stream order — nothing for the host to wait for
     cp = _ResidentCheckpoint(dev)
-    if st.get("last_reports"):     # the newest launch is the one the checkpoint waits for: everything issued so far is covered
+    if st["last_reports"]:     # the newest launch is the one the checkpoint waits for: everything issued so far is covered
         st["dirty"] = False        # (a later inference launch does not report completion: the next ensure_resident_ok still waits)
     try:
         torch.autograd.Variable._execution_engine.queue_callback(cp.wait_and_check)
@@ -1745,10 +1765,11 @@ _SCORED_FAST = {}      # call signature -> _ScoredFast: cspn3_refine_and_score g
 class _ScoredFast(object):
     """Everything a scored resident forward of one call signature needs, resolved once (round 5: at per-GPU shard sizes the call is
     HOST-bound — 20 us of host time against 17 us of kernel, tools/probes/r05_shard_host.py): the cached plan, the device's
-    state, the workspace, the constant arguments of the C call.  `issue` is _resident_launch + forward_resident with nothing left
-    to look up; whatever it does not handle (another device current, a stream change, HIP-graph capture, an event log, a sequence
-    wrap, an evicted workspace) returns None and the caller takes the general path."""
-    __slots__ = ("plan", "plan_guarded", "dev", "idx", "st", "work", "wkey", "B", "H", "W", "T", "blend", "gs0", "gs1", "nslots", "nbytes",
+    state, the constant arguments of the C call.  `issue` is the lean way into _issue — forward_resident + _resident_launch with
+    nothing left to look up: no Stream object, no device switch, no launch closure; whatever it does not handle (a spin limit,
+    another device current, HIP-graph capture, a stream change, an evicted workspace, a sequence wrap) returns None BEFORE anything
+    is consumed or allocated — the sampling slot of an event log, the output — and the caller takes the general path."""
+    __slots__ = ("plan", "plan_guarded", "dev", "idx", "st", "wkey", "B", "H", "W", "T", "blend", "gs0", "gs1", "nslots", "nbytes",
                  "what", "cfunc")
 
     def __init__(self, plan, guidance, T, blend, acc):
@@ -1756,61 +1777,38 @@ class _ScoredFast(object):
         self.plan, self.dev, self.idx = plan, guidance.device, guidance.device.index
         self.st = _resident_state(guidance.device)
         self.wkey = (B, H, W, "3", 4)
-        self.work = self.st["work"].get(self.wkey)
         self.B, self.H, self.W, self.T, self.blend = B, H, W, int(T), int(blend)
         self.gs0, self.gs1, self.nslots = guidance.stride(0), guidance.stride(1), int(acc.shape[0])
         self.nbytes = (guidance.numel() + (3 + int(bool(blend))) * B * H * W) * 4
         self.what = "cspn3_forward_resident %dx%dx%d (scored)" % (B, H, W)
         self.cfunc = _lib.lib().cspn3_forward_resident
-        self.plan_guarded = _with_spin_limit(plan, guard=1) if int(T) <= _GUARD_MAX_T and not _RESIDENT_SPIN_LIMIT else None
+        # the guarded copy of the plan (whether a call takes it is _guard_default's business); a spin limit keeps calls off this path
+        self.plan_guarded = None if _RESIDENT_SPIN_LIMIT else _with_spin_limit(plan, guard=1)
+
+    def _launch(self, work, seq, host_err_ptr, raw, guidance, d0, sparse, out, target, acc, plan):
+        return self.cfunc(guidance.data_ptr(), self.gs0, self.gs1, d0.data_ptr(), None if sparse is None else sparse.data_ptr(), out.data_ptr(),
+                          None, None, None, work.data_ptr(), seq, host_err_ptr, self.B, self.H, self.W, 0, self.T, self.blend,
+                          target.data_ptr(), acc.data_ptr(), self.nslots, plan, raw)
 
     def issue(self, guidance, d0, sparse, target, acc):
         st = self.st
         if (_RESIDENT_SPIN_LIMIT or torch._C._cuda_getDevice() != self.idx or torch._C._cuda_isCurrentStreamCapturing()):
             return None
-        log = _EVENT_LOG                               # bench.py's sampled HIP events: recorded here as well, so that an instrumented
-        if log is not None and not log.take():         # loop runs the same lean path as an uninstrumented one (round 6)
-            log = None
         raw = torch._C._cuda_getCurrentRawStream(self.idx)
-        out = torch.empty((self.B, self.H, self.W), dtype=torch.float32, device=self.dev)
-        B, H, W, T, blend = self.B, self.H, self.W, self.T, self.blend
-        guarded = _RESIDENT_GUARD == "all" and self.plan_guarded is not None
         with st["lock"]:
             # everything another thread's launch can change is read under the device's lock (read before it, a launch from
             # another stream in between let this one skip wait_stream and overlap a resident launch — time-outs, not wrong output)
-            work = st["work"].get(self.wkey)
-            if work is None or raw != st.get("last_raw") or st["seq"] > _RES_SEQ_MAX:
+            work = st["work"].get(self.wkey)       # (looked up per call: the workspace cache may have been started over)
+            if work is None or raw != st["last_raw"] or st["seq"] > _RES_SEQ_MAX:
                 return None                        # stream change / evicted workspace / sequence wrap: the general path
-            self.work = work                       # (the workspace cache may have been started over: more than 16 shapes)
-            if st["host_err_np"][0] != 0:
-                _recover(self.dev, st)
-            seq = st["seq"]
-            st["seq"] = seq + _RES_SEQ_STEP
-            if log is not None:
-                ev0, ev1 = log.pair()
-                ev0.record(st["last_stream"])
-            ok = self.cfunc(guidance.data_ptr(), self.gs0, self.gs1, d0.data_ptr(), None if sparse is None else sparse.data_ptr(), out.data_ptr(),
-                            None, None, None, self.work.data_ptr(), seq, st["host_err_ptr"], B, H, W, 0, T, blend, target.data_ptr(),
-                            acc.data_ptr(), self.nslots, self.plan_guarded if guarded else self.plan, raw)
-            if log is not None:
-                ev1.record(st["last_stream"])
-                log.append((ev0, ev1, 1, T))
-            if ok:
-                st["dirty"] = True
-                st["last_reports"] = False
-            if ok and guarded:                     # the guard re-computes the depth AND the missing metric terms on the stream: no entry
-                st["guarded_pending"] = st.get("guarded_pending", 0) + 1
-            elif ok:
-
-                def redo(out, guidance, d0, sparse, target):       # the same call on the multi-launch schedule, into the same tensors
-                    from . import evaluation                       # (bit-identical: DESIGN.md §4.1b)
-                    tgp = target.reshape(B, H, W)
-                    _unscore_failed_launch(out, tgp, acc)
-                    res, _ = propagate_from_guidance(guidance, d0.reshape(B, H, W), None if sparse is None else sparse.reshape(B, H, W), T, blend)
-                    out.copy_(res)
-                    evaluation.metric_sums(out, tgp, out=acc)
-
-                _journal_add(self.dev, st, _JournalEntry(redo, out, (guidance, d0, sparse, target), self.what, self.nbytes), st["last_stream"])
+            log = _sampled_log()                   # (bench.py's HIP events: an instrumented loop runs the same lean path: round 6)
+            out = torch.empty((self.B, self.H, self.W), dtype=torch.float32, device=self.dev)
+            # (guarded: the guard re-computes the depth AND the missing metric terms on the stream: no entry)
+            guarded = self.plan_guarded is not None and _guard_default(self.T, "scored")
+            journal = None if guarded else (_redo3(self.B, self.H, self.W, self.T, self.blend, 0, acc), out, (guidance, d0, sparse, target),
+                                            self.what, self.nbytes)
+            ok = _issue(self.dev, st, raw, log, self.T, self._launch,
+                        (guidance, d0, sparse, out, target, acc, self.plan_guarded if guarded else self.plan), False, journal, work)
         _lib.check(ok, "cspn3_forward_resident")
         return out
 
@@ -1841,7 +1839,7 @@ def cspn3_refine_and_score(guidance, blur_depth, sparse_depth, target, acc, prop
                     out = forward_resident(guidance, blur_depth, sparse_depth, prop_time, fast_plan.blend, score=(target, acc),
                                            _plan=fast_plan.plan if _RESIDENT_GUARD != "all" else None)
             return out.unsqueeze(1)
-    dev = _require_device(guidance, blur_depth, sparse_depth, target)
+    _require_device(guidance, blur_depth, sparse_depth, target)
     W0 = guidance.shape[-1]
     pad = _row_padding(W0, plan)
     if pad:
@@ -1877,7 +1875,6 @@ def cspn3_refine_and_score(guidance, blur_depth, sparse_depth, target, acc, prop
         else:
             out, _ = propagate(w8, d0, sp, 3, prop_time, blend, plan=plan, valid_w=vw)
             evaluation.metric_sums(out, tg, out=acc)
-    del dev
     return out.unsqueeze(1)[..., :W0]
 
 

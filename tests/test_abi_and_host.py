@@ -535,6 +535,86 @@ def test_journal_entries_accept_inference_tensors_and_training_entries_pin_nothi
     assert e3.out.get() is None
 
 
+def test_guard_rule_truth_table(monkeypatch):
+    """functional._guard_default is the one place that says which resident calls carry the device-side guard when the caller does
+    not: the switch is on, the halo of the re-computation (T for the 3x3 entries, T * (K // 2) for the K x K ones) fits
+    _GUARD_MAX_T = 54, and the scored policy allows it — every call site's decision, row by row."""
+    from cspn_monodepth_amd import functional as F
+    assert F._GUARD_MAX_T == 54
+    for switch in (False, True, "all"):
+        monkeypatch.setattr(F, "_RESIDENT_GUARD", switch)
+        on = int(bool(switch))
+        # transposed_resident(_guidance), the unscored forward_resident: h = T
+        assert [F._guard_default(T) for T in (1, 24, 54, 55)] == [on, on, on, 0]
+        # pac_transposed_resident, the K = 5 forms of pac_forward_resident(_history): h = T * (5 // 2)
+        assert [F._guard_default(T * (5 // 2)) for T in (1, 24, 27, 28)] == [on, on, on, 0]
+        # K = 3 K x K: h = T * (3 // 2)
+        assert [F._guard_default(T * (3 // 2)) for T in (24, 54, 55)] == [on, on, 0]
+        # the scored 3x3 forward (forward_resident with score=, _ScoredFast): only under "all"
+        assert [F._guard_default(T, "scored") for T in (24, 54, 55)] == [int(switch == "all"), int(switch == "all"), 0]
+        # the scored K x K forward: never; so a history form without a guard kernel
+        assert [F._guard_default(T * (K // 2), "never") for K in (3, 5) for T in (1, 24, 27, 28, 54, 55)] == [0] * 12
+    # the history form takes "plain" for exactly these (K, guidance dtype), "never" for every other
+    assert F._GUARDED_HISTORY_FORMS == {(3, torch.float32), (5, torch.float16)}
+    assert (3, torch.float16) not in F._GUARDED_HISTORY_FORMS and (5, torch.float32) not in F._GUARDED_HISTORY_FORMS
+
+
+def test_journal_demotion_passes_over_training_entries(monkeypatch):
+    """a training-form entry (redo None: weak from birth) between strong inference entries must not end the
+    newest-first demotion walk — the entries older than it would stay pinned past _JOURNAL_STRONG_BYTES.  Oldest to newest:
+    inference, inference, training, inference, inference; three inference entries exceed the budget, so the two oldest are
+    demoted and the newest two stay strong (the "at least the last two" rule).  The same list without the training entry
+    gives the same answer for the inference entries."""
+    from cspn_monodepth_amd import functional as F
+
+    def inference():
+        out, g = torch.zeros(2, 4, 8), torch.ones(2, 12, 4, 8)
+        return F._JournalEntry(lambda *a: None, out, (g, None), "test")
+
+    one = inference().nbytes
+    assert one == (2 * 4 * 8 + 2 * 12 * 4 * 8) * 4
+    monkeypatch.setattr(F, "_JOURNAL_STRONG_BYTES", 2 * one + one // 2)       # two entries fit, three do not
+    hist = torch.zeros(3, 2, 4, 8)
+    for with_training in (True, False):
+        inf = [inference() for _ in range(4)]
+        j = inf[:2] + ([F._JournalEntry(None, hist[2], (), "training")] if with_training else []) + inf[2:]
+        assert sum(e.nbytes for e in j[:2]) + j[-1].nbytes > F._JOURNAL_STRONG_BYTES
+        F._journal_demote(j)
+        assert [e.weak for e in inf] == [True, True, False, False], with_training
+        assert inf[0].resolve()[0] is None and inf[3].resolve()[0] is not None      # demoted: nothing kept alive; strong: held
+        F._journal_demote(j)                                                      # a second walk changes nothing
+        assert [e.weak for e in inf] == [True, True, False, False]
+
+
+def test_device_state_has_every_key_from_the_start(monkeypatch):
+    """The per-device state of the resident launches is created whole (functional._new_state, the device-free part of
+    _resident_state): no host-side function that can run without a device adds a key to it, whichever runs first."""
+    from cspn_monodepth_amd import functional as F
+    st = F._new_state(torch.zeros(4, dtype=torch.int32), 256)
+    keys = set(st)
+    assert keys >= {"seq", "host_err_np", "dirty", "journal", "last_seq", "work", "marks", "mark_pool", "jcount", "guarded_pending",
+                    "need_bwd_check", "last_raw", "last_stream", "last_reports", "lost", "lock", "n_cu"}
+    assert st["seq"] == F._RES_SEQ_STEP and not st["dirty"] and st["guarded_pending"] == 0 and st["last_raw"] is None
+    monkeypatch.setattr(F, "_RES", {0: st})
+    dev = torch.device("cuda", 0)
+    out, g = torch.zeros(2, 4, 8), torch.ones(2, 12, 4, 8)
+    for k in range(15):                                    # (the 16th add records a HIP event: that needs a device)
+        F._journal_add(dev, st, F._JournalEntry(lambda *a: None, out, (g,), "test") if k % 2 else F._JournalEntry(None, out), None)
+        assert set(st) == keys
+    assert len(st["journal"]) == 15 and st["jcount"] == 15
+    assert F._resident_state(dev) is st
+    F.check_resident_errors()
+    F.check_resident_errors(dev)
+    cp = F._ResidentCheckpoint(dev)
+    cp.wait_and_check()
+    assert set(st) == keys and len(st["journal"]) == 15   # nothing reports completion: the checkpoint clears nothing
+    st["guarded_pending"] = 3
+    F.ensure_resident_ok()                                 # nothing is pending on a stream: everything issued has finished cleanly
+    assert set(st) == keys and not st["journal"] and st["guarded_pending"] == 0
+    F._journal_clear(st)
+    assert set(st) == keys
+
+
 def test_bench_cpu_binding_narrows_and_restores_the_affinity_mask():
     """bench.py --cpu-bind auto: a rank's host threads go to its share of the first allowed cores; the CPU baseline leg gets the
     whole mask back (full_affinity), and the reported host budget is the original one."""

@@ -616,6 +616,92 @@ def test_journal_does_not_pin_batches(c_oracle):
         F.ensure_resident_ok()
 
 
+def _small_scored_case(c_oracle, seed):
+    """(3, 100, 148), T = 24: a shape with a resident plan (test_resident_launch_replays_from_a_hip_graph), a few ms per call."""
+    B, H, W = 3, 100, 148
+    g, d, s = c_oracle.synthetic_inputs(seed, B, H, W, 12, 300)
+    tgt = np.maximum(d + 0.05, 0.0).astype(np.float32)
+    return dev(g), dev(d), dev(s), dev(tgt)
+
+
+def _scored_fast_registered(B, H, W):
+    return any((v.B, v.H, v.W) == (B, H, W) for v in F._SCORED_FAST.values())
+
+
+def test_one_sampling_slot_per_forward(c_oracle):
+    """bench.py's event log samples every n-th instrumented call: a forward must ask it exactly once, whichever path serves it —
+    the general path, the lean path of forward_scored, or the lean path bailing out (here: on a stream change) and falling to the
+    general one.  Before the lean path shared the general path's issue sequence this failed at the side-stream call: the lean
+    path took a sampling slot (and allocated its output) before the test that made it bail out, and the general path took a
+    second one.  Results are the multi-launch schedule's bits on every path."""
+    ev = pkg.evaluation
+    T = 24
+    gt, dt, st, tt = _small_scored_case(c_oracle, 910)
+    m = pkg.CSPN_new.AffinityPropagate(T, 3)
+    outs = []
+    prev_log = F._EVENT_LOG
+    with torch.no_grad():
+        with resident("off"):
+            acc0 = ev.new_accumulator(DEV)
+            ref = m.forward_scored(gt, dt, st, tt, acc0)
+        F._SCORED_FAST.clear()                                   # the first call below takes the general path and registers the lean one
+        log = F.EventLog(n_pairs=8, every=1)
+        try:
+            F.set_event_log(log)
+            with resident("on"):
+                acc = ev.new_accumulator(DEV)
+
+                def call(where):
+                    before = (log.calls, len(log))
+                    outs.append(m.forward_scored(gt, dt, st, tt, acc))
+                    assert (log.calls, len(log)) == (before[0] + 1, before[1] + 1), where
+
+                call("general path")
+                assert _scored_fast_registered(3, 100, 148)
+                call("lean path")
+                cur, side = torch.cuda.current_stream(), torch.cuda.Stream()
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):
+                    call("lean path bails out on the stream change, general path")
+                cur.wait_stream(side)
+                call("back on the original stream")
+        finally:
+            F.set_event_log(prev_log)
+    torch.cuda.synchronize()
+    assert len(outs) == 4
+    for o in outs:
+        assert bits_equal(o, ref)
+    assert np.allclose(acc.sum(0).cpu().numpy(), 4 * acc0.sum(0).cpu().numpy(), rtol=1e-6)
+    F.check_resident_errors()
+
+
+def test_lean_and_general_path_leave_the_same_host_state(c_oracle):
+    """The lean path of forward_scored and the general path run ONE issue sequence: after one call of each, without the guard,
+    the device's state holds what two general calls would have left — two journal entries of the same size, two sequence steps,
+    launches pending, the newest of them not reporting completion — and ensure_resident_ok empties the journal."""
+    ev = pkg.evaluation
+    gt, dt, st, tt = _small_scored_case(c_oracle, 920)
+    m = pkg.CSPN_new.AffinityPropagate(24, 3)
+    with torch.no_grad(), resident("on"), guard(False):
+        F.ensure_resident_ok()
+        state = F._resident_state(gt.device)
+        assert not state["journal"]
+        state["jcount"] = 0                                      # (no completion mark between the two calls: every 16th add records one,
+        F._SCORED_FAST.clear()                                   #  and the add after it drops the entries it covers)
+        seq0 = state["seq"]
+        acc = ev.new_accumulator(DEV)
+        m.forward_scored(gt, dt, st, tt, acc)                    # general path; registers the lean one
+        assert len(state["journal"]) == 1 and _scored_fast_registered(3, 100, 148)
+        m.forward_scored(gt, dt, st, tt, acc)                    # lean path
+        j = state["journal"]
+        assert len(j) == 2 and j[0].nbytes == j[1].nbytes and not j[0].weak and not j[1].weak
+        assert state["seq"] - seq0 == 2 * F._RES_SEQ_STEP
+        assert state["dirty"] and not state["last_reports"]
+        F.ensure_resident_ok()
+        assert not state["journal"] and not state["dirty"]
+    F.check_resident_errors()
+
+
 def test_contended_device_results_equal_uncontended(c_oracle):
     """a REAL co-tenant — a side-stream kernel holding 64 CUs (120 KB of LDS each: no resident workgroup fits
     beside it) for 5 ms at a time — while 50 scored forwards and 10 training steps run with a short neighbour wait (10 polls).

@@ -37,6 +37,8 @@ SGD_CHUNK, SGD_TENSORS_PER_LAUNCH, SGD_MAX_WORKGROUPS = 4096, 109, 2048
 VISUAL_RANGE_CHUNK, VISUAL_MAX_PLANES = 4096, 3
 VISUAL_RGB_NONE, VISUAL_RGB_F32, VISUAL_RGB_U8 = 0, 1, 2      # cspn_visual_rows_t.rgb_kind
 BLEND_NONE, BLEND_SPARSE, BLEND_PREMASK = 0, 1, 2
+HEADS_MAX_HEADS, HEADS_MAX_OUT_CHANNELS = 4, 16              # CSPN_HEADS_MAX_* (include/cspn_heads.h)
+HEADS_FORWARD, HEADS_BACKWARD_INPUT, HEADS_BACKWARD_WEIGHTS = 0, 1, 2      # the `pass` of cspn_heads_workspace_bytes
 
 
 class cspn_plan(ctypes.Structure):
@@ -188,25 +190,38 @@ def _families():
             "cspn_visual_workspace_bytes": (cs, [ci, ci, cs]),
             "cspn_visual_rows": [ptr(cspn_visual_rows), ci, ci, ci, vp, cs, vp, vp],
             "cspn_visual_features": [vp, cl, ci, ci, ci, ci, ci, vp, cs, vp, vp]}),
+        family("heads", "cspn_heads.h", 1, {"cspn_heads.hip": False}, {
+            "cspn_heads_abi_version": None,
+            "cspn_heads_workspace_bytes": (cs, [ci, ci, ci, ci, ci, ci, ci, ci]),
+            "cspn_heads_forward": [vp, ptr(vp), ptr(vp), ptr(ci), ci, vp, ci, ci, ci, ci, ci, ci, vp],
+            "cspn_heads_backward_input": [ptr(vp), ptr(vp), ptr(ci), ci, vp, vp, ci, ci, ci, ci, ci, ci, vp],
+            "cspn_heads_backward_weights": [vp, ptr(vp), ptr(vp), ptr(ci), ci, vp, ci, ci, ci, ci, ci, ci, vp]}),
     )
 
 
-FAMILIES = _families()
+# The table has two parts.  FAMILIES: what a default call of the package can reach — the nine families the loader's tests spell
+# out in literals, with SOURCES their translation units.  OPT_IN_FAMILIES: families behind a switch that is off by default (heads:
+# `fused_heads=True` of the models, network.up_pooling.up_pooling_conv3x3); they are built, declared and version-checked with the
+# others, and no file of theirs is part of code_digest().
+ALL_FAMILIES = _families()
+FAMILIES = ALL_FAMILIES[:9]
+OPT_IN_FAMILIES = ALL_FAMILIES[9:]
 
 
 def family(name):
-    return next(f for f in FAMILIES if f.name == name)
+    return next(f for f in ALL_FAMILIES if f.name == name)
 
 
-def _files(suffix, benchmarked=None):
-    return tuple(f for fam in FAMILIES for f, b in fam.files.items() if f.endswith(suffix) and benchmarked in (None, b))
+def _files(suffix, benchmarked=None, families=FAMILIES):
+    return tuple(f for fam in families for f, b in fam.files.items() if f.endswith(suffix) and benchmarked in (None, b))
 
 
 SOURCES = _files(".hip")                      # one TU each
+OPT_IN_SOURCES = _files(".hip", families=OPT_IN_FAMILIES)
 BENCH_UNRELATED = _files(".hip", False)       # kernels no bench.py workload launches
 HEADERS = tuple(os.path.join(CSRC, f) for f in _files(".hpp", True)) + tuple(f.header for f in FAMILIES if any(f.files.values()))
 BUILD_HEADERS = HEADERS + tuple(os.path.join(CSRC, f) for f in _files(".hpp", False)) + \
-    tuple(f.header for f in FAMILIES if not any(f.files.values()))
+    tuple(f.header for f in ALL_FAMILIES if not any(f.files.values()))
 EXPORTS = tuple(family("core").functions)      # every symbol include/cspn_hip.h declares
 
 
@@ -217,7 +232,8 @@ def _source_digest(flags, code_only=False):
     import hashlib
     import re
     h = hashlib.sha256(" ".join(flags).encode())
-    for path in [os.path.join(CSRC, f) for f in SOURCES if not (code_only and f in BENCH_UNRELATED)] + list(HEADERS if code_only else BUILD_HEADERS):
+    tus = [f for f in SOURCES if f not in BENCH_UNRELATED] if code_only else SOURCES + OPT_IN_SOURCES
+    for path in [os.path.join(CSRC, f) for f in tus] + list(HEADERS if code_only else BUILD_HEADERS):
         with open(path, "rb") as fh:
             data = fh.read()
         if code_only:
@@ -237,7 +253,7 @@ def build(force=False, verbose=False):
     csrc/_build/*.o and linked into the in-tree .so (which travels with gpurun snapshots).  Staleness is decided by
     a content hash of the sources + flags stored next to the library (file times do not survive every copy)."""
     from concurrent.futures import ThreadPoolExecutor
-    srcs = [os.path.join(CSRC, f) for f in SOURCES]
+    srcs = [os.path.join(CSRC, f) for f in SOURCES + OPT_IN_SOURCES]
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     # -fno-slp-vectorize: the SLP pass pairs the stencil FMAs into v_pk_fma_f32 and pays for it with ~50 v_mov
     # per step to build operand pairs; scalar v_fma_f32 measured 4 % faster (profiles/).  No fast-math: 0/0 = NaN.
@@ -290,7 +306,7 @@ _lock = threading.Lock()
 
 
 def _declare(lib):
-    for fam in FAMILIES:
+    for fam in ALL_FAMILIES:
         for name, (restype, argtypes) in fam.functions.items():
             fn = getattr(lib, name)
             if restype is not ctypes.c_int:           # ctypes' default
@@ -311,7 +327,7 @@ def lib():
                         "cspn_monodepth_amd: %s is missing — build it with `python -c 'import __graft_entry__ as g; "
                         "g.build()'` (hipcc --offload-arch=gfx950).  There is no CPU fallback." % SO_PATH)
                 _lib = _declare(ctypes.CDLL(SO_PATH))
-                for fam in FAMILIES:
+                for fam in ALL_FAMILIES:
                     sub = "" if fam.name == "core" else fam.name      # cspn_abi_version, cspn_<family>_abi_version
                     if getattr(_lib, "cspn_%sabi_version" % (sub and sub + "_"))() != fam.abi_version:
                         raise RuntimeError("cspn_monodepth_amd: %sABI version mismatch" % (sub and sub + " "))

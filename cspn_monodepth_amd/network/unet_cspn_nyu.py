@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from ..post_process import CSPN_new as post_process
-from .up_pooling import up_pooling
+from .up_pooling import up_pooling, up_pooling_conv3x3
 
 __all__ = ["ResNet", "resnet50", "resnet18", "Bottleneck", "BasicBlock", "Gudi_UpProj_Block", "Gudi_UpProj_Block_Cat",
            "Simple_Gudi_UpConv_Block_Last_Layer", "UpProj_Block", "DECODER_SIZES_NYU"]
@@ -158,10 +158,13 @@ class ResNet(nn.Module):
     (:332) the forward runs.  The default 8 is all the CSPN module reads (CSPN_new.py:29-36): the head's last convolution, its
     weight-gradient work and the [B,12,H,W] write shrink by a third (27 MB less per forward at B = 24), the refined depth and the
     gradients of channels 0..7 are unchanged (the 4 dead filters received exact zeros before, and receive them now), the parameter
-    and the state_dict keep the reference's [12,64,3,3] shape.  12 reproduces the reference's tensor (guidance [B,12,H,W])."""
+    and the state_dict keep the reference's [12,64,3,3] shape.  12 reproduces the reference's tensor (guidance [B,12,H,W]).
+    fused_heads (off by default): both heads run as one ``up_pooling_conv3x3`` call on gud_up_proj_layer5's weight and the first
+    `affinity_channels` filters of gud_up_proj_layer6's, without the un-pooled [B,64,H,W] map; blocks, parameters and state_dict
+    stay as they are (the one difference in values: up_pooling_conv3x3's docstring)."""
 
     def __init__(self, block, layers, up_proj_block=UpProj_Block, decoder_sizes=DECODER_SIZES_NYU, prop_time=24,
-                 prop_kernel=3, reference_state_dict=True, cspn_plan=None, affinity_channels=8):
+                 prop_kernel=3, reference_state_dict=True, cspn_plan=None, affinity_channels=8, fused_heads=False):
         super(ResNet, self).__init__()
         self.inplanes = 64
         e = block.expansion
@@ -194,6 +197,7 @@ class ResNet(nn.Module):
             raise ValueError("affinity_channels must be in [8, 12] (the CSPN module reads channels 0..7)")
         self.affinity_channels = int(affinity_channels)
         self.return_cspn_io = False
+        self.fused_heads = bool(fused_heads)
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None
@@ -224,6 +228,10 @@ class ResNet(nn.Module):
         x = self.gud_up_proj_layer2(x, skip2)
         x = self.gud_up_proj_layer3(x, skip3)
         x = self.gud_up_proj_layer4(x, skip4)
+        if self.fused_heads:
+            l5, l6 = self.gud_up_proj_layer5, self.gud_up_proj_layer6
+            coarse, guidance = up_pooling_conv3x3(x, (l5.conv1.weight, l6.conv1.weight[:self.affinity_channels]), l5.oheight, l5.owidth)
+            return guidance, coarse, sparse_depth
         return self.gud_up_proj_layer6(x, self.affinity_channels), self.gud_up_proj_layer5(x), sparse_depth
 
     def forward(self, x):

@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from ..post_process import CSPN_ours as post_process
 from .unet_cspn_nyu import DECODER_SIZES_NYU, BasicBlock, Bottleneck, _conv
-from .up_pooling import MyBlock
+from .up_pooling import MyBlock, up_pooling_conv3x3
 
 __all__ = ["ResNet", "resnet50", "resnet18", "Bottleneck", "BasicBlock", "UpProj_Block", "Gudi_UpProj_Block",
            "Gudi_UpProj_Block_Cat", "Simple_Gudi_UpConv_Block", "Simple_Gudi_UpConv_Block_Last_Layer", "DECODER_SIZES_NYU", "decoder_sizes_for"]
@@ -99,9 +99,14 @@ class ResNet(nn.Module):
     `up_proj_block` is accepted and ignored, as in the reference (:253; it builds no up_proj_layer).  decoder_sizes: the five
     (oheight, owidth) pairs of the decoder stages; the default is the reference's hard-coded 228 x 304 pyramid (:274-279).
     prop_time: the reference hard-codes 24 (:305).  cspn_plan: handed to the CSPN module.  `return_cspn_io = True` makes
-    forward return ([x, guidance], (blur_depth, guidance, sparse_depth)) — the tensors handed to the CSPN module."""
+    forward return ([x, guidance], (blur_depth, guidance, sparse_depth)) — the tensors handed to the CSPN module.
+    fused_heads (off by default): the two output heads run as one ``up_pooling_conv3x3`` call on the weights of
+    gud_up_proj_layer5 / 6 instead of the two blocks — the [B,64,H,W] un-pooled map is neither written nor saved for the backward.
+    The blocks and their parameters stay where they are (the same state_dict either way); the sums are the same terms in another
+    order, and a NaN in the decoder's last map spreads less far (up_pooling_conv3x3's docstring)."""
 
-    def __init__(self, block, layers, up_proj_block=None, decoder_sizes=DECODER_SIZES_NYU, prop_time=24, cspn_plan=None):
+    def __init__(self, block, layers, up_proj_block=None, decoder_sizes=DECODER_SIZES_NYU, prop_time=24, cspn_plan=None,
+                 fused_heads=False):
         super(ResNet, self).__init__()
         self.inplanes = 64
         e = block.expansion
@@ -125,6 +130,7 @@ class ResNet(nn.Module):
         self.gud_up_proj_layer5 = Simple_Gudi_UpConv_Block_Last_Layer(64, 1, *s[4])       # coarse ("blur") depth head
         self.gud_up_proj_layer6 = Simple_Gudi_UpConv_Block_Last_Layer(64, 8, *s[4])       # affinity head: K*K - 1 = 8, K = 3
         self.return_cspn_io = False
+        self.fused_heads = bool(fused_heads)
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None
@@ -154,6 +160,10 @@ class ResNet(nn.Module):
         x = self.gud_up_proj_layer2(x, skip2)
         x = self.gud_up_proj_layer3(x, skip3)
         x = self.gud_up_proj_layer4(x, skip4)
+        if self.fused_heads:
+            l5, l6 = self.gud_up_proj_layer5, self.gud_up_proj_layer6
+            blur_depth, guidance = up_pooling_conv3x3(x, (l5.conv1.weight, l6.conv1.weight), l5.oheight, l5.owidth)
+            return blur_depth, guidance, sparse_depth
         return self.gud_up_proj_layer5(x), self.gud_up_proj_layer6(x), sparse_depth
 
     def forward(self, x):

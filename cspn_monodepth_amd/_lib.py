@@ -39,6 +39,7 @@ VISUAL_RGB_NONE, VISUAL_RGB_F32, VISUAL_RGB_U8 = 0, 1, 2      # cspn_visual_rows
 BLEND_NONE, BLEND_SPARSE, BLEND_PREMASK = 0, 1, 2
 HEADS_MAX_HEADS, HEADS_MAX_OUT_CHANNELS = 4, 16              # CSPN_HEADS_MAX_* (include/cspn_heads.h)
 HEADS_FORWARD, HEADS_BACKWARD_INPUT, HEADS_BACKWARD_WEIGHTS = 0, 1, 2      # the `pass` of cspn_heads_workspace_bytes
+UPCONV_MAX_FILTERS = 2                                       # CSPN_UPCONV_MAX_FILTERS (include/cspn_upconv.h)
 
 
 class cspn_plan(ctypes.Structure):
@@ -196,13 +197,18 @@ def _families():
             "cspn_heads_forward": [vp, ptr(vp), ptr(vp), ptr(ci), ci, vp, ci, ci, ci, ci, ci, ci, vp],
             "cspn_heads_backward_input": [ptr(vp), ptr(vp), ptr(ci), ci, vp, vp, ci, ci, ci, ci, ci, ci, vp],
             "cspn_heads_backward_weights": [vp, ptr(vp), ptr(vp), ptr(ci), ci, vp, ci, ci, ci, ci, ci, ci, vp]}),
+        family("upconv", "cspn_upconv.h", 1, {"cspn_upconv.hip": False}, {
+            "cspn_upconv_abi_version": None,
+            "cspn_upconv_workspace_bytes": (cs, [ci, ci]),
+            "cspn_upconv_pack": [ptr(vp), ptr(ci), ci, ci, ci, ci, ci, vp, vp],
+            "cspn_upconv_forward": [vp, ci, vp, vp, vp, ci, ptr(vp), ptr(ci), ci, ci, ci, ci, ci, ci, ci, vp]}),
     )
 
 
 # The table has two parts.  FAMILIES: what a default call of the package can reach — the nine families the loader's tests spell
 # out in literals, with SOURCES their translation units.  OPT_IN_FAMILIES: families behind a switch that is off by default (heads:
-# `fused_heads=True` of the models, network.up_pooling.up_pooling_conv3x3); they are built, declared and version-checked with the
-# others, and no file of theirs is part of code_digest().
+# `fused_heads=True` of the models, network.up_pooling.up_pooling_conv3x3; upconv: `fused_decoder`, up_pooling_conv5x5); they are
+# built, declared and version-checked with the others, and no file of theirs is part of code_digest().
 ALL_FAMILIES = _families()
 FAMILIES = ALL_FAMILIES[:9]
 OPT_IN_FAMILIES = ALL_FAMILIES[9:]

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from ..post_process import CSPN_new as post_process
-from .up_pooling import up_pooling, up_pooling_conv3x3
+from .up_pooling import FusedHead, select_fused_decoder, up_pooling, up_pooling_conv3x3
 
 __all__ = ["ResNet", "resnet50", "resnet18", "Bottleneck", "BasicBlock", "Gudi_UpProj_Block", "Gudi_UpProj_Block_Cat",
            "Simple_Gudi_UpConv_Block_Last_Layer", "UpProj_Block", "DECODER_SIZES_NYU"]
@@ -73,7 +73,7 @@ class Bottleneck(_Residual):                                     # unet_cspn_nyu
         return self._finish(self.bn3(self.conv3(out)), x)
 
 
-class _UpBlock(nn.Module):
+class _UpBlock(FusedHead, nn.Module):
     """Base of the decoder blocks: un-pool by 2 to (oheight, owidth) with the HIP kernel.
 
     The reference's blocks up-sample to 2H x 2W, crop to (oheight, owidth) and multiply with a mask that is 1 at even
@@ -105,6 +105,9 @@ class Gudi_UpProj_Block(_UpBlock):                               # unet_cspn_nyu
         self.relu = nn.ReLU(inplace=True)
 
     def forward(self, x):
+        if self._fuse_head():
+            out, shortcut = self._head(x)
+            return self.relu(self.bn2(self.conv2(out)) + shortcut)
         x = self._up_pooling(x)
         out = self.bn2(self.conv2(self.relu(self.bn1(self.conv1(x)))))
         return self.relu(out + self.sc_bn1(self.sc_conv1(x)))
@@ -126,6 +129,10 @@ class Gudi_UpProj_Block_Cat(_UpBlock):                           # unet_cspn_nyu
         self.relu = nn.ReLU(inplace=True)
 
     def forward(self, x, side_input):
+        if self._fuse_head():
+            out, shortcut = self._head(x)
+            out = torch.cat((out, side_input), 1)
+            return self.relu(self.bn2(self.conv2(self.relu(self.bn1_1(self.conv1_1(out))))) + shortcut)
         x = self._up_pooling(x)
         out = torch.cat((self.relu(self.bn1(self.conv1(x))), side_input), 1)
         out = self.bn2(self.conv2(self.relu(self.bn1_1(self.conv1_1(out)))))
@@ -161,10 +168,15 @@ class ResNet(nn.Module):
     and the state_dict keep the reference's [12,64,3,3] shape.  12 reproduces the reference's tensor (guidance [B,12,H,W]).
     fused_heads (off by default): both heads run as one ``up_pooling_conv3x3`` call on gud_up_proj_layer5's weight and the first
     `affinity_channels` filters of gud_up_proj_layer6's, without the un-pooled [B,64,H,W] map; blocks, parameters and state_dict
-    stay as they are (the one difference in values: up_pooling_conv3x3's docstring)."""
+    stay as they are (the one difference in values: up_pooling_conv3x3's docstring).
+    fused_decoder (off by default; independent of fused_heads): True, or a collection of block names out of "gud_up_proj_layer1" ..
+    "gud_up_proj_layer4" — in eval mode with grad mode off a named block runs its head (un-pool, conv1 -> bn1 -> ReLU, sc_conv1 ->
+    sc_bn1) as one ``up_pooling_conv5x5`` call and the rest of itself on stock ops; otherwise exactly the default code.  True selects
+    the blocks where that was measured to be faster (up_pooling.FUSED_DECODER_DEFAULT).  The state_dict is the same either way."""
 
     def __init__(self, block, layers, up_proj_block=UpProj_Block, decoder_sizes=DECODER_SIZES_NYU, prop_time=24,
-                 prop_kernel=3, reference_state_dict=True, cspn_plan=None, affinity_channels=8, fused_heads=False):
+                 prop_kernel=3, reference_state_dict=True, cspn_plan=None, affinity_channels=8, fused_heads=False,
+                 fused_decoder=False):
         super(ResNet, self).__init__()
         self.inplanes = 64
         e = block.expansion
@@ -198,6 +210,7 @@ class ResNet(nn.Module):
         self.affinity_channels = int(affinity_channels)
         self.return_cspn_io = False
         self.fused_heads = bool(fused_heads)
+        self.fused_decoder = select_fused_decoder(self, fused_decoder)
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None

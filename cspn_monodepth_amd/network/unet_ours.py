@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from ..post_process import CSPN_ours as post_process
 from .unet_cspn_nyu import DECODER_SIZES_NYU, BasicBlock, Bottleneck, _conv
-from .up_pooling import MyBlock, up_pooling_conv3x3
+from .up_pooling import MyBlock, select_fused_decoder, up_pooling_conv3x3
 
 __all__ = ["ResNet", "resnet50", "resnet18", "Bottleneck", "BasicBlock", "UpProj_Block", "Gudi_UpProj_Block",
            "Gudi_UpProj_Block_Cat", "Simple_Gudi_UpConv_Block", "Simple_Gudi_UpConv_Block_Last_Layer", "DECODER_SIZES_NYU", "decoder_sizes_for"]
@@ -47,6 +47,9 @@ class Gudi_UpProj_Block(MyBlock):                              # unet_ours.py:20
         self.relu = nn.ReLU(inplace=False)
 
     def forward(self, x):
+        if self._fuse_head():
+            out, shortcut = self._head(x)
+            return self.relu(self.bn2(self.conv2(out)) + shortcut)
         x = self._up_pooling(x, 2)
         out = self.bn2(self.conv2(self.relu(self.bn1(self.conv1(x)))))
         return self.relu(out + self.sc_bn1(self.sc_conv1(x)))
@@ -63,6 +66,8 @@ class Simple_Gudi_UpConv_Block(MyBlock):                         # unet_ours.py:
         self.relu = nn.ReLU(inplace=False)
 
     def forward(self, x):
+        if self._fuse_head():
+            return self._head(x)[0]
         return self.relu(self.bn1(self.conv1(self._up_pooling(x, 2))))
 
 
@@ -87,6 +92,10 @@ class Gudi_UpProj_Block_Cat(MyBlock):                            # unet_ours.py:
         self.relu = nn.ReLU(inplace=False)
 
     def forward(self, x, side_input):
+        if self._fuse_head():
+            out, shortcut = self._head(x)
+            out = torch.cat((out, side_input), 1)
+            return self.relu(self.bn2(self.conv2(self.relu(self.bn1_1(self.conv1_1(out))))) + shortcut)
         x = self._up_pooling(x, 2)
         out = torch.cat((self.relu(self.bn1(self.conv1(x))), side_input), 1)
         out = self.bn2(self.conv2(self.relu(self.bn1_1(self.conv1_1(out)))))
@@ -103,10 +112,15 @@ class ResNet(nn.Module):
     fused_heads (off by default): the two output heads run as one ``up_pooling_conv3x3`` call on the weights of
     gud_up_proj_layer5 / 6 instead of the two blocks — the [B,64,H,W] un-pooled map is neither written nor saved for the backward.
     The blocks and their parameters stay where they are (the same state_dict either way); the sums are the same terms in another
-    order, and a NaN in the decoder's last map spreads less far (up_pooling_conv3x3's docstring)."""
+    order, and a NaN in the decoder's last map spreads less far (up_pooling_conv3x3's docstring).
+    fused_decoder (off by default; independent of fused_heads): True, or a collection of block names out of "gud_up_proj_layer1" ..
+    "gud_up_proj_layer4".  In eval mode with grad mode off a named block computes relu(bn1(conv1(up(x)))) and sc_bn1(sc_conv1(up(x)))
+    with one ``up_pooling_conv5x5`` call on the compact map and runs the rest of itself on stock ops; in train mode or with grad mode
+    on it runs exactly the default code.  True selects the blocks where that was measured to be faster
+    (up_pooling.FUSED_DECODER_DEFAULT).  Modules, parameters and the state_dict are the same either way."""
 
     def __init__(self, block, layers, up_proj_block=None, decoder_sizes=DECODER_SIZES_NYU, prop_time=24, cspn_plan=None,
-                 fused_heads=False):
+                 fused_heads=False, fused_decoder=False):
         super(ResNet, self).__init__()
         self.inplanes = 64
         e = block.expansion
@@ -131,6 +145,7 @@ class ResNet(nn.Module):
         self.gud_up_proj_layer6 = Simple_Gudi_UpConv_Block_Last_Layer(64, 8, *s[4])       # affinity head: K*K - 1 = 8, K = 3
         self.return_cspn_io = False
         self.fused_heads = bool(fused_heads)
+        self.fused_decoder = select_fused_decoder(self, fused_decoder)
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None

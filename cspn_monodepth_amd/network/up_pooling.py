@@ -20,6 +20,12 @@ empty tensor (unet_ours.py:147-148) or an all-zero one (the mask loop never runs
 ``up_pooling_conv3x3`` is the un-pooling by 2 fused with the bias-free 3x3 convolutions that follow it in the two output heads
 (``Simple_Gudi_UpConv_Block_Last_Layer``, unet_ours.py:194-202): the un-pooled map is never written (include/cspn_heads.h).  It is
 opt-in — ``fused_heads=True`` of the models — and differs from the two-block path in one stated way, see its docstring.
+
+``up_pooling_conv5x5`` is the same for the head of a decoder block (``Gudi_UpProj_Block``, ``Gudi_UpProj_Block_Cat``, ``UpProj_Block``,
+``Simple_Gudi_UpConv_Block``, unet_ours.py:160-248): un-pooling by 2, the one or two bias-free 5x5 convolutions over it, their batch
+norms in eval mode and the ReLU of the first, as one implicit GEMM per output phase on the fp32 matrix cores
+(include/cspn_upconv.h).  Forward only and opt-in — ``fused_decoder`` of the models; the filters are reordered once by
+``pack_upconv5x5``.
 """
 import ctypes
 
@@ -30,7 +36,7 @@ from torch.autograd.function import Function, once_differentiable
 from .. import _lib
 from .._host import _dt, _p, _require_device, launch
 
-__all__ = ["up_pooling", "up_pooling_conv3x3", "MyBlock"]
+__all__ = ["up_pooling", "up_pooling_conv3x3", "up_pooling_conv5x5", "pack_upconv5x5", "UpconvPack", "MyBlock"]
 
 
 def _forward(x, scale, oh, ow):
@@ -183,7 +189,224 @@ def up_pooling_conv3x3(x, weights, oheight, owidth):
     return _heads_forward(x.contiguous(), tuple(w.contiguous() for w in weights), oheight, owidth)
 
 
-class MyBlock(nn.Module):
+class UpconvPack(object):
+    """What ``up_pooling_conv5x5`` runs on: the filters of one block head in the order the kernel walks them (``packed``), the folded
+    batch norms (``scale``, ``shift``: fp32 [sum of out_channels], or None), how many leading flat channels get a ReLU, and the
+    ``_version`` and ``data_ptr`` of every tensor it was made from — ``stale()`` says whether one of them has changed since."""
+
+    def __init__(self, packed, scale, shift, out_channels, in_channels, relu_channels, sources):
+        self.packed, self.scale, self.shift = packed, scale, shift
+        self.out_channels, self.in_channels, self.relu_channels = tuple(out_channels), int(in_channels), int(relu_channels)
+        self.sources = tuple(sources)
+        self._seen = tuple((t._version, t.data_ptr()) for t in self.sources)
+
+    def stale(self):
+        """True once a source tensor was written in place (an optimizer step, ``load_state_dict``) or moved."""
+        return any((t._version, t.data_ptr()) != seen for t, seen in zip(self.sources, self._seen))
+
+    def made_from(self, sources):
+        """Are these the very tensors the pack was made from (a parameter that was replaced, not written, is another object)?"""
+        sources = tuple(sources)
+        return len(sources) == len(self.sources) and all(a is b for a, b in zip(sources, self.sources))
+
+
+def _check_filters(who, weights):
+    if not isinstance(weights, (tuple, list)):
+        raise ValueError("%s: weights must be a tuple of [O,C,5,5] tensors" % who)
+    weights = tuple(weights)
+    if not 1 <= len(weights) <= _lib.UPCONV_MAX_FILTERS:
+        raise ValueError("%s: one or two filters, got %d" % (who, len(weights)))
+    for k, w in enumerate(weights):
+        if w.dim() != 4 or w.shape[0] < 1 or w.shape[1] < 1 or tuple(w.shape[2:]) != (5, 5) or w.shape[1] != weights[0].shape[1]:
+            raise ValueError("%s: filter %d must be [O,%d,5,5], got %s" % (who, k, weights[0].shape[1] if weights[0].dim() == 4 else 0, tuple(w.shape)))
+        if w.dtype != torch.float32:
+            raise ValueError("%s: fp32 only, got %s" % (who, w.dtype))
+        if w.numel() >= 2 ** 31:
+            raise ValueError("%s: filter %d has 2^31 elements or more" % (who, k))
+    return weights
+
+
+def _bn_sources(bn):
+    return [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
+
+
+def pack_upconv5x5(weights, batchnorms=None, relu=(True, False)):
+    """The pack of one block head: ``weights`` — one or two [O_k, C, 5, 5] fp32 filters on a ROCm device (``conv1.weight``,
+    ``sc_conv1.weight``) — reordered for the kernel, and ``batchnorms`` — None, or one ``nn.BatchNorm2d`` per filter —
+    folded as eval mode applies them: scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale, by device
+    tensor ops (nothing is read back).  ``relu``: per filter, whether a ReLU follows; the filters with one come first.  Made once
+    per version of the weights: ``stale()`` of the result says when to make it again."""
+    who = "pack_upconv5x5"
+    weights = _check_filters(who, weights)
+    relu = tuple(bool(r) for r in relu)[:len(weights)]
+    if len(relu) != len(weights):
+        raise ValueError("%s: relu needs one entry per filter" % who)
+    if any(b and not a for a, b in zip(relu, relu[1:])):
+        raise ValueError("%s: the filters with a ReLU come first, got relu=%s" % (who, relu))
+    if batchnorms is not None:
+        batchnorms = tuple(batchnorms)
+        if len(batchnorms) != len(weights):
+            raise ValueError("%s: batchnorms needs one entry per filter" % who)
+        for w, bn in zip(weights, batchnorms):
+            if bn.num_features != w.shape[0] or bn.running_mean is None:
+                raise ValueError("%s: a batch norm over %d channels with running statistics per filter" % (who, w.shape[0]))
+    dev = _require_device(*weights)
+    out_channels, C = [w.shape[0] for w in weights], weights[0].shape[1]
+    total = sum(out_channels)
+    nbytes = _lib.lib().cspn_upconv_workspace_bytes(total, C)
+    if not nbytes:
+        raise ValueError("%s: the packed form of %d x %d channels has 2^31 elements or more" % (who, total, C))
+    sources = list(weights)
+    with torch.no_grad():
+        wc = [w.detach().contiguous() for w in weights]
+        packed = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        launch(dev, "cspn_upconv_pack", _ptrs(wc), _channels(wc), len(wc), C, 5, 5, _lib.CSPN_F32, _p(packed))
+        scale = shift = None
+        if batchnorms is not None:
+            scales, shifts = [], []
+            for w, bn in zip(weights, batchnorms):
+                _require_device(w, *_bn_sources(bn))
+                sources += _bn_sources(bn)
+                s = 1.0 / torch.sqrt(bn.running_var.float() + bn.eps)
+                if bn.weight is not None:
+                    s = bn.weight.detach().float() * s
+                b = -bn.running_mean.float() * s
+                if bn.bias is not None:
+                    b = bn.bias.detach().float() + b
+                scales.append(s)
+                shifts.append(b)
+            scale, shift = torch.cat(scales).contiguous(), torch.cat(shifts).contiguous()
+    return UpconvPack(packed, scale, shift, out_channels, C, sum(o for o, r in zip(out_channels, relu) if r), sources)
+
+
+def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=None, relu_channels=0):
+    """Un-pooling by 2 to (oheight, owidth), the one or two bias-free 5x5 convolutions (padding 2) of a decoder block over it, a
+    per-channel affine map and a ReLU on the leading channels, in one kernel:
+
+        x [N,C,H,W], filters (w_0 [O_0,C,5,5][, w_1 [O_1,C,5,5]])  ->  (y_0 [N,O_0,oheight,owidth][, y_1 [N,O_1,oheight,owidth]])
+        (y_0 | y_1)[:, q] == act_q(conv2d(up_pooling(x, 2, oheight, owidth), w, padding=2)[:, q] * scale[q] + shift[q])
+
+    over the flat channels q of both filters, act_q the ReLU for q < relu_channels — with a pack of ``pack_upconv5x5(weights,
+    (bn1, sc_bn1))`` that is ``relu(bn1(conv1(u)))`` and ``sc_bn1(sc_conv1(u))`` of ``Gudi_UpProj_Block`` in eval mode
+    (unet_ours.py:205-223).  The un-pooled map u is never written: each of the four output phases is an implicit GEMM over the 9, 6, 6
+    or 4 taps that meet the compact map (include/cspn_upconv.h), on the fp32 matrix cores — exact fp32 products, every output one
+    chain over (tap, channel), so a frame's bits do not depend on the batch and runs repeat.  fp32 on a ROCm device; 1 <= oheight
+    <= 2H, 1 <= owidth <= 2W as ``up_pooling`` at scale 2; every tensor below 2^31 elements.
+
+    ``pack_or_weights``: an ``UpconvPack`` (its scale, shift and ReLU count apply; the arguments of that name must be left alone),
+    or the filters themselves — packed for this one call — with ``scale`` / ``shift`` (fp32 [O_0 + O_1], both or neither) and
+    ``relu_channels`` as given.
+
+    Forward only.  With grad mode on and ``x`` or a source of the pack requiring a gradient it raises: training runs the stock
+    blocks (``up_pooling`` and the convolutions, as the models do by default).
+
+    One difference from the stock blocks: a NaN or Inf in ``x[n,c,i,j]`` reaches only the outputs whose 5x5 window covers (2i, 2j).
+    The reference's un-pooling holds ``x * 0`` at the inserted positions, so there it also reaches the rest of the windows over its
+    2 x 2 block."""
+    who = "up_pooling_conv5x5"
+    if x.dim() != 4:
+        raise ValueError("%s: x must be [N,C,H,W], got %s" % (who, tuple(x.shape)))
+    pack = pack_or_weights if isinstance(pack_or_weights, UpconvPack) else None
+    if pack is not None:
+        if scale is not None or shift is not None or relu_channels:
+            raise ValueError("%s: scale, shift and relu_channels come with the pack" % who)
+        out_channels, C_w, sources = pack.out_channels, pack.in_channels, pack.sources
+        scale, shift, relu_channels = pack.scale, pack.shift, pack.relu_channels
+    else:
+        weights = _check_filters(who, pack_or_weights)
+        out_channels, C_w, sources = tuple(w.shape[0] for w in weights), weights[0].shape[1], weights
+    N, C, H, W = x.shape
+    if C != C_w:
+        raise ValueError("%s: x has %d channels, the filters take %d" % (who, C, C_w))
+    if x.dtype != torch.float32:
+        raise ValueError("%s: fp32 only, got %s" % (who, x.dtype))
+    total = sum(out_channels)
+    if (scale is None) != (shift is None):
+        raise ValueError("%s: scale and shift come together" % who)
+    for name, t in (("scale", scale), ("shift", shift)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (total,)):
+            raise ValueError("%s: %s must be fp32 [%d], got %s %s" % (who, name, total, t.dtype, tuple(t.shape)))
+    relu_channels = int(relu_channels)
+    if not 0 <= relu_channels <= total:
+        raise ValueError("%s: relu_channels %d outside [0, %d]" % (who, relu_channels, total))
+    oheight, owidth = int(oheight), int(owidth)
+    if N < 1 or C < 1 or H < 1 or W < 1:
+        raise ValueError("%s: empty input %s" % (who, tuple(x.shape)))
+    if not (1 <= oheight <= 2 * H and 1 <= owidth <= 2 * W):
+        raise ValueError("%s: output %dx%d must lie within [1, %d] x [1, %d] (scale 2 of a %dx%d input)"
+                         % (who, oheight, owidth, 2 * H, 2 * W, H, W))
+    if x.numel() >= 2 ** 31 or N * max(out_channels) * oheight * owidth >= 2 ** 31:
+        raise ValueError("%s: a tensor of 2^31 elements or more; split the batch" % who)
+    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in sources)):
+        raise RuntimeError("%s is forward-only: with grad mode on, run the stock blocks (up_pooling and the 5x5 convolutions, the "
+                           "models' default and their training path), or call it under torch.no_grad()" % who)
+    dev = _require_device(x, scale, shift, *sources)
+    if pack is None:
+        pack = pack_upconv5x5(weights, None, (False,) * len(weights))
+    xc = x.contiguous()
+    outs = tuple(torch.empty((N, o, oheight, owidth), dtype=torch.float32, device=dev) for o in out_channels)
+    launch(dev, "cspn_upconv_forward", _p(xc), _lib.CSPN_F32, _p(pack.packed), _p(None if scale is None else scale.contiguous()),
+           _p(None if shift is None else shift.contiguous()), relu_channels, _ptrs(outs), (ctypes.c_int * len(outs))(*out_channels), len(outs),
+           N, C, H, W, oheight, owidth)
+    return outs
+
+
+DECODER_BLOCKS = ("gud_up_proj_layer1", "gud_up_proj_layer2", "gud_up_proj_layer3", "gud_up_proj_layer4")
+# What `fused_decoder=True` selects: the blocks at which tools/upconv_bench.py measured the fused head ahead of the stock one by
+# more than the spread of the two measurements — its 90th percentile below the stock 10th, warm and cache-cold
+# (profiles/r18_upconv_bench.json, RESULTS.md row 33: all four, 3.3 to 5.3 times).
+FUSED_DECODER_DEFAULT = ("gud_up_proj_layer1", "gud_up_proj_layer2", "gud_up_proj_layer3", "gud_up_proj_layer4")
+
+
+def select_fused_decoder(model, fused_decoder):
+    """The `fused_decoder` switch of the models: False / None, True (FUSED_DECODER_DEFAULT) or a collection of block names out of
+    DECODER_BLOCKS.  Marks the named blocks and returns their names in decoder order (what the model keeps as `fused_decoder`)."""
+    if fused_decoder is True:
+        names = FUSED_DECODER_DEFAULT
+    elif not fused_decoder:
+        names = ()
+    elif isinstance(fused_decoder, str):
+        names = (fused_decoder,)
+    else:
+        names = tuple(fused_decoder)
+    unknown = [n for n in names if n not in DECODER_BLOCKS]
+    if unknown:
+        raise ValueError("fused_decoder: %s not among %s" % (unknown, list(DECODER_BLOCKS)))
+    for n in DECODER_BLOCKS:
+        getattr(model, n).fused_head = n in names
+    return tuple(n for n in DECODER_BLOCKS if n in names)
+
+
+class FusedHead(object):
+    """Mixed into the decoder blocks: the block's head — un-pool, conv1 -> bn1 -> ReLU and, where the block has one, sc_conv1 -> sc_bn1 —
+    as one ``up_pooling_conv5x5`` call when the block is marked (`fused_head`, set by the model's `fused_decoder`), in eval mode and
+    with grad mode off.  The pack is made at the first such call, made again when a source changed (``load_state_dict``, an
+    in-place update, a parameter replaced by ``.to()``) and dropped by ``train()``; it is no parameter, buffer or module."""
+    fused_head = False
+    _upconv_pack = None
+
+    def _fuse_head(self):
+        return self.fused_head and not self.training and not torch.is_grad_enabled()
+
+    def _head(self, x):
+        """(relu(bn1(conv1(u))), sc_bn1(sc_conv1(u)) or None) for u = the un-pooled x, without u."""
+        convs, bns = [self.conv1], [self.bn1]
+        if hasattr(self, "sc_conv1"):
+            convs.append(self.sc_conv1)
+            bns.append(self.sc_bn1)
+        weights = [c.weight for c in convs]
+        pack = self._upconv_pack
+        if pack is None or pack.stale() or not pack.made_from(weights + [t for bn in bns for t in _bn_sources(bn)]):
+            pack = self._upconv_pack = pack_upconv5x5(weights, bns, (True, False)[:len(convs)])
+        outs = up_pooling_conv5x5(x, pack, self.oheight, self.owidth)
+        return outs[0], (outs[1] if len(outs) > 1 else None)
+
+    def train(self, mode=True):
+        self._upconv_pack = None
+        return super(FusedHead, self).train(mode)
+
+
+class MyBlock(FusedHead, nn.Module):
     """network/unet_ours.py:131-157: base of the decoder blocks; holds the target size of the un-pooled map."""
 
     def __init__(self, oheight=0, owidth=0):

@@ -105,7 +105,7 @@ class Gudi_UpProj_Block(_UpBlock):                               # unet_cspn_nyu
         self.relu = nn.ReLU(inplace=True)
 
     def forward(self, x):
-        if self._fuse_head():
+        if self._fuse_head(x):
             out, shortcut = self._head(x)
             return self.relu(self.bn2(self.conv2(out)) + shortcut)
         x = self._up_pooling(x)
@@ -129,7 +129,7 @@ class Gudi_UpProj_Block_Cat(_UpBlock):                           # unet_cspn_nyu
         self.relu = nn.ReLU(inplace=True)
 
     def forward(self, x, side_input):
-        if self._fuse_head():
+        if self._fuse_head(x):
             out, shortcut = self._head(x)
             out = torch.cat((out, side_input), 1)
             return self.relu(self.bn2(self.conv2(self.relu(self.bn1_1(self.conv1_1(out))))) + shortcut)
@@ -172,7 +172,8 @@ class ResNet(nn.Module):
     fused_decoder (off by default; independent of fused_heads): True, or a collection of block names out of "gud_up_proj_layer1" ..
     "gud_up_proj_layer4" — in eval mode with grad mode off a named block runs its head (un-pool, conv1 -> bn1 -> ReLU, sc_conv1 ->
     sc_bn1) as one ``up_pooling_conv5x5`` call and the rest of itself on stock ops; otherwise exactly the default code.  True selects
-    the blocks where that was measured to be faster (up_pooling.FUSED_DECODER_DEFAULT).  The state_dict is the same either way."""
+    the blocks where that was measured to be faster (up_pooling.FUSED_DECODER_DEFAULT; for a half input — autocast, ``half()`` — FUSED_DECODER_HALF_DEFAULT, on the fp16 kernel of
+    include/cspn_uphalf.h; any other dtype runs the default code).  The state_dict is the same either way."""
 
     def __init__(self, block, layers, up_proj_block=UpProj_Block, decoder_sizes=DECODER_SIZES_NYU, prop_time=24,
                  prop_kernel=3, reference_state_dict=True, cspn_plan=None, affinity_channels=8, fused_heads=False,

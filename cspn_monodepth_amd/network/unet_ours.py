@@ -47,7 +47,7 @@ class Gudi_UpProj_Block(MyBlock):                              # unet_ours.py:20
         self.relu = nn.ReLU(inplace=False)
 
     def forward(self, x):
-        if self._fuse_head():
+        if self._fuse_head(x):
             out, shortcut = self._head(x)
             return self.relu(self.bn2(self.conv2(out)) + shortcut)
         x = self._up_pooling(x, 2)
@@ -66,7 +66,7 @@ class Simple_Gudi_UpConv_Block(MyBlock):                         # unet_ours.py:
         self.relu = nn.ReLU(inplace=False)
 
     def forward(self, x):
-        if self._fuse_head():
+        if self._fuse_head(x):
             return self._head(x)[0]
         return self.relu(self.bn1(self.conv1(self._up_pooling(x, 2))))
 
@@ -92,7 +92,7 @@ class Gudi_UpProj_Block_Cat(MyBlock):                            # unet_ours.py:
         self.relu = nn.ReLU(inplace=False)
 
     def forward(self, x, side_input):
-        if self._fuse_head():
+        if self._fuse_head(x):
             out, shortcut = self._head(x)
             out = torch.cat((out, side_input), 1)
             return self.relu(self.bn2(self.conv2(self.relu(self.bn1_1(self.conv1_1(out))))) + shortcut)
@@ -117,7 +117,8 @@ class ResNet(nn.Module):
     "gud_up_proj_layer4".  In eval mode with grad mode off a named block computes relu(bn1(conv1(up(x)))) and sc_bn1(sc_conv1(up(x)))
     with one ``up_pooling_conv5x5`` call on the compact map and runs the rest of itself on stock ops; in train mode or with grad mode
     on it runs exactly the default code.  True selects the blocks where that was measured to be faster
-    (up_pooling.FUSED_DECODER_DEFAULT).  Modules, parameters and the state_dict are the same either way."""
+    (up_pooling.FUSED_DECODER_DEFAULT; for a half input — autocast, ``half()`` — FUSED_DECODER_HALF_DEFAULT, on the fp16 kernel of
+    include/cspn_uphalf.h; any other dtype runs the default code).  Modules, parameters and the state_dict are the same either way."""
 
     def __init__(self, block, layers, up_proj_block=None, decoder_sizes=DECODER_SIZES_NYU, prop_time=24, cspn_plan=None,
                  fused_heads=False, fused_decoder=False):

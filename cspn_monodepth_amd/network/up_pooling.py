@@ -25,7 +25,8 @@ opt-in — ``fused_heads=True`` of the models — and differs from the two-block
 ``Simple_Gudi_UpConv_Block``, unet_ours.py:160-248): un-pooling by 2, the one or two bias-free 5x5 convolutions over it, their batch
 norms in eval mode and the ReLU of the first, as one implicit GEMM per output phase on the fp32 matrix cores
 (include/cspn_upconv.h).  Forward only and opt-in — ``fused_decoder`` of the models; the filters are reordered once by
-``pack_upconv5x5``.
+``pack_upconv5x5``.  A half ``x`` (``torch.autocast``, ``model.half()``) takes a pack of ``dtype=torch.float16`` and runs on the fp16
+matrix cores with fp32 accumulation and one rounding of the result (include/cspn_uphalf.h).
 """
 import ctypes
 
@@ -191,11 +192,12 @@ def up_pooling_conv3x3(x, weights, oheight, owidth):
 
 class UpconvPack(object):
     """What ``up_pooling_conv5x5`` runs on: the filters of one block head in the order the kernel walks them (``packed``), the folded
-    batch norms (``scale``, ``shift``: fp32 [sum of out_channels], or None), how many leading flat channels get a ReLU, and the
+    batch norms (``scale``, ``shift``: fp32 [sum of out_channels], or None), how many leading flat channels get a ReLU, the ``dtype``
+    of the packed filters and so of the ``x`` it takes and the outputs it gives (fp32: include/cspn_upconv.h, fp16: cspn_uphalf.h), and the
     ``_version`` and ``data_ptr`` of every tensor it was made from — ``stale()`` says whether one of them has changed since."""
 
-    def __init__(self, packed, scale, shift, out_channels, in_channels, relu_channels, sources):
-        self.packed, self.scale, self.shift = packed, scale, shift
+    def __init__(self, packed, scale, shift, out_channels, in_channels, relu_channels, sources, dtype=torch.float32):
+        self.packed, self.scale, self.shift, self.dtype = packed, scale, shift, dtype
         self.out_channels, self.in_channels, self.relu_channels = tuple(out_channels), int(in_channels), int(relu_channels)
         self.sources = tuple(sources)
         self._seen = tuple((t._version, t.data_ptr()) for t in self.sources)
@@ -210,7 +212,10 @@ class UpconvPack(object):
         return len(sources) == len(self.sources) and all(a is b for a, b in zip(sources, self.sources))
 
 
-def _check_filters(who, weights):
+def _check_filters(who, weights, dtype=torch.float32):
+    """The filters as a tuple.  They are fp32, or — for a pack of ``dtype`` fp16 only — fp16 (the parameters of ``model.half()``)."""
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError("%s: a pack is fp32 or fp16, got dtype=%s" % (who, dtype))
     if not isinstance(weights, (tuple, list)):
         raise ValueError("%s: weights must be a tuple of [O,C,5,5] tensors" % who)
     weights = tuple(weights)
@@ -219,8 +224,10 @@ def _check_filters(who, weights):
     for k, w in enumerate(weights):
         if w.dim() != 4 or w.shape[0] < 1 or w.shape[1] < 1 or tuple(w.shape[2:]) != (5, 5) or w.shape[1] != weights[0].shape[1]:
             raise ValueError("%s: filter %d must be [O,%d,5,5], got %s" % (who, k, weights[0].shape[1] if weights[0].dim() == 4 else 0, tuple(w.shape)))
-        if w.dtype != torch.float32:
-            raise ValueError("%s: fp32 only, got %s" % (who, w.dtype))
+        if w.dtype != torch.float32 and not (dtype == torch.float16 and w.dtype == torch.float16):
+            raise ValueError("%s: fp32 only (fp16 filters go into a pack of dtype=torch.float16 alone), got %s" % (who, w.dtype))
+        if w.dtype != weights[0].dtype:
+            raise ValueError("%s: the filters of one pack have one dtype, got %s and %s" % (who, weights[0].dtype, w.dtype))
         if w.numel() >= 2 ** 31:
             raise ValueError("%s: filter %d has 2^31 elements or more" % (who, k))
     return weights
@@ -230,14 +237,18 @@ def _bn_sources(bn):
     return [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
 
 
-def pack_upconv5x5(weights, batchnorms=None, relu=(True, False)):
+def pack_upconv5x5(weights, batchnorms=None, relu=(True, False), dtype=torch.float32):
     """The pack of one block head: ``weights`` — one or two [O_k, C, 5, 5] fp32 filters on a ROCm device (``conv1.weight``,
     ``sc_conv1.weight``) — reordered for the kernel, and ``batchnorms`` — None, or one ``nn.BatchNorm2d`` per filter —
     folded as eval mode applies them: scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale, by device
     tensor ops (nothing is read back).  ``relu``: per filter, whether a ReLU follows; the filters with one come first.  Made once
-    per version of the weights: ``stale()`` of the result says when to make it again."""
+    per version of the weights: ``stale()`` of the result says when to make it again.
+
+    ``dtype``: torch.float32, or torch.float16 for the half-precision kernel (include/cspn_uphalf.h) — fp32 filters are then rounded
+    to fp16 once (autocast: fp32 parameters, half activations), fp16 filters (``model.half()``) are taken as they are; the batch
+    norms are folded in fp32 either way.  The pack takes an ``x`` of its dtype."""
     who = "pack_upconv5x5"
-    weights = _check_filters(who, weights)
+    weights = _check_filters(who, weights, dtype)
     relu = tuple(bool(r) for r in relu)[:len(weights)]
     if len(relu) != len(weights):
         raise ValueError("%s: relu needs one entry per filter" % who)
@@ -253,14 +264,15 @@ def pack_upconv5x5(weights, batchnorms=None, relu=(True, False)):
     dev = _require_device(*weights)
     out_channels, C = [w.shape[0] for w in weights], weights[0].shape[1]
     total = sum(out_channels)
-    nbytes = _lib.lib().cspn_upconv_workspace_bytes(total, C)
+    half = dtype == torch.float16
+    nbytes = (_lib.lib().cspn_uphalf_packed_bytes if half else _lib.lib().cspn_upconv_workspace_bytes)(total, C)
     if not nbytes:
         raise ValueError("%s: the packed form of %d x %d channels has 2^31 elements or more" % (who, total, C))
     sources = list(weights)
     with torch.no_grad():
         wc = [w.detach().contiguous() for w in weights]
-        packed = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        launch(dev, "cspn_upconv_pack", _ptrs(wc), _channels(wc), len(wc), C, 5, 5, _lib.CSPN_F32, _p(packed))
+        packed = torch.empty(nbytes // (2 if half else 4), dtype=dtype, device=dev)
+        launch(dev, "cspn_uphalf_pack" if half else "cspn_upconv_pack", _ptrs(wc), _channels(wc), len(wc), C, 5, 5, _dt(wc[0]), _p(packed))
         scale = shift = None
         if batchnorms is not None:
             scales, shifts = [], []
@@ -276,7 +288,7 @@ def pack_upconv5x5(weights, batchnorms=None, relu=(True, False)):
                 scales.append(s)
                 shifts.append(b)
             scale, shift = torch.cat(scales).contiguous(), torch.cat(shifts).contiguous()
-    return UpconvPack(packed, scale, shift, out_channels, C, sum(o for o, r in zip(out_channels, relu) if r), sources)
+    return UpconvPack(packed, scale, shift, out_channels, C, sum(o for o, r in zip(out_channels, relu) if r), sources, dtype)
 
 
 def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=None, relu_channels=0):
@@ -292,6 +304,10 @@ def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=No
     or 4 taps that meet the compact map (include/cspn_upconv.h), on the fp32 matrix cores — exact fp32 products, every output one
     chain over (tap, channel), so a frame's bits do not depend on the batch and runs repeat.  fp32 on a ROCm device; 1 <= oheight
     <= 2H, 1 <= owidth <= 2W as ``up_pooling`` at scale 2; every tensor below 2^31 elements.
+
+    Half precision: a fp16 ``x`` goes with an ``UpconvPack`` of ``dtype`` fp16 (``pack_upconv5x5(..., dtype=torch.float16)``) and
+    gives fp16 outputs — fp16 products accumulated in fp32 on the fp16 matrix cores, the affine map and the ReLU in fp32, one
+    rounding to fp16 at the end (include/cspn_uphalf.h); the same contract otherwise.  The filters themselves are taken in fp32 only.
 
     ``pack_or_weights``: an ``UpconvPack`` (its scale, shift and ReLU count apply; the arguments of that name must be left alone),
     or the filters themselves — packed for this one call — with ``scale`` / ``shift`` (fp32 [O_0 + O_1], both or neither) and
@@ -318,8 +334,13 @@ def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=No
     N, C, H, W = x.shape
     if C != C_w:
         raise ValueError("%s: x has %d channels, the filters take %d" % (who, C, C_w))
-    if x.dtype != torch.float32:
-        raise ValueError("%s: fp32 only, got %s" % (who, x.dtype))
+    if pack is None:
+        if x.dtype != torch.float32:
+            raise ValueError("%s: fp32 only with the filters themselves (a half x takes pack_upconv5x5(..., dtype=torch.float16)), got %s"
+                             % (who, x.dtype))
+    elif x.dtype != pack.dtype:
+        raise ValueError("%s: x is %s, the pack was made for %s (pack_upconv5x5(..., dtype=...); fp32 and fp16 packs exist)"
+                         % (who, x.dtype, pack.dtype))
     total = sum(out_channels)
     if (scale is None) != (shift is None):
         raise ValueError("%s: scale and shift come together" % who)
@@ -344,10 +365,13 @@ def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=No
     if pack is None:
         pack = pack_upconv5x5(weights, None, (False,) * len(weights))
     xc = x.contiguous()
-    outs = tuple(torch.empty((N, o, oheight, owidth), dtype=torch.float32, device=dev) for o in out_channels)
-    launch(dev, "cspn_upconv_forward", _p(xc), _lib.CSPN_F32, _p(pack.packed), _p(None if scale is None else scale.contiguous()),
-           _p(None if shift is None else shift.contiguous()), relu_channels, _ptrs(outs), (ctypes.c_int * len(outs))(*out_channels), len(outs),
-           N, C, H, W, oheight, owidth)
+    outs = tuple(torch.empty((N, o, oheight, owidth), dtype=pack.dtype, device=dev) for o in out_channels)
+    tail = (_p(pack.packed), _p(None if scale is None else scale.contiguous()), _p(None if shift is None else shift.contiguous()),
+            relu_channels, _ptrs(outs), (ctypes.c_int * len(outs))(*out_channels), len(outs), N, C, H, W, oheight, owidth)
+    if pack.dtype == torch.float16:
+        launch(dev, "cspn_uphalf_forward", _p(xc), *tail)
+    else:
+        launch(dev, "cspn_upconv_forward", _p(xc), _lib.CSPN_F32, *tail)
     return outs
 
 
@@ -356,11 +380,16 @@ DECODER_BLOCKS = ("gud_up_proj_layer1", "gud_up_proj_layer2", "gud_up_proj_layer
 # more than the spread of the two measurements — its 90th percentile below the stock 10th, warm and cache-cold
 # (profiles/r18_upconv_bench.json, RESULTS.md row 33: all four, 3.3 to 5.3 times).
 FUSED_DECODER_DEFAULT = ("gud_up_proj_layer1", "gud_up_proj_layer2", "gud_up_proj_layer3", "gud_up_proj_layer4")
+# The same rule for half inputs, from tools/uphalf_bench.py: the half kernel's 90th percentile below the 10th of the stock half head
+# (un-pool, MIOpen convolutions, batch norms and ReLU on half tensors), warm and cache-cold (profiles/r19_uphalf_bench.json,
+# RESULTS.md row 34: all four, 3.8 to 9.5 times).
+FUSED_DECODER_HALF_DEFAULT = ("gud_up_proj_layer1", "gud_up_proj_layer2", "gud_up_proj_layer3", "gud_up_proj_layer4")
 
 
 def select_fused_decoder(model, fused_decoder):
-    """The `fused_decoder` switch of the models: False / None, True (FUSED_DECODER_DEFAULT) or a collection of block names out of
-    DECODER_BLOCKS.  Marks the named blocks and returns their names in decoder order (what the model keeps as `fused_decoder`)."""
+    """The `fused_decoder` switch of the models: False / None, True (FUSED_DECODER_DEFAULT; for half inputs
+    FUSED_DECODER_HALF_DEFAULT) or a collection of block names out of DECODER_BLOCKS (for inputs of either precision).  Marks the named
+    blocks and returns their names in decoder order (what the model keeps as `fused_decoder`)."""
     if fused_decoder is True:
         names = FUSED_DECODER_DEFAULT
     elif not fused_decoder:
@@ -374,6 +403,7 @@ def select_fused_decoder(model, fused_decoder):
         raise ValueError("fused_decoder: %s not among %s" % (unknown, list(DECODER_BLOCKS)))
     for n in DECODER_BLOCKS:
         getattr(model, n).fused_head = n in names
+        getattr(model, n).fused_head_half = n in (FUSED_DECODER_HALF_DEFAULT if fused_decoder is True else names)
     return tuple(n for n in DECODER_BLOCKS if n in names)
 
 
@@ -381,12 +411,23 @@ class FusedHead(object):
     """Mixed into the decoder blocks: the block's head — un-pool, conv1 -> bn1 -> ReLU and, where the block has one, sc_conv1 -> sc_bn1 —
     as one ``up_pooling_conv5x5`` call when the block is marked (`fused_head`, set by the model's `fused_decoder`), in eval mode and
     with grad mode off.  The pack is made at the first such call, made again when a source changed (``load_state_dict``, an
-    in-place update, a parameter replaced by ``.to()``) and dropped by ``train()``; it is no parameter, buffer or module."""
+    in-place update, a parameter replaced by ``.to()``) and dropped by ``train()``; it is no parameter, buffer or module.  It is made
+    for the dtype of the block's input, fp32 or fp16, and made again when that changes (one pack at a time: a model run in both
+    precisions in turn repacks at every change)."""
     fused_head = False
+    fused_head_half = None               # None: as fused_head (a block marked by hand)
     _upconv_pack = None
 
-    def _fuse_head(self):
-        return self.fused_head and not self.training and not torch.is_grad_enabled()
+    def _fuse_head(self, x=None):
+        """Does this call run the fused head?  ``x``: the block's input — fp32 goes by `fused_head`, fp16 (autocast, ``model.half()``)
+        by `fused_head_half`, any other dtype runs the stock block."""
+        if self.training or torch.is_grad_enabled():
+            return False
+        if x is None or x.dtype == torch.float32:
+            return self.fused_head
+        if x.dtype == torch.float16:
+            return self.fused_head if self.fused_head_half is None else self.fused_head_half
+        return False
 
     def _head(self, x):
         """(relu(bn1(conv1(u))), sc_bn1(sc_conv1(u)) or None) for u = the un-pooled x, without u."""
@@ -396,8 +437,8 @@ class FusedHead(object):
             bns.append(self.sc_bn1)
         weights = [c.weight for c in convs]
         pack = self._upconv_pack
-        if pack is None or pack.stale() or not pack.made_from(weights + [t for bn in bns for t in _bn_sources(bn)]):
-            pack = self._upconv_pack = pack_upconv5x5(weights, bns, (True, False)[:len(convs)])
+        if pack is None or pack.dtype != x.dtype or pack.stale() or not pack.made_from(weights + [t for bn in bns for t in _bn_sources(bn)]):
+            pack = self._upconv_pack = pack_upconv5x5(weights, bns, (True, False)[:len(convs)], dtype=x.dtype)
         outs = up_pooling_conv5x5(x, pack, self.oheight, self.owidth)
         return outs[0], (outs[1] if len(outs) > 1 else None)
 

@@ -1,195 +1,62 @@
 // cspn_upconv.hip — the head of a decoder block fused with its un-pooling (include/cspn_upconv.h).
 //
-//   network/unet_ours.py:160-248 UpProj_Block / Gudi_UpProj_Block / Gudi_UpProj_Block_Cat / Simple_Gudi_UpConv_Block: zero-insertion
-//   un-pooling by 2, crop to oh x ow, then one or two bias-free 5x5 convolutions over that map, each followed by a batch norm (in eval
-//   mode a per-channel affine map) and, for the first, a ReLU.
-// The un-pooled map is never formed.  Output pixel (2i + a, 2j + b) of a pad-2 5x5 window over it meets the compact map through the
-// taps (ky, kx) with a + ky and b + kx even: rows i - 1, i, i + 1 (ky = 0, 2, 4) for a = 0 and i, i + 1 (ky = 1, 3) for a = 1,
-// likewise the columns — 9, 6, 6, 4 taps for the phases (0,0), (0,1), (1,0), (1,1).
-//   upconv_pack  the filters -> wp[25 taps, phase-major][Cp][Mp]: tap t of phase p, channel c, flat output channel m; Cp = C rounded
-//                up to KC, Mp = the flat channels rounded up to TM, zero-filled, so that the forward loads whole tiles unguarded
-//   upconv_fwd   an implicit GEMM per phase: a workgroup of 4 wavefronts owns a TM x TN = 128 x 128 tile of (flat channels) x (the
-//                phase's pixels over the whole batch) and walks K = (tap, channel) in chunks of KC = 32 channels of one tap: the
-//                filter chunk [KC][TM] and the gathered pixels [KC][TN] go through LDS, a wavefront holds 2 x 2 accumulators of
-//                v_mfma_f32_32x32x2_f32 (64 x 64).  Single-buffered: the loads of a chunk are issued before the barrier that ends
-//                the previous chunk's products, and several workgroups per CU cover each other's loads.
-// An output element is one chain over K in the packed order, whatever its tile: no split-K, no atomics.  fp32 only.
-#include "cspn_common.hpp"
+// The computation, the decomposition into four phases, the kernels and the argument checks are those of cspn_upconv_core.hpp; here is
+// the fp32 form of a chunk.
+//   pack  wp[25 taps, phase-major][Cp][Mp] fp32: filter-contiguous, a row of the chunk is TM consecutive floats
+//   fwd   the filter chunk [KC][TM] and the gathered pixels [KC][TN] go through LDS as they are loaded: a thread fetches 4 x 16 bytes of
+//         the filter chunk (rows (t >> 5) + 8 r) and pixel t & 127 of the channels (t >> 7) + 2 r, consecutive lanes on consecutive
+//         pixels of a row.  v_mfma_f32_32x32x2_f32: lane l holds A[l & 31][l >> 5] and B[l >> 5][l & 31], so a step reads two rows
+//         of each tile.  Exact fp32 products.
+// fp32 only.
+#include "cspn_upconv_core.hpp"
 #include "cspn_upconv.h"
 
 namespace {
 
-constexpr int TM = 128, TN = 128, KC = 32, THREADS = 256;
-constexpr int TAPS = 25;
+struct F32 {
+    using T = float;
+    using ATile = float[KC][TM];
+    using BTile = float[KC][TN];
+    struct Chunk {
+        v4f wv[4];
+        float xv[16];
+    };
+    static constexpr bool CHANNEL_INNER = false;
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-struct Args {
-    const float* x;
-    const float* wp;
-    const float* scale;       // null: no affine map
-    const float* shift;
-    float* y0;
-    float* y1;
-    int O0, O1, M, Mp, relu;
-    int N, C, Cp, H, W, oh, ow;
-    int mtiles;
-    unsigned first[5];        // first workgroup of phase p (p = 2a + b), first[4] = the grid
-};
-
-// phase p = 2a + b: rows of taps, columns of taps, first tap in the packed order
-__host__ __device__ constexpr int tap_rows(int p) { return (p >> 1) ? 2 : 3; }
-__host__ __device__ constexpr int tap_cols(int p) { return (p & 1) ? 2 : 3; }
-__host__ __device__ constexpr int tap_base(int p) { return p == 0 ? 0 : p == 1 ? 9 : p == 2 ? 15 : 21; }
-
-// e = (packed tap, channel, flat output channel)
-__global__ __launch_bounds__(256) void upconv_pack(const float* __restrict__ w0, const float* __restrict__ w1, float* __restrict__ wp,
-                                                   int O0, int M, int Mp, int C, int Cp, size_t elems) {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= elems) return;
-    const int m = (int)(e % Mp);
-    const size_t row = e / Mp;
-    const int c = (int)(row % Cp), tg = (int)(row / Cp);
-    const int p = tg < 9 ? 0 : tg < 15 ? 1 : tg < 21 ? 2 : 3;
-    const int t = tg - tap_base(p);
-    const int tr = t / tap_cols(p), tc = t - tr * tap_cols(p);
-    const int ky = 2 * tr + (p >> 1), kx = 2 * tc + (p & 1);
-    float v = 0.f;
-    if (m < M && c < C) {
-        const float* src = m < O0 ? w0 + (size_t)m * C * 25 : w1 + (size_t)(m - O0) * C * 25;
-        v = src[(size_t)c * 25 + ky * 5 + kx];
+    static __device__ __forceinline__ const float* wtile(const Args<float>& a, int mt, int t) {
+        return a.wp + (size_t)mt * TM + (size_t)(t >> 5) * a.Mp + 4 * (t & 31);
     }
-    wp[e] = v;
-}
-
-// pixel n of phase p -> frame, compact row and column
-struct Pixel {
-    int frame, i, j;
-    bool ok;
-};
-__device__ __forceinline__ Pixel decode(unsigned n, unsigned npix, int Ha, int Wb) {
-    Pixel q;
-    q.ok = n < npix;
-    const unsigned nn = q.ok ? n : 0u;
-    const unsigned per = (unsigned)Ha * Wb;
-    q.frame = nn / per;
-    const unsigned r = nn - q.frame * per;
-    q.i = r / Wb;
-    q.j = r - q.i * Wb;
-    return q;
-}
-
-__global__ __launch_bounds__(THREADS) void upconv_fwd(const Args a) {
-    __shared__ __attribute__((aligned(16))) float As[KC][TM];
-    __shared__ __attribute__((aligned(16))) float Bs[KC][TN];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l31 = lane & 31, lh = lane >> 5;
-
-    const unsigned bid = blockIdx.x;
-    const int p = bid >= a.first[3] ? 3 : bid >= a.first[2] ? 2 : bid >= a.first[1] ? 1 : 0;
-    const unsigned local = bid - (p == 3 ? a.first[3] : p == 2 ? a.first[2] : p == 1 ? a.first[1] : 0u);
-    const int mt = local % a.mtiles;
-    const unsigned nt = local / a.mtiles;
-    const int pa = p >> 1, pb = p & 1;
-    const int Hc = (a.oh + 1) >> 1, Wc = (a.ow + 1) >> 1;        // the compact pixels that take part
-    const int Ha = (a.oh + 1 - pa) >> 1, Wb = (a.ow + 1 - pb) >> 1;      // the phase's output pixels: 2i + a < oh, 2j + b < ow
-    const unsigned npix = (unsigned)a.N * Ha * Wb;
-    const int ntc = tap_cols(p), ntaps = tap_rows(p) * ntc;
-    const int di0 = pa ? 0 : -1, dj0 = pb ? 0 : -1;
-    const size_t hw = (size_t)a.H * a.W;
-
-    // the loads of this thread: pixel t & 127 for the channels (t >> 7) + 2 r of a chunk; 4 x 16 bytes of the filter chunk
-    const Pixel mine = decode(nt * TN + (t & 127), npix, Ha, Wb);
-    const float* xpix = a.x + (size_t)mine.frame * a.C * hw + (size_t)mine.i * a.W + mine.j;
-    const int kb = t >> 7;
-    const float* wtile = a.wp + (size_t)mt * TM + (size_t)(t >> 5) * a.Mp + 4 * (t & 31);      // rows (t >> 5) + 8 r
-
-    v16f acc[2][2];
+    static __device__ __forceinline__ void load(Chunk& k, const Args<float>& a, const float* wt, const float* xt, int c0, int t, bool there,
+                                                size_t hw) {
+        const int kb = t >> 7;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+        for (int r = 0; r < 4; ++r) k.wv[r] = *reinterpret_cast<const v4f*>(wt + (size_t)(c0 + 8 * r) * a.Mp);
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int cchunks = a.Cp / KC;
-    for (int tap = 0; tap < ntaps; ++tap) {
-        const int tr = tap / ntc, tc = tap - tr * ntc;
-        const int di = di0 + tr, dj = dj0 + tc;
-        const int ii = mine.i + di, jj = mine.j + dj;
-        const bool there = mine.ok && ii >= 0 && ii < Hc && jj >= 0 && jj < Wc;
-        const float* xt = xpix + (long)di * a.W + dj;
-        const float* wt = wtile + (size_t)(tap_base(p) + tap) * a.Cp * a.Mp;
-        for (int cc = 0; cc < cchunks; ++cc) {
-            const int c0 = cc * KC;
-            v4f wv[4];
-            float xv[16];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) wv[r] = *reinterpret_cast<const v4f*>(wt + (size_t)(c0 + 8 * r) * a.Mp);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int c = c0 + kb + 2 * r;
-                xv[r] = (there && c < a.C) ? xt[(size_t)c * hw] : 0.f;
-            }
-            __syncthreads();                                     // the previous chunk has been read
-#pragma unroll
-            for (int r = 0; r < 4; ++r) *reinterpret_cast<v4f*>(&As[(t >> 5) + 8 * r][4 * (t & 31)]) = wv[r];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Bs[kb + 2 * r][t & 127] = xv[r];
-            __syncthreads();
-#pragma unroll
-            for (int s = 0; s < KC / 2; ++s) {
-                const int k = 2 * s + lh;
-                const float a0 = As[k][wm * 64 + l31], a1 = As[k][wm * 64 + 32 + l31];
-                const float b0 = Bs[k][wn * 64 + l31], b1 = Bs[k][wn * 64 + 32 + l31];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-            }
+        for (int r = 0; r < 16; ++r) {
+            const int c = c0 + kb + 2 * r;
+            k.xv[r] = (there && c < a.C) ? xt[(size_t)c * hw] : 0.f;
         }
     }
-
-    // accumulator register r of a 32 x 32 tile: column (pixel) lane & 31, row (channel) (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-    const size_t plane = (size_t)a.oh * a.ow;
+    static __device__ __forceinline__ void stage(ATile& As, BTile& Bs, const Chunk& k, int t) {
+        const int kb = t >> 7;
 #pragma unroll
-    for (int tn = 0; tn < 2; ++tn) {
-        const Pixel q = decode(nt * TN + wn * 64 + tn * 32 + l31, npix, Ha, Wb);
-        if (!q.ok) continue;
-        const size_t at = (size_t)(2 * q.i + pa) * a.ow + (2 * q.j + pb);
+        for (int r = 0; r < 4; ++r) *reinterpret_cast<v4f*>(&As[(t >> 5) + 8 * r][4 * (t & 31)]) = k.wv[r];
 #pragma unroll
-        for (int tm = 0; tm < 2; ++tm) {
+        for (int r = 0; r < 16; ++r) Bs[kb + 2 * r][t & 127] = k.xv[r];
+    }
+    static __device__ __forceinline__ void products(const ATile& As, const BTile& Bs, v16f (&acc)[2][2], int wm, int wn, int l31, int lh) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = mt * TM + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (m >= a.M) continue;
-                float y = acc[tm][tn][r];
-                if (a.scale) y = fmaf(y, a.scale[m], a.shift[m]);
-                if (m < a.relu) y = y < 0.f ? 0.f : y;           // NaN stays NaN
-                float* dst = m < a.O0 ? a.y0 + ((size_t)q.frame * a.O0 + m) * plane : a.y1 + ((size_t)q.frame * a.O1 + (m - a.O0)) * plane;
-                dst[at] = y;
-            }
+        for (int s = 0; s < KC / 2; ++s) {
+            const int kk = 2 * s + lh;
+            const float a0 = As[kk][wm * 64 + l31], a1 = As[kk][wm * 64 + 32 + l31];
+            const float b0 = Bs[kk][wn * 64 + l31], b1 = Bs[kk][wn * 64 + 32 + l31];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
         }
     }
-}
-
-inline int round_up(int v, int to) { return ceil_div(v, to) * to; }
-
-// the packed filters: elements, or 0 for a bad size
-size_t packed_elems(int M, int C) {
-    if (M < 1 || C < 1 || M > (1 << 24) || C > (1 << 24)) return 0;
-    const double e = (double)TAPS * round_up(C, KC) * round_up(M, TM);
-    return e >= 2147483648.0 ? 0 : (size_t)e;
-}
-
-int check_filters(const char* who, const int* out_channels, int n, int& O0, int& O1) {
-    if (!out_channels || n < 1 || n > CSPN_UPCONV_MAX_FILTERS) return fail("%s: between 1 and %d filters, got %d", who, CSPN_UPCONV_MAX_FILTERS, n);
-    for (int k = 0; k < n; ++k)
-        if (out_channels[k] < 1 || out_channels[k] > (1 << 23)) return fail("%s: filter %d has %d output channels", who, k, out_channels[k]);
-    O0 = out_channels[0], O1 = n > 1 ? out_channels[1] : 0;
-    return 1;
-}
+};
 
 }  // namespace
 
@@ -203,23 +70,10 @@ int cspn_upconv_pack(const void* const* weights, const int* out_channels, int n_
                      cspn_stream_t stream) {
     const char* who = "cspn_upconv_pack";
     if (dtype != CSPN_F32) return fail("%s: fp32 only", who);
-    if (kh != 5 || kw != 5) return fail("%s: the filters must be 5x5, got %dx%d", who, kh, kw);
-    int O0 = 0, O1 = 0;
-    if (!check_filters(who, out_channels, n_filters, O0, O1)) return 0;
-    if (!weights || !packed) return fail("%s: null pointer", who);
-    for (int k = 0; k < n_filters; ++k)
-        if (!weights[k]) return fail("%s: null pointer (filter %d)", who, k);
-    if (!aligned16(packed)) return fail("%s: packed must be 16-byte aligned", who);
-    const int M = O0 + O1;
-    const size_t elems = packed_elems(M, C);
-    if (!elems) return fail("%s: bad size (%d output channels, C=%d), or a packed form of 2^31 elements or more", who, M, C);
-    if ((double)out_channels[0] * C * 25 >= 2147483648.0 || (double)O1 * C * 25 >= 2147483648.0) return fail("%s: a filter of 2^31 elements or more", who);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    CSPN_PRE(st), upconv_pack<<<dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st>>>(
-        static_cast<const float*>(weights[0]), n_filters > 1 ? static_cast<const float*>(weights[1]) : nullptr, static_cast<float*>(packed), O0, M,
-        round_up(M, TM), C, round_up(C, KC), elems);
-    HIP_OK(hipGetLastError());
-    return 1;
+    int O0 = 0, M = 0;
+    size_t elems = 0;
+    if (!check_pack(who, weights, out_channels, n_filters, C, kh, kw, packed, CSPN_UPCONV_MAX_FILTERS, O0, M, elems)) return 0;
+    return launch_pack<float, F32>(weights, n_filters, packed, O0, M, C, elems, stream);
 }
 
 int cspn_upconv_forward(const void* x, int dtype, const void* packed, const void* scale, const void* shift, int relu_channels,
@@ -227,39 +81,8 @@ int cspn_upconv_forward(const void* x, int dtype, const void* packed, const void
                         cspn_stream_t stream) {
     const char* who = "cspn_upconv_forward";
     if (dtype != CSPN_F32) return fail("%s: fp32 only", who);
-    if (N < 1 || C < 1 || H < 1 || W < 1) return fail("%s: bad shape (N=%d, C=%d, H=%d, W=%d)", who, N, C, H, W);
-    if (oh < 1 || ow < 1 || (long)oh > 2L * H || (long)ow > 2L * W)
-        return fail("%s: output %dx%d must lie in [1, 2H] x [1, 2W] = %ldx%ld", who, oh, ow, 2L * H, 2L * W);
-    Args a;
-    if (!check_filters(who, out_channels, n_outs, a.O0, a.O1)) return 0;
-    a.M = a.O0 + a.O1;
-    if (!packed_elems(a.M, C)) return fail("%s: bad size (%d output channels, C=%d)", who, a.M, C);
-    if ((double)N * C * H * W >= 2147483648.0 || (double)N * a.O0 * oh * ow >= 2147483648.0 || (double)N * a.O1 * oh * ow >= 2147483648.0)
-        return fail("%s: a tensor of 2^31 elements or more; split the batch", who);
-    if (!x || !packed || !outs) return fail("%s: null pointer", who);
-    for (int k = 0; k < n_outs; ++k)
-        if (!outs[k]) return fail("%s: null pointer (output %d)", who, k);
-    if (!aligned16(packed)) return fail("%s: packed must be 16-byte aligned", who);
-    if (!scale != !shift) return fail("%s: scale and shift come together", who);
-    if (relu_channels < 0 || relu_channels > a.M) return fail("%s: relu_channels %d outside [0, %d]", who, relu_channels, a.M);
-    a.x = static_cast<const float*>(x), a.wp = static_cast<const float*>(packed);
-    a.scale = static_cast<const float*>(scale), a.shift = static_cast<const float*>(shift);
-    a.y0 = static_cast<float*>(outs[0]), a.y1 = n_outs > 1 ? static_cast<float*>(outs[1]) : nullptr;
-    a.Mp = round_up(a.M, TM), a.relu = relu_channels;
-    a.N = N, a.C = C, a.Cp = round_up(C, KC), a.H = H, a.W = W, a.oh = oh, a.ow = ow;
-    a.mtiles = a.Mp / TM;
-    double blocks = 0;
-    for (int p = 0; p < 4; ++p) {
-        a.first[p] = (unsigned)blocks;
-        const double npix = (double)N * ((oh + 1 - (p >> 1)) / 2) * ((ow + 1 - (p & 1)) / 2);      // < 2^31: an output has fewer elements
-        blocks += (double)(((long)npix + TN - 1) / TN) * a.mtiles;
-        if (blocks >= 2147483648.0) return fail("%s: more than 2^31 tiles; split the batch", who);
-    }
-    a.first[4] = (unsigned)blocks;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    CSPN_PRE(st), upconv_fwd<<<dim3(a.first[4]), dim3(THREADS), 0, st>>>(a);
-    HIP_OK(hipGetLastError());
-    return 1;
+    return forward<F32>(who, x, packed, scale, shift, relu_channels, outs, out_channels, n_outs, N, C, H, W, oh, ow, CSPN_UPCONV_MAX_FILTERS,
+                        stream);
 }
 
 }  // extern "C"

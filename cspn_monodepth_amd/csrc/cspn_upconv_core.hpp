@@ -1,0 +1,259 @@
+// cspn_upconv_core.hpp — what the fused decoder-block heads share: cspn_upconv.hip (fp32) and cspn_uphalf.hip (fp16, f-13).
+//
+//   network/unet_ours.py:160-248 UpProj_Block / Gudi_UpProj_Block / Gudi_UpProj_Block_Cat / Simple_Gudi_UpConv_Block: zero-insertion
+//   un-pooling by 2, crop to oh x ow, then one or two bias-free 5x5 convolutions over that map, each followed by a batch norm (in eval
+//   mode a per-channel affine map) and, for the first, a ReLU.
+// The un-pooled map is never formed.  Output pixel (2i + a, 2j + b) of a pad-2 5x5 window over it meets the compact map through the
+// taps (ky, kx) with a + ky and b + kx even: rows i - 1, i, i + 1 (ky = 0, 2, 4) for a = 0 and i, i + 1 (ky = 1, 3) for a = 1,
+// likewise the columns — 9, 6, 6, 4 taps for the phases (0,0), (0,1), (1,0), (1,1).  A neighbour outside the compact pixels that take
+// part contributes zeros.
+//   pack   the filters -> 25 taps, phase-major, of a Cp x Mp matrix each (tap t of phase p, channel c, flat output channel m; Cp = C
+//          rounded up to KC, Mp = the flat channels rounded up to TM, zero-filled, so that the forward loads whole tiles unguarded),
+//          in the element type and the order (channel- or filter-contiguous) of the precision
+//   fwd    an implicit GEMM per phase: M = flat channels, N = the phase's pixels over the whole batch, K = (tap, channel).  A workgroup
+//          of 4 wavefronts owns a TM x TN = 128 x 128 tile and walks K in chunks of KC = 32 channels of one tap: the filter chunk and
+//          the gathered pixels go through LDS, a wavefront holds 2 x 2 accumulators of a 32 x 32 matrix instruction (64 x 64).
+//          Single-buffered: the loads of a chunk are issued before the barrier that ends the previous chunk's products, and several
+//          workgroups per CU cover each other's loads.
+// An output element is one chain over K in the packed order, whatever its tile: no split-K, no atomics.
+// A precision is a policy P: the element type T, the two LDS tiles, the registers of a chunk, and how a chunk is found (wtile), loaded,
+// staged and multiplied; everything else, the argument checks of the entry points included, is here once.
+#pragma once
+#include "cspn_common.hpp"
+
+namespace {
+
+constexpr int TM = 128, TN = 128, KC = 32, THREADS = 256;
+constexpr int TAPS = 25;
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+
+template <typename T>
+struct Args {
+    const T* x;
+    const T* wp;
+    const float* scale;       // null: no affine map
+    const float* shift;
+    T* y0;
+    T* y1;
+    int O0, O1, M, Mp, relu;
+    int N, C, Cp, H, W, oh, ow;
+    int mtiles;
+    unsigned first[5];        // first workgroup of phase p (p = 2a + b), first[4] = the grid
+};
+
+// phase p = 2a + b: rows of taps, columns of taps, first tap in the packed order
+__host__ __device__ constexpr int tap_rows(int p) { return (p >> 1) ? 2 : 3; }
+__host__ __device__ constexpr int tap_cols(int p) { return (p & 1) ? 2 : 3; }
+__host__ __device__ constexpr int tap_base(int p) { return p == 0 ? 0 : p == 1 ? 9 : p == 2 ? 15 : 21; }
+
+// e = (packed tap, channel, flat output channel), or with CHANNEL_INNER (packed tap, flat output channel, channel); S -> D rounds to
+// nearest even
+template <typename S, typename D, bool CHANNEL_INNER>
+__global__ __launch_bounds__(256) void pack(const S* __restrict__ w0, const S* __restrict__ w1, D* __restrict__ wp, int O0, int M, int Mp,
+                                            int C, int Cp, size_t elems) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= elems) return;
+    const int inner = CHANNEL_INNER ? Cp : Mp, outer = CHANNEL_INNER ? Mp : Cp;
+    const int in = (int)(e % inner);
+    const size_t row = e / inner;
+    const int out = (int)(row % outer), tg = (int)(row / outer);
+    const int m = CHANNEL_INNER ? out : in, c = CHANNEL_INNER ? in : out;
+    const int p = tg < 9 ? 0 : tg < 15 ? 1 : tg < 21 ? 2 : 3;
+    const int t = tg - tap_base(p);
+    const int tr = t / tap_cols(p), tc = t - tr * tap_cols(p);
+    const int ky = 2 * tr + (p >> 1), kx = 2 * tc + (p & 1);
+    D v = (D)0.f;
+    if (m < M && c < C) {
+        const S* src = m < O0 ? w0 + (size_t)m * C * 25 : w1 + (size_t)(m - O0) * C * 25;
+        v = (D)src[(size_t)c * 25 + ky * 5 + kx];
+    }
+    wp[e] = v;
+}
+
+// pixel n of phase p -> frame, compact row and column
+struct Pixel {
+    int frame, i, j;
+    bool ok;
+};
+__device__ __forceinline__ Pixel decode(unsigned n, unsigned npix, int Ha, int Wb) {
+    Pixel q;
+    q.ok = n < npix;
+    const unsigned nn = q.ok ? n : 0u;
+    const unsigned per = (unsigned)Ha * Wb;
+    q.frame = nn / per;
+    const unsigned r = nn - q.frame * per;
+    q.i = r / Wb;
+    q.j = r - q.i * Wb;
+    return q;
+}
+
+template <class P>
+__global__ __launch_bounds__(THREADS) void fwd(const Args<typename P::T> a) {
+    using T = typename P::T;
+    __shared__ __attribute__((aligned(16))) typename P::ATile As;
+    __shared__ __attribute__((aligned(16))) typename P::BTile Bs;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int l31 = lane & 31, lh = lane >> 5;
+
+    const unsigned bid = blockIdx.x;
+    const int p = bid >= a.first[3] ? 3 : bid >= a.first[2] ? 2 : bid >= a.first[1] ? 1 : 0;
+    const unsigned local = bid - (p == 3 ? a.first[3] : p == 2 ? a.first[2] : p == 1 ? a.first[1] : 0u);
+    const int mt = local % a.mtiles;
+    const unsigned nt = local / a.mtiles;
+    const int pa = p >> 1, pb = p & 1;
+    const int Hc = (a.oh + 1) >> 1, Wc = (a.ow + 1) >> 1;        // the compact pixels that take part
+    const int Ha = (a.oh + 1 - pa) >> 1, Wb = (a.ow + 1 - pb) >> 1;      // the phase's output pixels: 2i + a < oh, 2j + b < ow
+    const unsigned npix = (unsigned)a.N * Ha * Wb;
+    const int ntc = tap_cols(p), ntaps = tap_rows(p) * ntc;
+    const int di0 = pa ? 0 : -1, dj0 = pb ? 0 : -1;
+    const size_t hw = (size_t)a.H * a.W;
+
+    // the loads of this thread: pixel t & 127 for the policy's share of a chunk's channels, and its share of the filter chunk
+    const Pixel mine = decode(nt * TN + (t & 127), npix, Ha, Wb);
+    const T* xpix = a.x + (size_t)mine.frame * a.C * hw + (size_t)mine.i * a.W + mine.j;
+    const T* wtile = P::wtile(a, mt, t);
+
+    v16f acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    const int cchunks = a.Cp / KC;
+    for (int tap = 0; tap < ntaps; ++tap) {
+        const int tr = tap / ntc, tc = tap - tr * ntc;
+        const int di = di0 + tr, dj = dj0 + tc;
+        const int ii = mine.i + di, jj = mine.j + dj;
+        const bool there = mine.ok && ii >= 0 && ii < Hc && jj >= 0 && jj < Wc;
+        const T* xt = xpix + (long)di * a.W + dj;
+        const T* wt = wtile + (size_t)(tap_base(p) + tap) * a.Mp * a.Cp;
+        for (int cc = 0; cc < cchunks; ++cc) {
+            typename P::Chunk k;
+            P::load(k, a, wt, xt, cc * KC, t, there, hw);
+            __syncthreads();                                     // the previous chunk has been read
+            P::stage(As, Bs, k, t);
+            __syncthreads();
+            P::products(As, Bs, acc, wm, wn, l31, lh);
+        }
+    }
+
+    // accumulator register r of a 32 x 32 tile: column (pixel) lane & 31, row (channel) (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    const size_t plane = (size_t)a.oh * a.ow;
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) {
+        const Pixel q = decode(nt * TN + wn * 64 + tn * 32 + l31, npix, Ha, Wb);
+        if (!q.ok) continue;
+        const size_t at = (size_t)(2 * q.i + pa) * a.ow + (2 * q.j + pb);
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = mt * TM + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                if (m >= a.M) continue;
+                float y = acc[tm][tn][r];
+                if (a.scale) y = fmaf(y, a.scale[m], a.shift[m]);
+                if (m < a.relu) y = y < 0.f ? 0.f : y;           // NaN stays NaN
+                T* dst = m < a.O0 ? a.y0 + ((size_t)q.frame * a.O0 + m) * plane : a.y1 + ((size_t)q.frame * a.O1 + (m - a.O0)) * plane;
+                dst[at] = (T)y;                                  // the one rounding to T, to nearest even; overflow gives +-Inf
+            }
+        }
+    }
+}
+
+inline int round_up(int v, int to) { return ceil_div(v, to) * to; }
+
+// the packed filters: elements, or 0 for a bad size
+size_t packed_elems(int M, int C) {
+    if (M < 1 || C < 1 || M > (1 << 24) || C > (1 << 24)) return 0;
+    const double e = (double)TAPS * round_up(C, KC) * round_up(M, TM);
+    return e >= 2147483648.0 ? 0 : (size_t)e;
+}
+
+int check_filters(const char* who, const int* out_channels, int n, int& O0, int& O1, int max_filters) {
+    if (!out_channels || n < 1 || n > max_filters) return fail("%s: between 1 and %d filters, got %d", who, max_filters, n);
+    for (int k = 0; k < n; ++k)
+        if (out_channels[k] < 1 || out_channels[k] > (1 << 23)) return fail("%s: filter %d has %d output channels", who, k, out_channels[k]);
+    O0 = out_channels[0], O1 = n > 1 ? out_channels[1] : 0;
+    return 1;
+}
+
+// The argument rules of a pack entry point behind its own rule for the dtype; `who` is the entry point's name.
+int check_pack(const char* who, const void* const* weights, const int* out_channels, int n_filters, int C, int kh, int kw, const void* packed,
+               int max_filters, int& O0, int& M, size_t& elems) {
+    if (kh != 5 || kw != 5) return fail("%s: the filters must be 5x5, got %dx%d", who, kh, kw);
+    int O1 = 0;
+    if (!check_filters(who, out_channels, n_filters, O0, O1, max_filters)) return 0;
+    if (!weights || !packed) return fail("%s: null pointer", who);
+    for (int k = 0; k < n_filters; ++k)
+        if (!weights[k]) return fail("%s: null pointer (filter %d)", who, k);
+    if (!aligned16(packed)) return fail("%s: packed must be 16-byte aligned", who);
+    M = O0 + O1;
+    elems = packed_elems(M, C);
+    if (!elems) return fail("%s: bad size (%d output channels, C=%d), or a packed form of 2^31 elements or more", who, M, C);
+    if ((double)out_channels[0] * C * 25 >= 2147483648.0 || (double)O1 * C * 25 >= 2147483648.0) return fail("%s: a filter of 2^31 elements or more", who);
+    return 1;
+}
+
+// ... and the launch: filters of type S into the packed form of the precision P
+template <typename S, class P>
+int launch_pack(const void* const* weights, int n_filters, void* packed, int O0, int M, int C, size_t elems, cspn_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CSPN_PRE(st), pack<S, typename P::T, P::CHANNEL_INNER><<<dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st>>>(
+        static_cast<const S*>(weights[0]), n_filters > 1 ? static_cast<const S*>(weights[1]) : nullptr, static_cast<typename P::T*>(packed), O0, M,
+        round_up(M, TM), C, round_up(C, KC), elems);
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+
+// The argument rules of a forward entry point behind its own rule for the dtype, and the arguments of the kernel with its grid.
+template <typename T>
+int fill_forward_args(const char* who, Args<T>& a, const void* x, const void* packed, const void* scale, const void* shift, int relu_channels,
+                      void* const* outs, const int* out_channels, int n_outs, int N, int C, int H, int W, int oh, int ow, int max_filters) {
+    if (N < 1 || C < 1 || H < 1 || W < 1) return fail("%s: bad shape (N=%d, C=%d, H=%d, W=%d)", who, N, C, H, W);
+    if (oh < 1 || ow < 1 || (long)oh > 2L * H || (long)ow > 2L * W)
+        return fail("%s: output %dx%d must lie in [1, 2H] x [1, 2W] = %ldx%ld", who, oh, ow, 2L * H, 2L * W);
+    if (!check_filters(who, out_channels, n_outs, a.O0, a.O1, max_filters)) return 0;
+    a.M = a.O0 + a.O1;
+    if (!packed_elems(a.M, C)) return fail("%s: bad size (%d output channels, C=%d)", who, a.M, C);
+    if ((double)N * C * H * W >= 2147483648.0 || (double)N * a.O0 * oh * ow >= 2147483648.0 || (double)N * a.O1 * oh * ow >= 2147483648.0)
+        return fail("%s: a tensor of 2^31 elements or more; split the batch", who);
+    if (!x || !packed || !outs) return fail("%s: null pointer", who);
+    for (int k = 0; k < n_outs; ++k)
+        if (!outs[k]) return fail("%s: null pointer (output %d)", who, k);
+    if (!aligned16(packed)) return fail("%s: packed must be 16-byte aligned", who);
+    if (!scale != !shift) return fail("%s: scale and shift come together", who);
+    if (relu_channels < 0 || relu_channels > a.M) return fail("%s: relu_channels %d outside [0, %d]", who, relu_channels, a.M);
+    a.x = static_cast<const T*>(x), a.wp = static_cast<const T*>(packed);
+    a.scale = static_cast<const float*>(scale), a.shift = static_cast<const float*>(shift);
+    a.y0 = static_cast<T*>(outs[0]), a.y1 = n_outs > 1 ? static_cast<T*>(outs[1]) : nullptr;
+    a.Mp = round_up(a.M, TM), a.relu = relu_channels;
+    a.N = N, a.C = C, a.Cp = round_up(C, KC), a.H = H, a.W = W, a.oh = oh, a.ow = ow;
+    a.mtiles = a.Mp / TM;
+    double blocks = 0;
+    for (int p = 0; p < 4; ++p) {
+        a.first[p] = (unsigned)blocks;
+        const double npix = (double)N * ((oh + 1 - (p >> 1)) / 2) * ((ow + 1 - (p & 1)) / 2);      // < 2^31: an output has fewer elements
+        blocks += (double)(((long)npix + TN - 1) / TN) * a.mtiles;
+        if (blocks >= 2147483648.0) return fail("%s: more than 2^31 tiles; split the batch", who);
+    }
+    a.first[4] = (unsigned)blocks;
+    return 1;
+}
+
+// ... and the launch in the precision P
+template <class P>
+int forward(const char* who, const void* x, const void* packed, const void* scale, const void* shift, int relu_channels, void* const* outs,
+            const int* out_channels, int n_outs, int N, int C, int H, int W, int oh, int ow, int max_filters, cspn_stream_t stream) {
+    Args<typename P::T> a;
+    if (!fill_forward_args(who, a, x, packed, scale, shift, relu_channels, outs, out_channels, n_outs, N, C, H, W, oh, ow, max_filters)) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CSPN_PRE(st), fwd<P><<<dim3(a.first[4]), dim3(THREADS), 0, st>>>(a);
+    HIP_OK(hipGetLastError());
+    return 1;
+}
+
+}  // namespace

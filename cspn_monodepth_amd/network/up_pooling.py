@@ -38,6 +38,8 @@ from .. import _lib
 from .._host import _dt, _p, _require_device, launch
 
 __all__ = ["up_pooling", "up_pooling_conv3x3", "up_pooling_conv5x5", "pack_upconv5x5", "UpconvPack", "MyBlock"]
+_UPCONV_KERNELS = {torch.float32: ("cspn_upconv_workspace_bytes", "cspn_upconv_pack", "cspn_upconv_forward", True, 4),      # by pack dtype: bytes, pack, forward,
+                   torch.float16: ("cspn_uphalf_packed_bytes", "cspn_uphalf_pack", "cspn_uphalf_forward", False, 2)}       # forward takes a dtype, element size
 
 
 def _forward(x, scale, oh, ow):
@@ -264,15 +266,15 @@ def pack_upconv5x5(weights, batchnorms=None, relu=(True, False), dtype=torch.flo
     dev = _require_device(*weights)
     out_channels, C = [w.shape[0] for w in weights], weights[0].shape[1]
     total = sum(out_channels)
-    half = dtype == torch.float16
-    nbytes = (_lib.lib().cspn_uphalf_packed_bytes if half else _lib.lib().cspn_upconv_workspace_bytes)(total, C)
+    bytes_fn, pack_fn, _, _, esize = _UPCONV_KERNELS[dtype]
+    nbytes = getattr(_lib.lib(), bytes_fn)(total, C)
     if not nbytes:
         raise ValueError("%s: the packed form of %d x %d channels has 2^31 elements or more" % (who, total, C))
     sources = list(weights)
     with torch.no_grad():
         wc = [w.detach().contiguous() for w in weights]
-        packed = torch.empty(nbytes // (2 if half else 4), dtype=dtype, device=dev)
-        launch(dev, "cspn_uphalf_pack" if half else "cspn_upconv_pack", _ptrs(wc), _channels(wc), len(wc), C, 5, 5, _dt(wc[0]), _p(packed))
+        packed = torch.empty(nbytes // esize, dtype=dtype, device=dev)
+        launch(dev, pack_fn, _ptrs(wc), _channels(wc), len(wc), C, 5, 5, _dt(wc[0]), _p(packed))
         scale = shift = None
         if batchnorms is not None:
             scales, shifts = [], []
@@ -368,10 +370,8 @@ def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=No
     outs = tuple(torch.empty((N, o, oheight, owidth), dtype=pack.dtype, device=dev) for o in out_channels)
     tail = (_p(pack.packed), _p(None if scale is None else scale.contiguous()), _p(None if shift is None else shift.contiguous()),
             relu_channels, _ptrs(outs), (ctypes.c_int * len(outs))(*out_channels), len(outs), N, C, H, W, oheight, owidth)
-    if pack.dtype == torch.float16:
-        launch(dev, "cspn_uphalf_forward", _p(xc), *tail)
-    else:
-        launch(dev, "cspn_upconv_forward", _p(xc), _lib.CSPN_F32, *tail)
+    _, _, forward_fn, takes_dtype, _ = _UPCONV_KERNELS[pack.dtype]
+    launch(dev, forward_fn, _p(xc), *((_dt(xc),) if takes_dtype else ()), *tail)
     return outs
 
 

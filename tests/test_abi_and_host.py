@@ -50,7 +50,7 @@ FAMILY_CONTRACT = {
     "visual": ("cspn_visual.h", "CSPN_VISUAL_ABI_VERSION", 1, ("cspn_visual.hip",), ("_visual_",),
                ("cspn_visual_abi_version", "cspn_visual_workspace_bytes", "cspn_visual_rows", "cspn_visual_features")),
 }
-BUILD_ONLY_HPP = ("pac_launch.hpp", "cspn_loss_units.hpp", "cspn_philox.hpp")
+BUILD_ONLY_HPP = ("pac_launch.hpp", "cspn_loss_units.hpp", "cspn_philox.hpp", "cspn_upconv_core.hpp")
 
 
 def _header_source(header):
@@ -134,7 +134,7 @@ def test_kernel_sources_carry_no_compile_time_switches():
     conditional = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b")
     switch = re.compile(r"^\s*#\s*define\s+CSPN_[A-Z0-9_]+\s+\S")
     paths = [os.path.join(_lib.CSRC, f) for f in _lib.SOURCES] + [p for p in _lib.BUILD_HEADERS if os.path.dirname(p) == _lib.CSRC]
-    assert len(paths) == len(_lib.SOURCES) + 5
+    assert len(paths) == len(_lib.SOURCES) + 6
     for path in paths:
         with open(path, encoding="utf-8") as fh:
             hits = [(no, ln.rstrip()) for no, ln in enumerate(fh, 1) if conditional.match(ln) or switch.match(ln)]

@@ -188,12 +188,12 @@ def test_switch_keeps_modules_and_state_dict(net):
         assert len(big) == 417
 
 
-def test_upconv_family_contract():
+def test_upconv_family_contract(monkeypatch):
     """Header, loader table and library agree on the family, in the terms tests/test_heads.py uses for `heads`; its files stay out of
     the digest that pins the recorded HBM traffic."""
     fam = _lib.family("upconv")
     names = ("cspn_upconv_abi_version", "cspn_upconv_workspace_bytes", "cspn_upconv_pack", "cspn_upconv_forward")
-    assert fam.header == os.path.join(ROOT, "include", "cspn_upconv.h") and fam.files == {"cspn_upconv.hip": False}
+    assert fam.header == os.path.join(ROOT, "include", "cspn_upconv.h") and fam.files == {"cspn_upconv.hip": False, "cspn_upconv_core.hpp": False}
     text = open(fam.header).read()
     assert re.search(r"^#define CSPN_UPCONV_ABI_VERSION 1$", text, flags=re.M)
     assert re.search(r"^#define CSPN_UPCONV_MAX_FILTERS 2$", text, flags=re.M) and _lib.UPCONV_MAX_FILTERS == 2
@@ -201,9 +201,18 @@ def test_upconv_family_contract():
     assert declared == sorted(fam.functions) == sorted(names)
     lib = _lib.lib()
     assert all(hasattr(lib, n) for n in names) and lib.cspn_upconv_abi_version() == fam.abi_version == 1
-    assert _lib.OPT_IN_FAMILIES == (_lib.family("heads"), fam) and fam not in _lib.FAMILIES and len(_lib.ALL_FAMILIES) == 11
+    assert _lib.OPT_IN_FAMILIES[:2] == (_lib.family("heads"), fam) and fam not in _lib.FAMILIES and len(_lib.ALL_FAMILIES) == 12
     assert "cspn_upconv.hip" in _lib.OPT_IN_SOURCES and "cspn_upconv.hip" not in _lib.SOURCES
     assert fam.header in _lib.BUILD_HEADERS and fam.header not in _lib.HEADERS
+    # the core both decoder-head families are built on is a header of an opt-in family: seen by the build's staleness hash (and so by
+    # the per-object one, which reads the same list), never by the digest behind profiles/
+    core = os.path.join(_lib.CSRC, "cspn_upconv_core.hpp")
+    assert core in _lib.BUILD_HEADERS and core not in _lib.HEADERS
+    with_core = _lib._source_digest(["x"])
+    monkeypatch.setattr(_lib, "BUILD_HEADERS", tuple(p for p in _lib.BUILD_HEADERS if p != core))
+    assert _lib._source_digest(["x"]) != with_core
+    monkeypatch.undo()
+    assert _lib._source_digest(["x"]) == with_core
     for other in _lib.ALL_FAMILIES:
         if other is not fam:
             assert not set(other.functions) & set(names) and not any("upconv" in n for n in other.functions)

@@ -208,20 +208,29 @@ def _families():
             "cspn_uphalf_packed_bytes": (cs, [ci, ci]),
             "cspn_uphalf_pack": [ptr(vp), ptr(ci), ci, ci, ci, ci, ci, vp, vp],
             "cspn_uphalf_forward": [vp, vp, vp, vp, ci, ptr(vp), ptr(ci), ci, ci, ci, ci, ci, ci, ci, vp]}),
+        family("uptail", "cspn_uptail.h", 1, {"cspn_uptail.hip": False}, {
+            "cspn_uptail_abi_version": None,
+            "cspn_uptail_packed_bytes": (cs, [ci, ci, ci, ci]),
+            "cspn_uptail_pack": [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp],
+            "cspn_uptail_forward": [vp, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp]}),
     )
 
 
-# The table has two parts.  FAMILIES: what a default call of the package can reach — the nine families the loader's tests spell
+# The table has three parts.  FAMILIES: what a default call of the package can reach — the nine families the loader's tests spell
 # out in literals, with SOURCES their translation units.  OPT_IN_FAMILIES: families behind a switch that is off by default (heads:
 # `fused_heads=True` of the models, network.up_pooling.up_pooling_conv3x3; upconv and uphalf: `fused_decoder`, up_pooling_conv5x5 on
 # fp32 and on half inputs); they are built, declared and version-checked with the others, and no file of theirs is part of code_digest().
-ALL_FAMILIES = _families()
+# LATER_FAMILIES: opt-in families added after those twelve, which the older tests count (uptail: `fused_tail`,
+# network.up_pooling.conv3x3_bn_act) — treated as the opt-in ones in every respect.
+EVERY_FAMILY = _families()
+ALL_FAMILIES = EVERY_FAMILY[:12]
 FAMILIES = ALL_FAMILIES[:9]
 OPT_IN_FAMILIES = ALL_FAMILIES[9:]
+LATER_FAMILIES = EVERY_FAMILY[12:]
 
 
 def family(name):
-    return next(f for f in ALL_FAMILIES if f.name == name)
+    return next(f for f in EVERY_FAMILY if f.name == name)
 
 
 def _files(suffix, benchmarked=None, families=FAMILIES):
@@ -230,10 +239,11 @@ def _files(suffix, benchmarked=None, families=FAMILIES):
 
 SOURCES = _files(".hip")                      # one TU each
 OPT_IN_SOURCES = _files(".hip", families=OPT_IN_FAMILIES)
+LATER_SOURCES = _files(".hip", families=LATER_FAMILIES)
 BENCH_UNRELATED = _files(".hip", False)       # kernels no bench.py workload launches
 HEADERS = tuple(os.path.join(CSRC, f) for f in _files(".hpp", True)) + tuple(f.header for f in FAMILIES if any(f.files.values()))
-BUILD_HEADERS = HEADERS + tuple(os.path.join(CSRC, f) for f in _files(".hpp", False, ALL_FAMILIES)) + \
-    tuple(f.header for f in ALL_FAMILIES if not any(f.files.values()))
+BUILD_HEADERS = HEADERS + tuple(os.path.join(CSRC, f) for f in _files(".hpp", False, EVERY_FAMILY)) + \
+    tuple(f.header for f in EVERY_FAMILY if not any(f.files.values()))
 EXPORTS = tuple(family("core").functions)      # every symbol include/cspn_hip.h declares
 
 
@@ -244,7 +254,7 @@ def _source_digest(flags, code_only=False):
     import hashlib
     import re
     h = hashlib.sha256(" ".join(flags).encode())
-    tus = [f for f in SOURCES if f not in BENCH_UNRELATED] if code_only else SOURCES + OPT_IN_SOURCES
+    tus = [f for f in SOURCES if f not in BENCH_UNRELATED] if code_only else SOURCES + OPT_IN_SOURCES + LATER_SOURCES
     for path in [os.path.join(CSRC, f) for f in tus] + list(HEADERS if code_only else BUILD_HEADERS):
         with open(path, "rb") as fh:
             data = fh.read()
@@ -265,7 +275,7 @@ def build(force=False, verbose=False):
     csrc/_build/*.o and linked into the in-tree .so (which travels with gpurun snapshots).  Staleness is decided by
     a content hash of the sources + flags stored next to the library (file times do not survive every copy)."""
     from concurrent.futures import ThreadPoolExecutor
-    srcs = [os.path.join(CSRC, f) for f in SOURCES + OPT_IN_SOURCES]
+    srcs = [os.path.join(CSRC, f) for f in SOURCES + OPT_IN_SOURCES + LATER_SOURCES]
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     # -fno-slp-vectorize: the SLP pass pairs the stencil FMAs into v_pk_fma_f32 and pays for it with ~50 v_mov
     # per step to build operand pairs; scalar v_fma_f32 measured 4 % faster (profiles/).  No fast-math: 0/0 = NaN.
@@ -318,7 +328,7 @@ _lock = threading.Lock()
 
 
 def _declare(lib):
-    for fam in ALL_FAMILIES:
+    for fam in EVERY_FAMILY:
         for name, (restype, argtypes) in fam.functions.items():
             fn = getattr(lib, name)
             if restype is not ctypes.c_int:           # ctypes' default
@@ -339,7 +349,7 @@ def lib():
                         "cspn_monodepth_amd: %s is missing — build it with `python -c 'import __graft_entry__ as g; "
                         "g.build()'` (hipcc --offload-arch=gfx950).  There is no CPU fallback." % SO_PATH)
                 _lib = _declare(ctypes.CDLL(SO_PATH))
-                for fam in ALL_FAMILIES:
+                for fam in EVERY_FAMILY:
                     sub = "" if fam.name == "core" else fam.name      # cspn_abi_version, cspn_<family>_abi_version
                     if getattr(_lib, "cspn_%sabi_version" % (sub and sub + "_"))() != fam.abi_version:
                         raise RuntimeError("cspn_monodepth_amd: %sABI version mismatch" % (sub and sub + " "))

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from ..post_process import CSPN_new as post_process
-from .up_pooling import FusedHead, select_fused_decoder, up_pooling, up_pooling_conv3x3
+from .up_pooling import FusedHead, select_fused_decoder, select_fused_tail, up_pooling, up_pooling_conv3x3
 
 __all__ = ["ResNet", "resnet50", "resnet18", "Bottleneck", "BasicBlock", "Gudi_UpProj_Block", "Gudi_UpProj_Block_Cat",
            "Simple_Gudi_UpConv_Block_Last_Layer", "UpProj_Block", "DECODER_SIZES_NYU"]
@@ -105,9 +105,8 @@ class Gudi_UpProj_Block(_UpBlock):                               # unet_cspn_nyu
         self.relu = nn.ReLU(inplace=True)
 
     def forward(self, x):
-        if self._fuse_head(x):
-            out, shortcut = self._head(x)
-            return self.relu(self.bn2(self.conv2(out)) + shortcut)
+        if self._fuse_head(x) or self._fuse_tail():
+            return self._tail(*(self._head(x) if self._fuse_head(x) else self._stock_head(x)))
         x = self._up_pooling(x)
         out = self.bn2(self.conv2(self.relu(self.bn1(self.conv1(x)))))
         return self.relu(out + self.sc_bn1(self.sc_conv1(x)))
@@ -129,10 +128,8 @@ class Gudi_UpProj_Block_Cat(_UpBlock):                           # unet_cspn_nyu
         self.relu = nn.ReLU(inplace=True)
 
     def forward(self, x, side_input):
-        if self._fuse_head(x):
-            out, shortcut = self._head(x)
-            out = torch.cat((out, side_input), 1)
-            return self.relu(self.bn2(self.conv2(self.relu(self.bn1_1(self.conv1_1(out))))) + shortcut)
+        if self._fuse_head(x) or self._fuse_tail():
+            return self._tail(*(self._head(x) if self._fuse_head(x) else self._stock_head(x)), side_input)
         x = self._up_pooling(x)
         out = torch.cat((self.relu(self.bn1(self.conv1(x))), side_input), 1)
         out = self.bn2(self.conv2(self.relu(self.bn1_1(self.conv1_1(out)))))
@@ -173,11 +170,18 @@ class ResNet(nn.Module):
     "gud_up_proj_layer4" — in eval mode with grad mode off a named block runs its head (un-pool, conv1 -> bn1 -> ReLU, sc_conv1 ->
     sc_bn1) as one ``up_pooling_conv5x5`` call and the rest of itself on stock ops; otherwise exactly the default code.  True selects
     the blocks where that was measured to be faster (up_pooling.FUSED_DECODER_DEFAULT; for a half input — autocast, ``half()`` — FUSED_DECODER_HALF_DEFAULT, on the fp16 kernel of
-    include/cspn_uphalf.h; any other dtype runs the default code).  The state_dict is the same either way."""
+    include/cspn_uphalf.h; any other dtype runs the default code).  The state_dict is the same either way.
+    fused_tail (off by default; independent of the other two): True, or block names as for fused_decoder.  Under the same conditions
+    a named block runs the rest of itself — conv1_1 -> bn1_1 -> ReLU over (out, side_input) without the ``cat``, then conv2 -> bn2,
+    + shortcut, ReLU — as one ``conv3x3_bn_act`` call per convolution (include/cspn_uptail.h), whether its head is fused or not.  True
+    selects up_pooling.FUSED_TAIL_DEFAULT (half inputs: FUSED_TAIL_HALF_DEFAULT), the blocks where that was measured to be faster —
+    lists that may be empty; names select those blocks in both precisions.
+    The three switches together: fused_heads covers gud_up_proj_layer5 / 6, fused_decoder the head and fused_tail the tail of
+    gud_up_proj_layer1 .. 4; each is forward-only, changes no module, parameter or state_dict key, and none changes what another does."""
 
     def __init__(self, block, layers, up_proj_block=UpProj_Block, decoder_sizes=DECODER_SIZES_NYU, prop_time=24,
                  prop_kernel=3, reference_state_dict=True, cspn_plan=None, affinity_channels=8, fused_heads=False,
-                 fused_decoder=False):
+                 fused_decoder=False, fused_tail=False):
         super(ResNet, self).__init__()
         self.inplanes = 64
         e = block.expansion
@@ -212,6 +216,7 @@ class ResNet(nn.Module):
         self.return_cspn_io = False
         self.fused_heads = bool(fused_heads)
         self.fused_decoder = select_fused_decoder(self, fused_decoder)
+        self.fused_tail = select_fused_tail(self, fused_tail)
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None

@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from ..post_process import CSPN_ours as post_process
 from .unet_cspn_nyu import DECODER_SIZES_NYU, BasicBlock, Bottleneck, _conv
-from .up_pooling import MyBlock, select_fused_decoder, up_pooling_conv3x3
+from .up_pooling import MyBlock, select_fused_decoder, select_fused_tail, up_pooling_conv3x3
 
 __all__ = ["ResNet", "resnet50", "resnet18", "Bottleneck", "BasicBlock", "UpProj_Block", "Gudi_UpProj_Block",
            "Gudi_UpProj_Block_Cat", "Simple_Gudi_UpConv_Block", "Simple_Gudi_UpConv_Block_Last_Layer", "DECODER_SIZES_NYU", "decoder_sizes_for"]
@@ -47,9 +47,8 @@ class Gudi_UpProj_Block(MyBlock):                              # unet_ours.py:20
         self.relu = nn.ReLU(inplace=False)
 
     def forward(self, x):
-        if self._fuse_head(x):
-            out, shortcut = self._head(x)
-            return self.relu(self.bn2(self.conv2(out)) + shortcut)
+        if self._fuse_head(x) or self._fuse_tail():
+            return self._tail(*(self._head(x) if self._fuse_head(x) else self._stock_head(x)))
         x = self._up_pooling(x, 2)
         out = self.bn2(self.conv2(self.relu(self.bn1(self.conv1(x)))))
         return self.relu(out + self.sc_bn1(self.sc_conv1(x)))
@@ -92,10 +91,8 @@ class Gudi_UpProj_Block_Cat(MyBlock):                            # unet_ours.py:
         self.relu = nn.ReLU(inplace=False)
 
     def forward(self, x, side_input):
-        if self._fuse_head(x):
-            out, shortcut = self._head(x)
-            out = torch.cat((out, side_input), 1)
-            return self.relu(self.bn2(self.conv2(self.relu(self.bn1_1(self.conv1_1(out))))) + shortcut)
+        if self._fuse_head(x) or self._fuse_tail():
+            return self._tail(*(self._head(x) if self._fuse_head(x) else self._stock_head(x)), side_input)
         x = self._up_pooling(x, 2)
         out = torch.cat((self.relu(self.bn1(self.conv1(x))), side_input), 1)
         out = self.bn2(self.conv2(self.relu(self.bn1_1(self.conv1_1(out)))))
@@ -118,10 +115,17 @@ class ResNet(nn.Module):
     with one ``up_pooling_conv5x5`` call on the compact map and runs the rest of itself on stock ops; in train mode or with grad mode
     on it runs exactly the default code.  True selects the blocks where that was measured to be faster
     (up_pooling.FUSED_DECODER_DEFAULT; for a half input — autocast, ``half()`` — FUSED_DECODER_HALF_DEFAULT, on the fp16 kernel of
-    include/cspn_uphalf.h; any other dtype runs the default code).  Modules, parameters and the state_dict are the same either way."""
+    include/cspn_uphalf.h; any other dtype runs the default code).  Modules, parameters and the state_dict are the same either way.
+    fused_tail (off by default; independent of the other two): True, or block names as for fused_decoder.  Under the same conditions
+    a named block runs the rest of itself — conv1_1 -> bn1_1 -> ReLU over (out, side_input) without the ``cat``, then conv2 -> bn2,
+    + shortcut, ReLU — as one ``conv3x3_bn_act`` call per convolution (include/cspn_uptail.h), whether its head is fused or not.  True
+    selects up_pooling.FUSED_TAIL_DEFAULT (half inputs: FUSED_TAIL_HALF_DEFAULT), the blocks where that was measured to be faster —
+    lists that may be empty; names select those blocks in both precisions.
+    The three switches together: fused_heads covers gud_up_proj_layer5 / 6, fused_decoder the head and fused_tail the tail of
+    gud_up_proj_layer1 .. 4; each is forward-only, changes no module, parameter or state_dict key, and none changes what another does."""
 
     def __init__(self, block, layers, up_proj_block=None, decoder_sizes=DECODER_SIZES_NYU, prop_time=24, cspn_plan=None,
-                 fused_heads=False, fused_decoder=False):
+                 fused_heads=False, fused_decoder=False, fused_tail=False):
         super(ResNet, self).__init__()
         self.inplanes = 64
         e = block.expansion
@@ -147,6 +151,7 @@ class ResNet(nn.Module):
         self.return_cspn_io = False
         self.fused_heads = bool(fused_heads)
         self.fused_decoder = select_fused_decoder(self, fused_decoder)
+        self.fused_tail = select_fused_tail(self, fused_tail)
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None

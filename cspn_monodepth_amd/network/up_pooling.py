@@ -27,6 +27,10 @@ norms in eval mode and the ReLU of the first, as one implicit GEMM per output ph
 (include/cspn_upconv.h).  Forward only and opt-in — ``fused_decoder`` of the models; the filters are reordered once by
 ``pack_upconv5x5``.  A half ``x`` (``torch.autocast``, ``model.half()``) takes a pack of ``dtype=torch.float16`` and runs on the fp16
 matrix cores with fp32 accumulation and one rounding of the result (include/cspn_uphalf.h).
+
+``conv3x3_bn_act`` is the rest of such a block — the 3x3 convolutions ``conv1_1`` (over the head's output and the encoder skip, without
+the ``cat``) and ``conv2``, their eval-mode batch norms, the shortcut add and the ReLUs — one call per convolution on the same matrix
+cores (include/cspn_uptail.h).  Forward only and opt-in — ``fused_tail`` of the models; ``pack_conv3x3`` makes its pack.
 """
 import ctypes
 
@@ -37,9 +41,11 @@ from torch.autograd.function import Function, once_differentiable
 from .. import _lib
 from .._host import _dt, _p, _require_device, launch
 
-__all__ = ["up_pooling", "up_pooling_conv3x3", "up_pooling_conv5x5", "pack_upconv5x5", "UpconvPack", "MyBlock"]
+__all__ = ["up_pooling", "up_pooling_conv3x3", "up_pooling_conv5x5", "pack_upconv5x5", "UpconvPack", "pack_conv3x3", "conv3x3_bn_act", "MyBlock"]
 _UPCONV_KERNELS = {torch.float32: ("cspn_upconv_workspace_bytes", "cspn_upconv_pack", "cspn_upconv_forward", True, 4),      # by pack dtype: bytes, pack, forward,
                    torch.float16: ("cspn_uphalf_packed_bytes", "cspn_uphalf_pack", "cspn_uphalf_forward", False, 2)}       # forward takes a dtype, element size
+
+_DT = {torch.float32: _lib.CSPN_F32, torch.float16: _lib.CSPN_F16}
 
 
 def _forward(x, scale, oh, ow):
@@ -196,10 +202,12 @@ class UpconvPack(object):
     """What ``up_pooling_conv5x5`` runs on: the filters of one block head in the order the kernel walks them (``packed``), the folded
     batch norms (``scale``, ``shift``: fp32 [sum of out_channels], or None), how many leading flat channels get a ReLU, the ``dtype``
     of the packed filters and so of the ``x`` it takes and the outputs it gives (fp32: include/cspn_upconv.h, fp16: cspn_uphalf.h), and the
-    ``_version`` and ``data_ptr`` of every tensor it was made from — ``stale()`` says whether one of them has changed since."""
+    ``_version`` and ``data_ptr`` of every tensor it was made from — ``stale()`` says whether one of them has changed since.  A pack of
+    ``pack_conv3x3`` for ``conv3x3_bn_act`` is the same thing with one filter and a ``split``: how many of its ``in_channels`` come from
+    the first of two maps (None: one map)."""
 
-    def __init__(self, packed, scale, shift, out_channels, in_channels, relu_channels, sources, dtype=torch.float32):
-        self.packed, self.scale, self.shift, self.dtype = packed, scale, shift, dtype
+    def __init__(self, packed, scale, shift, out_channels, in_channels, relu_channels, sources, dtype=torch.float32, split=None):
+        self.packed, self.scale, self.shift, self.dtype, self.split = packed, scale, shift, dtype, split
         self.out_channels, self.in_channels, self.relu_channels = tuple(out_channels), int(in_channels), int(relu_channels)
         self.sources = tuple(sources)
         self._seen = tuple((t._version, t.data_ptr()) for t in self.sources)
@@ -237,6 +245,17 @@ def _check_filters(who, weights, dtype=torch.float32):
 
 def _bn_sources(bn):
     return [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
+
+
+def _fold(bn):
+    """(scale, shift) of a batch norm as eval mode applies it, in fp32 by device tensor ops; call under no_grad."""
+    s = 1.0 / torch.sqrt(bn.running_var.float() + bn.eps)
+    if bn.weight is not None:
+        s = bn.weight.detach().float() * s
+    b = -bn.running_mean.float() * s
+    if bn.bias is not None:
+        b = bn.bias.detach().float() + b
+    return s, b
 
 
 def pack_upconv5x5(weights, batchnorms=None, relu=(True, False), dtype=torch.float32):
@@ -281,12 +300,7 @@ def pack_upconv5x5(weights, batchnorms=None, relu=(True, False), dtype=torch.flo
             for w, bn in zip(weights, batchnorms):
                 _require_device(w, *_bn_sources(bn))
                 sources += _bn_sources(bn)
-                s = 1.0 / torch.sqrt(bn.running_var.float() + bn.eps)
-                if bn.weight is not None:
-                    s = bn.weight.detach().float() * s
-                b = -bn.running_mean.float() * s
-                if bn.bias is not None:
-                    b = bn.bias.detach().float() + b
+                s, b = _fold(bn)
                 scales.append(s)
                 shifts.append(b)
             scale, shift = torch.cat(scales).contiguous(), torch.cat(shifts).contiguous()
@@ -375,6 +389,98 @@ def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=No
     return outs
 
 
+def pack_conv3x3(weight, batchnorm=None, split=None, dtype=torch.float32):
+    """The pack ``conv3x3_bn_act`` runs on: ``weight`` — one bias-free [O, C, 3, 3] filter on a ROCm device (``conv1_1.weight``,
+    ``conv2.weight``) — reordered for the kernel, and ``batchnorm`` — None or its ``nn.BatchNorm2d`` — folded in fp32 by device tensor
+    ops exactly as ``pack_upconv5x5`` folds one.  ``split``: Ca, when the convolution reads the concatenation of a [N, Ca, H, W] and a
+    [N, C - Ca, H, W] map (``conv3x3_bn_act`` then takes the second as ``side``); the default is all of C, one map.  ``dtype``: fp32, or
+    fp16 for the half kernel — fp32 weights are rounded once, fp16 weights (``model.half()``) go into a fp16 pack alone.  An
+    ``UpconvPack``: ``stale()`` and ``made_from()`` as there."""
+    who = "pack_conv3x3"
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError("%s: a pack is fp32 or fp16, got dtype=%s" % (who, dtype))
+    if not torch.is_tensor(weight) or weight.dim() != 4 or weight.shape[0] < 1 or weight.shape[1] < 1 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError("%s: weight must be [O,C,3,3], got %s" % (who, tuple(weight.shape) if torch.is_tensor(weight) else type(weight)))
+    if weight.dtype != torch.float32 and not (dtype == torch.float16 and weight.dtype == torch.float16):
+        raise ValueError("%s: fp32 only (a fp16 weight goes into a pack of dtype=torch.float16 alone), got %s" % (who, weight.dtype))
+    O, C = weight.shape[:2]
+    if split is not None and not 1 <= int(split) <= C:
+        raise ValueError("%s: split %s outside [1, %d], the weight's input channels" % (who, split, C))
+    Ca = C if split is None else int(split)
+    if batchnorm is not None and (batchnorm.num_features != O or batchnorm.running_mean is None):
+        raise ValueError("%s: batchnorm must be over %d channels with running statistics" % (who, O))
+    if weight.numel() >= 2 ** 31:
+        raise ValueError("%s: weight has 2^31 elements or more" % who)
+    sources = [weight] + ([] if batchnorm is None else _bn_sources(batchnorm))
+    dev = _require_device(*sources)
+    nbytes = _lib.lib().cspn_uptail_packed_bytes(O, Ca, C - Ca, _DT[dtype])
+    if not nbytes:
+        raise ValueError("%s: the packed form of %d x %d channels has 2^31 elements or more" % (who, O, C))
+    with torch.no_grad():
+        wc = weight.detach().contiguous()
+        packed = torch.empty(nbytes // (4 if dtype == torch.float32 else 2), dtype=dtype, device=dev)
+        launch(dev, "cspn_uptail_pack", _p(wc), O, Ca, C - Ca, 3, 3, _dt(wc), _DT[dtype], _p(packed))
+        scale, shift = (None, None) if batchnorm is None else (t.contiguous() for t in _fold(batchnorm))
+    return UpconvPack(packed, scale, shift, (O,), C, 0, sources, dtype, Ca if Ca < C else None)
+
+
+def conv3x3_bn_act(a, pack, side=None, residual=None, relu=True):
+    """The 3x3 tail step of a decoder block in one kernel (include/cspn_uptail.h):
+
+        out [N,O,H,W] = act( conv2d(cat(a, side), w, padding=1) * scale + shift  [+ residual] )
+
+    for the filter, scale and shift of ``pack`` (``pack_conv3x3``); ``cat`` is never formed — ``a`` [N,Ca,H,W] and ``side``
+    [N,C - Ca,H,W] (a pack made with ``split=Ca``; None otherwise) are read where they are.  ``residual``: [N,O,H,W] or None.
+    ``relu``: whether act is the ReLU (NaN stays NaN).  ``conv1_1`` of ``Gudi_UpProj_Block_Cat`` is ``conv3x3_bn_act(out, pack(conv1_1,
+    bn1_1, split), side_input)``, ``conv2`` of every block ``conv3x3_bn_act(out, pack(conv2, bn2), residual=shortcut)``.
+
+    Everything is of the pack's dtype, the result too.  fp32: exact products, one fused multiply-add chain over (tap, channel: a before
+    side) per output, then fmaf(acc, scale, shift), the residual added with a rounding of its own, the ReLU — the roundings of the
+    stock eval path.  fp16: fp16 products accumulated in fp32, the whole epilogue in fp32, ONE rounding to fp16; the stock half path
+    rounds after the convolution, after the batch norm and after the add.  A frame's bits do not depend on the batch, runs repeat, and
+    the call can be captured in a graph.  Non-contiguous inputs are made contiguous; every tensor stays below 2^31 elements.
+
+    Forward only.  With grad mode on and an input or a source of the pack requiring a gradient it raises: training runs the stock
+    block (``cat``, the convolutions and batch norms, as the models do by default)."""
+    who = "conv3x3_bn_act"
+    if not isinstance(pack, UpconvPack) or len(pack.out_channels) != 1:
+        raise ValueError("%s: pack must come from pack_conv3x3" % who)
+    if a.dim() != 4:
+        raise ValueError("%s: a must be [N,C,H,W], got %s" % (who, tuple(a.shape)))
+    N, Ca, H, W = a.shape
+    O, C = pack.out_channels[0], pack.in_channels
+    if side is None and pack.split is not None:
+        raise ValueError("%s: the pack was made with split=%d and needs a side of %d channels" % (who, pack.split, C - pack.split))
+    if side is not None and pack.split is None:
+        raise ValueError("%s: side given, but the pack was made without a split" % who)
+    Cb = 0 if side is None else C - pack.split
+    for name, t, want in (("a", a, (N, C - Cb, H, W)), ("side", side, (N, Cb, H, W)), ("residual", residual, (N, O, H, W))):
+        if t is None:
+            continue
+        if t.dtype != pack.dtype:
+            raise ValueError("%s: %s is %s, the pack was made for %s" % (who, name, t.dtype, pack.dtype))
+        if t.dim() != 4 or t.shape[1] != want[1]:
+            raise ValueError("%s: %s has %s channels, the pack takes %d there" % (who, name, t.shape[1] if t.dim() == 4 else "no", want[1]))
+        if tuple(t.shape) != want:
+            raise ValueError("%s: %s must be %s, got %s" % (who, name, want, tuple(t.shape)))
+        if t.numel() >= 2 ** 31:
+            raise ValueError("%s: %s has 2^31 elements or more; split the batch" % (who, name))
+    if N < 1 or H < 1 or W < 1:
+        raise ValueError("%s: empty input %s" % (who, tuple(a.shape)))
+    if N * O * H * W >= 2 ** 31:
+        raise ValueError("%s: the output has 2^31 elements or more; split the batch" % who)
+    inputs = [t for t in (a, side, residual) if t is not None]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in inputs + list(pack.sources)):
+        raise RuntimeError("%s is forward-only: with grad mode on, run the stock block (cat, the 3x3 convolutions and batch norms, the "
+                           "models' default and their training path), or call it under torch.no_grad()" % who)
+    dev = _require_device(*inputs, pack.scale, pack.shift, *pack.sources)
+    ac, sc, rc = (None if t is None else t.contiguous() for t in (a, side, residual))
+    out = torch.empty((N, O, H, W), dtype=pack.dtype, device=dev)
+    launch(dev, "cspn_uptail_forward", _p(ac), _p(sc), _p(pack.packed), _p(pack.scale), _p(pack.shift), _p(rc), int(bool(relu)), _p(out),
+           _DT[pack.dtype], N, Ca, Cb, O, H, W)
+    return out
+
+
 DECODER_BLOCKS = ("gud_up_proj_layer1", "gud_up_proj_layer2", "gud_up_proj_layer3", "gud_up_proj_layer4")
 # What `fused_decoder=True` selects: the blocks at which tools/upconv_bench.py measured the fused head ahead of the stock one by
 # more than the spread of the two measurements — its 90th percentile below the stock 10th, warm and cache-cold
@@ -386,25 +492,46 @@ FUSED_DECODER_DEFAULT = ("gud_up_proj_layer1", "gud_up_proj_layer2", "gud_up_pro
 FUSED_DECODER_HALF_DEFAULT = ("gud_up_proj_layer1", "gud_up_proj_layer2", "gud_up_proj_layer3", "gud_up_proj_layer4")
 
 
+# What `fused_tail=True` selects, by the same rule from tools/uptail_bench.py against the stock tail (cat, MIOpen 3x3 convolutions,
+# eval batch norms, add, ReLUs) measured in the same process: the fused tail's 90th percentile below the stock 10th, warm and
+# cache-cold (profiles/r21_uptail_bench.json, RESULTS.md row 36).  fp32: none — the fused tail was 4 to 67 % SLOWER than the stock tail
+# at every stage (11.2 against 9.6 ms per forward), so True selects nothing for fp32 inputs; names still force the path.  fp16: layers 2
+# and 3 (1.7 and 1.9 times); at layers 1 and 4 the two paths were within 4 % of each other.
+FUSED_TAIL_DEFAULT = ()
+FUSED_TAIL_HALF_DEFAULT = ("gud_up_proj_layer2", "gud_up_proj_layer3")
+
+
+def _select(model, switch, value, default, half_default, attr):
+    """One switch of the models over DECODER_BLOCKS: False / None, True (`default`; for half inputs `half_default`) or a collection of
+    block names (for inputs of either precision).  Marks the blocks (`attr`, `attr`_half) and returns the fp32 names in decoder order."""
+    if value is True:
+        names = default
+    elif not value:
+        names = ()
+    elif isinstance(value, str):
+        names = (value,)
+    else:
+        names = tuple(value)
+    unknown = [n for n in names if n not in DECODER_BLOCKS]
+    if unknown:
+        raise ValueError("%s: %s not among %s" % (switch, unknown, list(DECODER_BLOCKS)))
+    for n in DECODER_BLOCKS:
+        setattr(getattr(model, n), attr, n in names)
+        setattr(getattr(model, n), attr + "_half", n in (half_default if value is True else names))
+    return tuple(n for n in DECODER_BLOCKS if n in names)
+
+
 def select_fused_decoder(model, fused_decoder):
     """The `fused_decoder` switch of the models: False / None, True (FUSED_DECODER_DEFAULT; for half inputs
     FUSED_DECODER_HALF_DEFAULT) or a collection of block names out of DECODER_BLOCKS (for inputs of either precision).  Marks the named
     blocks and returns their names in decoder order (what the model keeps as `fused_decoder`)."""
-    if fused_decoder is True:
-        names = FUSED_DECODER_DEFAULT
-    elif not fused_decoder:
-        names = ()
-    elif isinstance(fused_decoder, str):
-        names = (fused_decoder,)
-    else:
-        names = tuple(fused_decoder)
-    unknown = [n for n in names if n not in DECODER_BLOCKS]
-    if unknown:
-        raise ValueError("fused_decoder: %s not among %s" % (unknown, list(DECODER_BLOCKS)))
-    for n in DECODER_BLOCKS:
-        getattr(model, n).fused_head = n in names
-        getattr(model, n).fused_head_half = n in (FUSED_DECODER_HALF_DEFAULT if fused_decoder is True else names)
-    return tuple(n for n in DECODER_BLOCKS if n in names)
+    return _select(model, "fused_decoder", fused_decoder, FUSED_DECODER_DEFAULT, FUSED_DECODER_HALF_DEFAULT, "fused_head")
+
+
+def select_fused_tail(model, fused_tail):
+    """The `fused_tail` switch of the models, as `select_fused_decoder`: True selects FUSED_TAIL_DEFAULT (half inputs:
+    FUSED_TAIL_HALF_DEFAULT), names select those blocks for both precisions.  What the model keeps as `fused_tail`."""
+    return _select(model, "fused_tail", fused_tail, FUSED_TAIL_DEFAULT, FUSED_TAIL_HALF_DEFAULT, "fused_tail")
 
 
 class FusedHead(object):
@@ -442,8 +569,52 @@ class FusedHead(object):
         outs = up_pooling_conv5x5(x, pack, self.oheight, self.owidth)
         return outs[0], (outs[1] if len(outs) > 1 else None)
 
+    # The tail of the block — conv1_1 -> bn1_1 -> ReLU over (out, side_input) where the block has them, then conv2 -> bn2, + shortcut,
+    # ReLU — as one ``conv3x3_bn_act`` call per convolution when the block is marked (`fused_tail`, set by the model's `fused_tail`),
+    # under the conditions of the head and whether or not the head of the same block is fused.  Its packs are kept as the head's is.
+    fused_tail = False
+    fused_tail_half = None               # None: as fused_tail
+    _tail_packs = None
+
+    def _fuse_tail(self, *operands):
+        """Does this call run the fused tail?  ``operands``: the tensors the tail reads (out, shortcut, side_input) — all fp32 goes
+        by `fused_tail`, all fp16 by `fused_tail_half`, anything else runs the stock lines.  Without operands: could any call?"""
+        if self.training or torch.is_grad_enabled():
+            return False
+        half = self.fused_tail if self.fused_tail_half is None else self.fused_tail_half
+        if not operands:
+            return self.fused_tail or half
+        dtype = operands[0].dtype
+        if any(t.dtype != dtype for t in operands):
+            return False
+        return self.fused_tail if dtype == torch.float32 else half if dtype == torch.float16 else False
+
+    def _stock_head(self, x):
+        """What `_head` returns, on stock ops."""
+        x = self._up_pooling(x, 2)
+        return self.relu(self.bn1(self.conv1(x))), (self.sc_bn1(self.sc_conv1(x)) if hasattr(self, "sc_conv1") else None)
+
+    def _tail_pack(self, conv, bn, dtype, split=None):
+        """The pack of the convolution named `conv` and the batch norm named `bn`, made or made again as the head's."""
+        packs = self._tail_packs = self._tail_packs or {}
+        pack, weight, bn = packs.get(conv), getattr(self, conv).weight, getattr(self, bn)
+        if pack is None or pack.dtype != dtype or pack.stale() or not pack.made_from([weight] + _bn_sources(bn)):
+            pack = packs[conv] = pack_conv3x3(weight, bn, split, dtype)
+        return pack
+
+    def _tail(self, out, shortcut, side_input=None):
+        """relu(bn2(conv2(out')) + shortcut), out' = relu(bn1_1(conv1_1(cat(out, side_input)))) with a side_input and out without."""
+        operands = (out, shortcut) if side_input is None else (out, shortcut, side_input)
+        if self._fuse_tail(*operands):
+            if side_input is not None:
+                out = conv3x3_bn_act(out, self._tail_pack("conv1_1", "bn1_1", out.dtype, out.shape[1]), side_input)
+            return conv3x3_bn_act(out, self._tail_pack("conv2", "bn2", out.dtype), residual=shortcut)
+        if side_input is not None:
+            out = self.relu(self.bn1_1(self.conv1_1(torch.cat((out, side_input), 1))))
+        return self.relu(self.bn2(self.conv2(out)) + shortcut)
+
     def train(self, mode=True):
-        self._upconv_pack = None
+        self._upconv_pack = self._tail_packs = None
         return super(FusedHead, self).train(mode)
 
 

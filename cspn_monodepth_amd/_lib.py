@@ -84,12 +84,13 @@ class cspn_visual_rows(ctypes.Structure):       # cspn_visual_rows_t (include/cs
                 ("d_max", ctypes.c_float)]
 
 
-Family = collections.namedtuple("Family", "name header abi_version files functions")
+Family = collections.namedtuple("Family", "name header abi_version files functions opt_in")
 
 
 def _families():
     """The one list of what the library is made of: everything below that names a file or a function reads it.  A family is a
-    header under include/, the ABI version of it this host code was written against, its files under csrc/ and its functions.
+    header under include/, the ABI version of it this host code was written against, its files under csrc/, its functions and
+    whether it is opt-in.
     A file marked True is run by a bench.py workload and so part of code_digest(), as is the header of a family with such a file;
     the others are part of the build's staleness hash only (a digest that moved would mark the HBM traffic recorded under
     profiles/ as stale, bench.py `traffic_stale`).  A function is name -> argtypes (None: left unset) where it returns int, and
@@ -99,9 +100,9 @@ def _families():
     ll, ull, ptr = ctypes.c_longlong, ctypes.c_ulonglong, ctypes.POINTER
     plan, rplan, geom = ptr(cspn_plan), ptr(cspn_resident_plan), ptr(cspn_conv_geometry)
 
-    def family(name, header, abi_version, files, functions):
+    def family(name, header, abi_version, files, functions, opt_in=False):
         return Family(name, os.path.join(INCLUDE, header), abi_version, files,
-                      {n: sig if isinstance(sig, tuple) else (ci, sig) for n, sig in functions.items()})
+                      {n: sig if isinstance(sig, tuple) else (ci, sig) for n, sig in functions.items()}, opt_in)
 
     return (
         family("core", "cspn_hip.h", ABI_VERSION, {
@@ -197,40 +198,35 @@ def _families():
             "cspn_heads_workspace_bytes": (cs, [ci, ci, ci, ci, ci, ci, ci, ci]),
             "cspn_heads_forward": [vp, ptr(vp), ptr(vp), ptr(ci), ci, vp, ci, ci, ci, ci, ci, ci, vp],
             "cspn_heads_backward_input": [ptr(vp), ptr(vp), ptr(ci), ci, vp, vp, ci, ci, ci, ci, ci, ci, vp],
-            "cspn_heads_backward_weights": [vp, ptr(vp), ptr(vp), ptr(ci), ci, vp, ci, ci, ci, ci, ci, ci, vp]}),
+            "cspn_heads_backward_weights": [vp, ptr(vp), ptr(vp), ptr(ci), ci, vp, ci, ci, ci, ci, ci, ci, vp]}, opt_in=True),
         family("upconv", "cspn_upconv.h", 1, {"cspn_upconv.hip": False, "cspn_upconv_core.hpp": False}, {
             "cspn_upconv_abi_version": None,
             "cspn_upconv_workspace_bytes": (cs, [ci, ci]),
             "cspn_upconv_pack": [ptr(vp), ptr(ci), ci, ci, ci, ci, ci, vp, vp],
-            "cspn_upconv_forward": [vp, ci, vp, vp, vp, ci, ptr(vp), ptr(ci), ci, ci, ci, ci, ci, ci, ci, vp]}),
+            "cspn_upconv_forward": [vp, ci, vp, vp, vp, ci, ptr(vp), ptr(ci), ci, ci, ci, ci, ci, ci, ci, vp]}, opt_in=True),
         family("uphalf", "cspn_uphalf.h", 1, {"cspn_uphalf.hip": False}, {
             "cspn_uphalf_abi_version": None,
             "cspn_uphalf_packed_bytes": (cs, [ci, ci]),
             "cspn_uphalf_pack": [ptr(vp), ptr(ci), ci, ci, ci, ci, ci, vp, vp],
-            "cspn_uphalf_forward": [vp, vp, vp, vp, ci, ptr(vp), ptr(ci), ci, ci, ci, ci, ci, ci, ci, vp]}),
+            "cspn_uphalf_forward": [vp, vp, vp, vp, ci, ptr(vp), ptr(ci), ci, ci, ci, ci, ci, ci, ci, vp]}, opt_in=True),
         family("uptail", "cspn_uptail.h", 1, {"cspn_uptail.hip": False}, {
             "cspn_uptail_abi_version": None,
             "cspn_uptail_packed_bytes": (cs, [ci, ci, ci, ci]),
             "cspn_uptail_pack": [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp],
-            "cspn_uptail_forward": [vp, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp]}),
+            "cspn_uptail_forward": [vp, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp]}, opt_in=True),
     )
 
 
-# The table has three parts.  FAMILIES: what a default call of the package can reach — the nine families the loader's tests spell
-# out in literals, with SOURCES their translation units.  OPT_IN_FAMILIES: families behind a switch that is off by default (heads:
-# `fused_heads=True` of the models, network.up_pooling.up_pooling_conv3x3; upconv and uphalf: `fused_decoder`, up_pooling_conv5x5 on
-# fp32 and on half inputs); they are built, declared and version-checked with the others, and no file of theirs is part of code_digest().
-# LATER_FAMILIES: opt-in families added after those twelve, which the older tests count (uptail: `fused_tail`,
-# network.up_pooling.conv3x3_bn_act) — treated as the opt-in ones in every respect.
-EVERY_FAMILY = _families()
-ALL_FAMILIES = EVERY_FAMILY[:12]
-FAMILIES = ALL_FAMILIES[:9]
-OPT_IN_FAMILIES = ALL_FAMILIES[9:]
-LATER_FAMILIES = EVERY_FAMILY[12:]
+# A family with `opt_in` set sits behind a switch of the models that is off by default (`fused_heads`, `fused_decoder`, `fused_tail`,
+# network/up_pooling.py); the others are what a default call of the package can reach.  All are built, declared and version-checked
+# alike, and no file of an opt-in family is part of code_digest().
+ALL_FAMILIES = _families()
+FAMILIES = tuple(f for f in ALL_FAMILIES if not f.opt_in)
+OPT_IN_FAMILIES = tuple(f for f in ALL_FAMILIES if f.opt_in)
 
 
 def family(name):
-    return next(f for f in EVERY_FAMILY if f.name == name)
+    return next(f for f in ALL_FAMILIES if f.name == name)
 
 
 def _files(suffix, benchmarked=None, families=FAMILIES):
@@ -239,11 +235,10 @@ def _files(suffix, benchmarked=None, families=FAMILIES):
 
 SOURCES = _files(".hip")                      # one TU each
 OPT_IN_SOURCES = _files(".hip", families=OPT_IN_FAMILIES)
-LATER_SOURCES = _files(".hip", families=LATER_FAMILIES)
 BENCH_UNRELATED = _files(".hip", False)       # kernels no bench.py workload launches
 HEADERS = tuple(os.path.join(CSRC, f) for f in _files(".hpp", True)) + tuple(f.header for f in FAMILIES if any(f.files.values()))
-BUILD_HEADERS = HEADERS + tuple(os.path.join(CSRC, f) for f in _files(".hpp", False, EVERY_FAMILY)) + \
-    tuple(f.header for f in EVERY_FAMILY if not any(f.files.values()))
+BUILD_HEADERS = HEADERS + tuple(os.path.join(CSRC, f) for f in _files(".hpp", False, ALL_FAMILIES)) + \
+    tuple(f.header for f in ALL_FAMILIES if not any(f.files.values()))
 EXPORTS = tuple(family("core").functions)      # every symbol include/cspn_hip.h declares
 
 
@@ -254,7 +249,7 @@ def _source_digest(flags, code_only=False):
     import hashlib
     import re
     h = hashlib.sha256(" ".join(flags).encode())
-    tus = [f for f in SOURCES if f not in BENCH_UNRELATED] if code_only else SOURCES + OPT_IN_SOURCES + LATER_SOURCES
+    tus = [f for f in SOURCES if f not in BENCH_UNRELATED] if code_only else SOURCES + OPT_IN_SOURCES
     for path in [os.path.join(CSRC, f) for f in tus] + list(HEADERS if code_only else BUILD_HEADERS):
         with open(path, "rb") as fh:
             data = fh.read()
@@ -275,7 +270,7 @@ def build(force=False, verbose=False):
     csrc/_build/*.o and linked into the in-tree .so (which travels with gpurun snapshots).  Staleness is decided by
     a content hash of the sources + flags stored next to the library (file times do not survive every copy)."""
     from concurrent.futures import ThreadPoolExecutor
-    srcs = [os.path.join(CSRC, f) for f in SOURCES + OPT_IN_SOURCES + LATER_SOURCES]
+    srcs = [os.path.join(CSRC, f) for f in SOURCES + OPT_IN_SOURCES]
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     # -fno-slp-vectorize: the SLP pass pairs the stencil FMAs into v_pk_fma_f32 and pays for it with ~50 v_mov
     # per step to build operand pairs; scalar v_fma_f32 measured 4 % faster (profiles/).  No fast-math: 0/0 = NaN.
@@ -328,7 +323,7 @@ _lock = threading.Lock()
 
 
 def _declare(lib):
-    for fam in EVERY_FAMILY:
+    for fam in ALL_FAMILIES:
         for name, (restype, argtypes) in fam.functions.items():
             fn = getattr(lib, name)
             if restype is not ctypes.c_int:           # ctypes' default
@@ -349,7 +344,7 @@ def lib():
                         "cspn_monodepth_amd: %s is missing — build it with `python -c 'import __graft_entry__ as g; "
                         "g.build()'` (hipcc --offload-arch=gfx950).  There is no CPU fallback." % SO_PATH)
                 _lib = _declare(ctypes.CDLL(SO_PATH))
-                for fam in EVERY_FAMILY:
+                for fam in ALL_FAMILIES:
                     sub = "" if fam.name == "core" else fam.name      # cspn_abi_version, cspn_<family>_abi_version
                     if getattr(_lib, "cspn_%sabi_version" % (sub and sub + "_"))() != fam.abi_version:
                         raise RuntimeError("cspn_monodepth_amd: %sABI version mismatch" % (sub and sub + " "))

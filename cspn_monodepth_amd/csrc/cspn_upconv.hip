@@ -1,64 +1,9 @@
 // cspn_upconv.hip — the head of a decoder block fused with its un-pooling (include/cspn_upconv.h).
 //
-// The computation, the decomposition into four phases, the kernels and the argument checks are those of cspn_upconv_core.hpp; here is
-// the fp32 form of a chunk.
-//   pack  wp[25 taps, phase-major][Cp][Mp] fp32: filter-contiguous, a row of the chunk is TM consecutive floats
-//   fwd   the filter chunk [KC][TM] and the gathered pixels [KC][TN] go through LDS as they are loaded: a thread fetches 4 x 16 bytes of
-//         the filter chunk (rows (t >> 5) + 8 r) and pixel t & 127 of the channels (t >> 7) + 2 r, consecutive lanes on consecutive
-//         pixels of a row.  v_mfma_f32_32x32x2_f32: lane l holds A[l & 31][l >> 5] and B[l >> 5][l & 31], so a step reads two rows
-//         of each tile.  Exact fp32 products.
-// fp32 only.
+// The entry points of the fp32 family and nothing else: the computation, the decomposition into four phases, the kernels, the fp32
+// form of a chunk (the policy F32) and the argument checks are those of cspn_upconv_core.hpp.  fp32 only.
 #include "cspn_upconv_core.hpp"
 #include "cspn_upconv.h"
-
-namespace {
-
-struct F32 {
-    using T = float;
-    using ATile = float[KC][TM];
-    using BTile = float[KC][TN];
-    struct Chunk {
-        v4f wv[4];
-        float xv[16];
-    };
-    static constexpr bool CHANNEL_INNER = false;
-
-    static __device__ __forceinline__ const float* wtile(const Args<float>& a, int mt, int t) {
-        return a.wp + (size_t)mt * TM + (size_t)(t >> 5) * a.Mp + 4 * (t & 31);
-    }
-    static __device__ __forceinline__ void load(Chunk& k, const Args<float>& a, const float* wt, const float* xt, int c0, int t, bool there,
-                                                size_t hw) {
-        const int kb = t >> 7;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) k.wv[r] = *reinterpret_cast<const v4f*>(wt + (size_t)(c0 + 8 * r) * a.Mp);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int c = c0 + kb + 2 * r;
-            k.xv[r] = (there && c < a.C) ? xt[(size_t)c * hw] : 0.f;
-        }
-    }
-    static __device__ __forceinline__ void stage(ATile& As, BTile& Bs, const Chunk& k, int t) {
-        const int kb = t >> 7;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) *reinterpret_cast<v4f*>(&As[(t >> 5) + 8 * r][4 * (t & 31)]) = k.wv[r];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Bs[kb + 2 * r][t & 127] = k.xv[r];
-    }
-    static __device__ __forceinline__ void products(const ATile& As, const BTile& Bs, v16f (&acc)[2][2], int wm, int wn, int l31, int lh) {
-#pragma unroll
-        for (int s = 0; s < KC / 2; ++s) {
-            const int kk = 2 * s + lh;
-            const float a0 = As[kk][wm * 64 + l31], a1 = As[kk][wm * 64 + 32 + l31];
-            const float b0 = Bs[kk][wn * 64 + l31], b1 = Bs[kk][wn * 64 + 32 + l31];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
-};
-
-}  // namespace
 
 extern "C" {
 

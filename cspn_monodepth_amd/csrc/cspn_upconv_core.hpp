@@ -1,5 +1,14 @@
-// cspn_upconv_core.hpp — what the fused decoder-block heads share: cspn_upconv.hip (fp32) and cspn_uphalf.hip (fp16, f-13).
+// cspn_upconv_core.hpp — what the fused decoder-block kernels share: the heads cspn_upconv.hip (fp32) and
+// cspn_uphalf.hip (fp16, f-13), and the 3x3 tail cspn_uptail.hip (f-14).
+//   shared by all three   the tile constants, Args, the pixel decode, round_up and the precision policies F32 / F16: how a chunk of the
+//                         implicit GEMM is found, loaded, staged in LDS and multiplied
+//   the heads' alone      the phase tables, pack, the forward fwd<P>, the argument checks and the launches
+// NOT shared, on purpose: the forward.  The tail's tail_fwd<P, G> is fwd<P> with a geometry parameter; with the heads instantiated from
+// that generic form the fp32 head kept its registers and LDS but compiled to gather loads that wait for one another (9 more s_waitcnt)
+// and ran 20 to 24 % slower on the MI355X (RESULTS.md row 36).  That is a finding about the forward: with the policies alone moved
+// here, every kernel of the three units compiles to the instructions it had with a copy of its own.
 //
+// The heads:
 //   network/unet_ours.py:160-248 UpProj_Block / Gudi_UpProj_Block / Gudi_UpProj_Block_Cat / Simple_Gudi_UpConv_Block: zero-insertion
 //   un-pooling by 2, crop to oh x ow, then one or two bias-free 5x5 convolutions over that map, each followed by a batch norm (in eval
 //   mode a per-channel affine map) and, for the first, a ReLU.
@@ -16,8 +25,8 @@
 //          Single-buffered: the loads of a chunk are issued before the barrier that ends the previous chunk's products, and several
 //          workgroups per CU cover each other's loads.
 // An output element is one chain over K in the packed order, whatever its tile: no split-K, no atomics.
-// A precision is a policy P: the element type T, the two LDS tiles, the registers of a chunk, and how a chunk is found (wtile), loaded,
-// staged and multiplied; everything else, the argument checks of the entry points included, is here once.
+// A precision is a policy P (F32, F16 below): the element type T, the two LDS tiles, the registers of a chunk, and how a chunk is found
+// (wtile), loaded, staged and multiplied; everything else of the heads, the argument checks of the entry points included, is here once.
 #pragma once
 #include "cspn_common.hpp"
 
@@ -88,6 +97,124 @@ __device__ __forceinline__ Pixel decode(unsigned n, unsigned npix, int Ha, int W
     return q;
 }
 
+// The fp32 form of a chunk.
+//   pack  wp[taps][Cp][Mp] fp32: filter-contiguous, a row of the chunk is TM consecutive floats
+//   fwd   the filter chunk [KC][TM] and the gathered pixels [KC][TN] go through LDS as they are loaded: a thread fetches 4 x 16 bytes of
+//         the filter chunk (rows (t >> 5) + 8 r) and pixel t & 127 of the channels (t >> 7) + 2 r, consecutive lanes on consecutive
+//         pixels of a row.  v_mfma_f32_32x32x2_f32: lane l holds A[l & 31][l >> 5] and B[l >> 5][l & 31], so a step reads two rows
+//         of each tile.  Exact fp32 products.
+// load(): c0 is the chunk's first channel within its map, C the map's channels, wt the filter chunk's tap at that map's channel 0.
+struct F32 {
+    using T = float;
+    using ATile = float[KC][TM];
+    using BTile = float[KC][TN];
+    struct Chunk {
+        v4f wv[4];
+        float xv[16];
+    };
+    static constexpr bool CHANNEL_INNER = false;
+
+    static __device__ __forceinline__ const float* wtile(const Args<float>& a, int mt, int t) {
+        return a.wp + (size_t)mt * TM + (size_t)(t >> 5) * a.Mp + 4 * (t & 31);
+    }
+    static __device__ __forceinline__ void load(Chunk& k, const Args<float>& a, const float* wt, const float* xt, int c0, int C, int t,
+                                                bool there, size_t hw) {
+        const int kb = t >> 7;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) k.wv[r] = *reinterpret_cast<const v4f*>(wt + (size_t)(c0 + 8 * r) * a.Mp);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int c = c0 + kb + 2 * r;
+            k.xv[r] = (there && c < C) ? xt[(size_t)c * hw] : 0.f;
+        }
+    }
+    static __device__ __forceinline__ void stage(ATile& As, BTile& Bs, const Chunk& k, int t) {
+        const int kb = t >> 7;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) *reinterpret_cast<v4f*>(&As[(t >> 5) + 8 * r][4 * (t & 31)]) = k.wv[r];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Bs[kb + 2 * r][t & 127] = k.xv[r];
+    }
+    static __device__ __forceinline__ void products(const ATile& As, const BTile& Bs, v16f (&acc)[2][2], int wm, int wn, int l31, int lh) {
+#pragma unroll
+        for (int s = 0; s < KC / 2; ++s) {
+            const int kk = 2 * s + lh;
+            const float a0 = As[kk][wm * 64 + l31], a1 = As[kk][wm * 64 + 32 + l31];
+            const float b0 = Bs[kk][wn * 64 + l31], b1 = Bs[kk][wn * 64 + 32 + l31];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+};
+
+// The fp16 form of a chunk.
+//   pack  wp[taps][Mp][Cp] fp16, from fp32 (rounded to nearest even) or fp16 filters.  Channel-contiguous: the 8 channels lane l of
+//         v_mfma_f32_32x32x16_f16 holds of row l & 31 (A[l & 31][8 (l >> 5) + j]) are 16 consecutive bytes.
+//   fwd   a chunk is two blocks of 16 channels.  The filter chunk [TM][KC] and the gathered pixels [TN][KC] go through LDS, both
+//         channel-contiguous with rows of 80 bytes (64 of data + 16 of padding): the 16 lanes a ds_read_b128 serves in one cycle then
+//         start at 20 l mod 64 banks, all different, so the operand reads are conflict-free without a swizzle.  A thread fetches
+//         2 x 16 bytes of the filter chunk (rows (t >> 2) + 64 r, fragment t & 3) and pixel t & 127 of the channel groups of 8
+//         (t >> 7) + 2 r.  The NCHW gather is 2-byte loads, consecutive lanes on consecutive pixels of a row (pairs are not formed: the
+//         column offset of a tap and the row length make half of them misaligned).  fp32 accumulation, one rounding of the result.
+constexpr int ROW8 = KC / 8 + 1;          // an LDS row in 16-byte fragments: 4 of data, 1 of padding
+
+typedef _Float16 v8h __attribute__((ext_vector_type(8)));
+
+struct F16 {
+    using T = _Float16;
+    using ATile = v8h[TM][ROW8];
+    using BTile = v8h[TN][ROW8];
+    struct Chunk {
+        v8h wv[2];
+        _Float16 xv[2][8];      // scalars: the two 16-byte vectors are formed in stage(), behind the barrier, not in front of it
+    };
+    static constexpr bool CHANNEL_INNER = true;
+
+    static __device__ __forceinline__ const _Float16* wtile(const Args<_Float16>& a, int mt, int t) {
+        return a.wp + ((size_t)mt * TM + (t >> 2)) * a.Cp + 8 * (t & 3);
+    }
+    static __device__ __forceinline__ void load(Chunk& k, const Args<_Float16>& a, const _Float16* wt, const _Float16* xt, int c0, int C,
+                                                int t, bool there, size_t hw) {
+        const int cb = c0 + 8 * (t >> 7);      // c = cb + a constant, one add: known not to wrap, c * hw needs no sign extension
+#pragma unroll
+        for (int r = 0; r < 2; ++r) k.wv[r] = *reinterpret_cast<const v8h*>(wt + (size_t)(64 * r) * a.Cp + c0);
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int c = cb + 16 * r + j;
+                k.xv[r][j] = (there && c < C) ? xt[(size_t)c * hw] : (_Float16)0.f;
+            }
+    }
+    static __device__ __forceinline__ void stage(ATile& As, BTile& Bs, const Chunk& k, int t) {
+        const int px = t & 127, kb = t >> 7, wrow = t >> 2, wseg = t & 3;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            As[wrow + 64 * r][wseg] = k.wv[r];
+            v8h xv;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) xv[j] = k.xv[r][j];
+            Bs[px][kb + 2 * r] = xv;
+        }
+    }
+    static __device__ __forceinline__ void products(const ATile& As, const BTile& Bs, v16f (&acc)[2][2], int wm, int wn, int l31, int lh) {
+#pragma unroll
+        for (int s = 0; s < KC / 16; ++s) {
+            const int f = 2 * s + lh;                        // channels 16 s + 8 (lane >> 5) .. + 7
+            const v8h a0 = As[wm * 64 + l31][f], a1 = As[wm * 64 + 32 + l31][f];
+            const v8h b0 = Bs[wn * 64 + l31][f], b1 = Bs[wn * 64 + 32 + l31][f];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+};
+
+// The heads' forward.  The tail's (cspn_uptail.hip, tail_fwd<P, G>) is this text with a geometry parameter, and the two stay two: see
+// the head of this file.
 template <class P>
 __global__ __launch_bounds__(THREADS) void fwd(const Args<typename P::T> a) {
     using T = typename P::T;
@@ -133,7 +260,7 @@ __global__ __launch_bounds__(THREADS) void fwd(const Args<typename P::T> a) {
         const T* wt = wtile + (size_t)(tap_base(p) + tap) * a.Mp * a.Cp;
         for (int cc = 0; cc < cchunks; ++cc) {
             typename P::Chunk k;
-            P::load(k, a, wt, xt, cc * KC, t, there, hw);
+            P::load(k, a, wt, xt, cc * KC, a.C, t, there, hw);
             __syncthreads();                                     // the previous chunk has been read
             P::stage(As, Bs, k, t);
             __syncthreads();

@@ -2,13 +2,11 @@
 // (include/cspn_uptail.h).
 //
 // An implicit GEMM as the fused heads': M = O, N = the pixels of the whole batch in tiles of 128, K = (tap, channel) in chunks of 32
-// channels of one tap.  From cspn_upconv_core.hpp come Args, the pixel decode, the tile constants and round_up.  The forward below is
-// the core's forward with a geometry parameter G beside the precision policy P (Same3: one phase of 9 taps at offsets -1 .. 1, the
-// store at y W + x, a per-chunk choice between two maps, a residual in the epilogue), and the policies F32 / F16 are the heads'
-// with the map's channel count as an argument of load().  They are HERE and not in the core on purpose: with the forward of the
-// heads instantiated from this generic form, the fp32 head compiled to the same registers and LDS but to gather loads that wait
-// for one another (9 more s_waitcnt) and ran 20 to 24 % slower on the MI355X (RESULTS.md row 36).  Until a shared form compiles
-// to the parent's schedule the heads keep their own text.
+// channels of one tap.  From cspn_upconv_core.hpp come Args, the pixel decode, the tile constants, round_up and the precision
+// policies F32 / F16, whose load() takes the channel count of the map a chunk lies in.  The forward is NOT shared: tail_fwd<P, G> below
+// is the core's fwd<P> with a geometry parameter G (Same3: one phase of 9 taps at offsets -1 .. 1, the store at y W + x, a per-chunk
+// choice between two maps, a residual in the epilogue), and the heads keep their own text because, instantiated from this generic
+// form, the fp32 head ran 20 to 24 % slower (RESULTS.md row 36; the head of the core has the detail).
 //   pack  wp[9 taps][Cp][Mp] fp32 or wp[9][Mp][Cp] fp16, as the precision's wtile() expects; Cp = roundup(Ca, KC) + roundup(Cb, KC),
 //         so that a chunk of KC packed channels never straddles the two maps.  Zero-filled.
 #include "cspn_upconv_core.hpp"
@@ -30,122 +28,6 @@ template <typename T>
 struct Source {
     const T* x;
     int skip, C;
-};
-
-// The fp32 form of a chunk.
-//   pack  wp[taps][Cp][Mp] fp32: filter-contiguous, a row of the chunk is TM consecutive floats
-//   fwd   the filter chunk [KC][TM] and the gathered pixels [KC][TN] go through LDS as they are loaded: a thread fetches 4 x 16 bytes of
-//         the filter chunk (rows (t >> 5) + 8 r) and pixel t & 127 of the channels (t >> 7) + 2 r, consecutive lanes on consecutive
-//         pixels of a row.  v_mfma_f32_32x32x2_f32: lane l holds A[l & 31][l >> 5] and B[l >> 5][l & 31], so a step reads two rows
-//         of each tile.  Exact fp32 products.
-// load(): c0 is the chunk's first channel within its map, C the map's channels, wt the filter chunk's tap at that map's channel 0.
-struct F32 {
-    using T = float;
-    using ATile = float[KC][TM];
-    using BTile = float[KC][TN];
-    struct Chunk {
-        v4f wv[4];
-        float xv[16];
-    };
-    static constexpr bool CHANNEL_INNER = false;
-
-    static __device__ __forceinline__ const float* wtile(const Args<float>& a, int mt, int t) {
-        return a.wp + (size_t)mt * TM + (size_t)(t >> 5) * a.Mp + 4 * (t & 31);
-    }
-    static __device__ __forceinline__ void load(Chunk& k, const Args<float>& a, const float* wt, const float* xt, int c0, int C, int t,
-                                                bool there, size_t hw) {
-        const int kb = t >> 7;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) k.wv[r] = *reinterpret_cast<const v4f*>(wt + (size_t)(c0 + 8 * r) * a.Mp);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int c = c0 + kb + 2 * r;
-            k.xv[r] = (there && c < C) ? xt[(size_t)c * hw] : 0.f;
-        }
-    }
-    static __device__ __forceinline__ void stage(ATile& As, BTile& Bs, const Chunk& k, int t) {
-        const int kb = t >> 7;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) *reinterpret_cast<v4f*>(&As[(t >> 5) + 8 * r][4 * (t & 31)]) = k.wv[r];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Bs[kb + 2 * r][t & 127] = k.xv[r];
-    }
-    static __device__ __forceinline__ void products(const ATile& As, const BTile& Bs, v16f (&acc)[2][2], int wm, int wn, int l31, int lh) {
-#pragma unroll
-        for (int s = 0; s < KC / 2; ++s) {
-            const int kk = 2 * s + lh;
-            const float a0 = As[kk][wm * 64 + l31], a1 = As[kk][wm * 64 + 32 + l31];
-            const float b0 = Bs[kk][wn * 64 + l31], b1 = Bs[kk][wn * 64 + 32 + l31];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
-};
-
-// The fp16 form of a chunk.
-//   pack  wp[taps][Mp][Cp] fp16, from fp32 (rounded to nearest even) or fp16 filters.  Channel-contiguous: the 8 channels lane l of
-//         v_mfma_f32_32x32x16_f16 holds of row l & 31 (A[l & 31][8 (l >> 5) + j]) are 16 consecutive bytes.
-//   fwd   a chunk is two blocks of 16 channels.  The filter chunk [TM][KC] and the gathered pixels [TN][KC] go through LDS, both
-//         channel-contiguous with rows of 80 bytes (64 of data + 16 of padding): the 16 lanes a ds_read_b128 serves in one cycle then
-//         start at 20 l mod 64 banks, all different, so the operand reads are conflict-free without a swizzle.  A thread fetches
-//         2 x 16 bytes of the filter chunk (rows (t >> 2) + 64 r, fragment t & 3) and pixel t & 127 of the channel groups of 8
-//         (t >> 7) + 2 r.  The NCHW gather is 2-byte loads, consecutive lanes on consecutive pixels of a row (pairs are not formed: the
-//         column offset of a tap and the row length make half of them misaligned).  fp32 accumulation, one rounding of the result.
-constexpr int ROW8 = KC / 8 + 1;          // an LDS row in 16-byte fragments: 4 of data, 1 of padding
-
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-
-struct F16 {
-    using T = _Float16;
-    using ATile = v8h[TM][ROW8];
-    using BTile = v8h[TN][ROW8];
-    struct Chunk {
-        v8h wv[2];
-        _Float16 xv[2][8];      // scalars: the two 16-byte vectors are formed in stage(), behind the barrier, not in front of it
-    };
-    static constexpr bool CHANNEL_INNER = true;
-
-    static __device__ __forceinline__ const _Float16* wtile(const Args<_Float16>& a, int mt, int t) {
-        return a.wp + ((size_t)mt * TM + (t >> 2)) * a.Cp + 8 * (t & 3);
-    }
-    static __device__ __forceinline__ void load(Chunk& k, const Args<_Float16>& a, const _Float16* wt, const _Float16* xt, int c0, int C,
-                                                int t, bool there, size_t hw) {
-        const int cb = c0 + 8 * (t >> 7);      // c = cb + a constant, one add: known not to wrap, c * hw needs no sign extension
-#pragma unroll
-        for (int r = 0; r < 2; ++r) k.wv[r] = *reinterpret_cast<const v8h*>(wt + (size_t)(64 * r) * a.Cp + c0);
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int c = cb + 16 * r + j;
-                k.xv[r][j] = (there && c < C) ? xt[(size_t)c * hw] : (_Float16)0.f;
-            }
-    }
-    static __device__ __forceinline__ void stage(ATile& As, BTile& Bs, const Chunk& k, int t) {
-        const int px = t & 127, kb = t >> 7, wrow = t >> 2, wseg = t & 3;
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            As[wrow + 64 * r][wseg] = k.wv[r];
-            v8h xv;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) xv[j] = k.xv[r][j];
-            Bs[px][kb + 2 * r] = xv;
-        }
-    }
-    static __device__ __forceinline__ void products(const ATile& As, const BTile& Bs, v16f (&acc)[2][2], int wm, int wn, int l31, int lh) {
-#pragma unroll
-        for (int s = 0; s < KC / 16; ++s) {
-            const int f = 2 * s + lh;                        // channels 16 s + 8 (lane >> 5) .. + 7
-            const v8h a0 = As[wm * 64 + l31][f], a1 = As[wm * 64 + 32 + l31][f];
-            const v8h b0 = Bs[wn * 64 + l31][f], b1 = Bs[wn * 64 + 32 + l31][f];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
 };
 
 // The tail: one phase, the 9 taps at offsets -1 .. 1 of a pad-1 3x3 window over the maps themselves (oh = H, ow = W).  The packed

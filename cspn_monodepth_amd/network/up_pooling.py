@@ -482,17 +482,17 @@ def conv3x3_bn_act(a, pack, side=None, residual=None, relu=True):
 
 
 DECODER_BLOCKS = ("gud_up_proj_layer1", "gud_up_proj_layer2", "gud_up_proj_layer3", "gud_up_proj_layer4")
-# What `fused_decoder=True` selects: the blocks at which tools/upconv_bench.py measured the fused head ahead of the stock one by
+# What `fused_decoder=True` selects: the blocks at which `tools/decoder_bench.py upconv` measured the fused head ahead of the stock one by
 # more than the spread of the two measurements — its 90th percentile below the stock 10th, warm and cache-cold
 # (profiles/r18_upconv_bench.json, RESULTS.md row 33: all four, 3.3 to 5.3 times).
 FUSED_DECODER_DEFAULT = ("gud_up_proj_layer1", "gud_up_proj_layer2", "gud_up_proj_layer3", "gud_up_proj_layer4")
-# The same rule for half inputs, from tools/uphalf_bench.py: the half kernel's 90th percentile below the 10th of the stock half head
+# The same rule for half inputs, from `tools/decoder_bench.py uphalf`: the half kernel's 90th percentile below the 10th of the stock half head
 # (un-pool, MIOpen convolutions, batch norms and ReLU on half tensors), warm and cache-cold (profiles/r19_uphalf_bench.json,
 # RESULTS.md row 34: all four, 3.8 to 9.5 times).
 FUSED_DECODER_HALF_DEFAULT = ("gud_up_proj_layer1", "gud_up_proj_layer2", "gud_up_proj_layer3", "gud_up_proj_layer4")
 
 
-# What `fused_tail=True` selects, by the same rule from tools/uptail_bench.py against the stock tail (cat, MIOpen 3x3 convolutions,
+# What `fused_tail=True` selects, by the same rule from `tools/decoder_bench.py uptail` against the stock tail (cat, MIOpen 3x3 convolutions,
 # eval batch norms, add, ReLUs) measured in the same process: the fused tail's 90th percentile below the stock 10th, warm and
 # cache-cold (profiles/r21_uptail_bench.json, RESULTS.md row 36).  fp32: none — the fused tail was 4 to 67 % SLOWER than the stock tail
 # at every stage (11.2 against 9.6 ms per forward), so True selects nothing for fp32 inputs; names still force the path.  fp16: layers 2

@@ -201,7 +201,7 @@ def test_upconv_family_contract(monkeypatch):
     assert declared == sorted(fam.functions) == sorted(names)
     lib = _lib.lib()
     assert all(hasattr(lib, n) for n in names) and lib.cspn_upconv_abi_version() == fam.abi_version == 1
-    assert _lib.OPT_IN_FAMILIES[:2] == (_lib.family("heads"), fam) and fam not in _lib.FAMILIES and len(_lib.ALL_FAMILIES) == 12
+    assert _lib.OPT_IN_FAMILIES[:2] == (_lib.family("heads"), fam) and fam not in _lib.FAMILIES and len(_lib.ALL_FAMILIES) == 13
     assert "cspn_upconv.hip" in _lib.OPT_IN_SOURCES and "cspn_upconv.hip" not in _lib.SOURCES
     assert fam.header in _lib.BUILD_HEADERS and fam.header not in _lib.HEADERS
     # the core both decoder-head families are built on is a header of an opt-in family: seen by the build's staleness hash (and so by

@@ -55,9 +55,9 @@ def test_uphalf_family_contract():
     lib = _lib.lib()
     assert all(hasattr(lib, n) for n in NAMES) and lib.cspn_uphalf_abi_version() == fam.abi_version == 1
     # the opt-in part of the table, after the nine
-    assert [f.name for f in _lib.OPT_IN_FAMILIES] == ["heads", "upconv", "uphalf"]
+    assert [f.name for f in _lib.OPT_IN_FAMILIES] == ["heads", "upconv", "uphalf", "uptail"]
     assert fam in _lib.OPT_IN_FAMILIES and fam not in _lib.FAMILIES
-    assert _lib.ALL_FAMILIES == _lib.FAMILIES + _lib.OPT_IN_FAMILIES and len(_lib.ALL_FAMILIES) == 12
+    assert _lib.ALL_FAMILIES == _lib.FAMILIES + _lib.OPT_IN_FAMILIES and len(_lib.ALL_FAMILIES) == 13
     assert "cspn_uphalf.hip" in _lib.OPT_IN_SOURCES and "cspn_uphalf.hip" not in _lib.SOURCES
     assert os.path.exists(os.path.join(_lib.CSRC, "cspn_uphalf.hip"))
     assert fam.header in _lib.BUILD_HEADERS and fam.header not in _lib.HEADERS

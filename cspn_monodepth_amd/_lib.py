@@ -40,6 +40,7 @@ BLEND_NONE, BLEND_SPARSE, BLEND_PREMASK = 0, 1, 2
 HEADS_MAX_HEADS, HEADS_MAX_OUT_CHANNELS = 4, 16              # CSPN_HEADS_MAX_* (include/cspn_heads.h)
 HEADS_FORWARD, HEADS_BACKWARD_INPUT, HEADS_BACKWARD_WEIGHTS = 0, 1, 2      # the `pass` of cspn_heads_workspace_bytes
 UPCONV_MAX_FILTERS = 2                                       # CSPN_UPCONV_MAX_FILTERS (include/cspn_upconv.h)
+UPCONV_F32_BF16X3 = 2                                        # CSPN_UPCONV_F32_BF16X3: a `dtype` of cspn_upconv_forward alone
 UPHALF_MAX_FILTERS = 2                                       # CSPN_UPHALF_MAX_FILTERS (include/cspn_uphalf.h)
 
 

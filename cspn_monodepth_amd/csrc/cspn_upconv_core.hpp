@@ -25,7 +25,7 @@
 //          Single-buffered: the loads of a chunk are issued before the barrier that ends the previous chunk's products, and several
 //          workgroups per CU cover each other's loads.
 // An output element is one chain over K in the packed order, whatever its tile: no split-K, no atomics.
-// A precision is a policy P (F32, F16 below): the element type T, the two LDS tiles, the registers of a chunk, and how a chunk is found
+// A precision is a policy P (F32, F16 and, for the heads' fp32 family alone, F32X3 below): the element type T, the two LDS tiles, the registers of a chunk, and how a chunk is found
 // (wtile), loaded, staged and multiplied; everything else of the heads, the argument checks of the entry points included, is here once.
 #pragma once
 #include "cspn_common.hpp"
@@ -209,6 +209,88 @@ struct F16 {
             acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc[0][1], 0, 0, 0);
             acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc[1][0], 0, 0, 0);
             acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+};
+
+// The split form of a chunk: fp32 in and out, the products on the bf16 matrix cores.
+//   split every fp32 value v, filter or pixel, becomes three bf16 terms, conversions to nearest even:
+//             v1 = bf16(v),  v2 = bf16(v - v1),  v3 = bf16(v - v1 - v2)
+//         Both subtractions are exact in fp32 and v1 + v2 + v3 == v (8 + 8 + 8 significant bits cover the 24 of v).  A product x w
+//         is the six terms x_i w_j with i + j <= 4, each exact in fp32; the three left out are below (2^-23 + 2^-32) |x w|.
+//   pack  the fp32 pack of F32 as it is, wp[taps][Cp][Mp]: one pack serves both forms.
+//   fwd   a thread fetches 8 x 8 bytes of the filter chunk — the channels 8 (t >> 6) .. + 7 of the flat channels 2 (t & 63), + 1 —
+//         and pixel t & 127 of the channel groups of 8 (t >> 7) + 2 r as F16 does, splits them in registers behind the barrier and
+//         stages the three planes of each tile channel-contiguous in F16's rows of 80 bytes: one ds_read_b128 per fragment, 60 KiB of
+//         LDS per workgroup.  A chunk is two blocks of 16 channels; per block the six terms go to v_mfma_f32_32x32x16_bf16 in the
+//         order (1,1) (1,2) (2,1) (1,3) (2,2) (3,1) (filter term, pixel term), accumulating in fp32.  An output element is still one
+//         chain: taps, chunks, blocks and terms in that order; the order of the 16 products inside an instruction is the hardware's.
+typedef __bf16 v8b __attribute__((ext_vector_type(8)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+struct F32X3 {
+    using T = float;
+    using ATile = v8b[3][TM][ROW8];
+    using BTile = v8b[3][TN][ROW8];
+    struct Chunk {
+        v2f wv[8];
+        float xv[2][8];
+    };
+    static constexpr bool CHANNEL_INNER = false;
+
+    static __device__ __forceinline__ const float* wtile(const Args<float>& a, int mt, int t) {
+        return a.wp + (size_t)mt * TM + (size_t)(8 * (t >> 6)) * a.Mp + 2 * (t & 63);
+    }
+    static __device__ __forceinline__ void load(Chunk& k, const Args<float>& a, const float* wt, const float* xt, int c0, int C, int t,
+                                                bool there, size_t hw) {
+        const int cb = c0 + 8 * (t >> 7);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) k.wv[j] = *reinterpret_cast<const v2f*>(wt + (size_t)(c0 + j) * a.Mp);
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int c = cb + 16 * r + j;
+                k.xv[r][j] = (there && c < C) ? xt[(size_t)c * hw] : 0.f;
+            }
+    }
+    // element j of the three planes' fragments <- the three terms of v
+    static __device__ __forceinline__ void split(float v, v8b (&p)[3], int j) {
+        const __bf16 v1 = (__bf16)v;
+        const float r1 = v - (float)v1;
+        const __bf16 v2 = (__bf16)r1;
+        p[0][j] = v1, p[1][j] = v2, p[2][j] = (__bf16)(r1 - (float)v2);
+    }
+    static __device__ __forceinline__ void stage(ATile& As, BTile& Bs, const Chunk& k, int t) {
+        const int px = t & 127, kb = t >> 7, wrow = 2 * (t & 63), wseg = t >> 6;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            v8b w[3], x[3];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) split(k.wv[j][r], w, j), split(k.xv[r][j], x, j);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) As[i][wrow + r][wseg] = w[i], Bs[i][px][kb + 2 * r] = x[i];
+        }
+    }
+    static __device__ __forceinline__ void products(const ATile& As, const BTile& Bs, v16f (&acc)[2][2], int wm, int wn, int l31, int lh) {
+        constexpr int TERMS[6][2] = {{0, 0}, {0, 1}, {1, 0}, {0, 2}, {1, 1}, {2, 0}};      // (filter plane, pixel plane)
+#pragma unroll
+        for (int s = 0; s < KC / 16; ++s) {
+            const int f = 2 * s + lh;                        // channels 16 s + 8 (lane >> 5) .. + 7
+            v8b a[3][2], b[3][2];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                a[i][0] = As[i][wm * 64 + l31][f], a[i][1] = As[i][wm * 64 + 32 + l31][f];
+                b[i][0] = Bs[i][wn * 64 + l31][f], b[i][1] = Bs[i][wn * 64 + 32 + l31][f];
+            }
+#pragma unroll
+            for (int e = 0; e < 6; ++e) {
+                const int i = TERMS[e][0], j = TERMS[e][1];
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][1], acc[1][1], 0, 0, 0);
+            }
         }
     }
 };

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from ..post_process import CSPN_new as post_process
-from .up_pooling import FusedHead, select_fused_decoder, select_fused_tail, up_pooling, up_pooling_conv3x3
+from .up_pooling import FusedHead, select_fused_decoder, select_fused_precision, select_fused_tail, up_pooling, up_pooling_conv3x3
 
 __all__ = ["ResNet", "resnet50", "resnet18", "Bottleneck", "BasicBlock", "Gudi_UpProj_Block", "Gudi_UpProj_Block_Cat",
            "Simple_Gudi_UpConv_Block_Last_Layer", "UpProj_Block", "DECODER_SIZES_NYU"]
@@ -176,12 +176,16 @@ class ResNet(nn.Module):
     + shortcut, ReLU — as one ``conv3x3_bn_act`` call per convolution (include/cspn_uptail.h), whether its head is fused or not.  True
     selects up_pooling.FUSED_TAIL_DEFAULT (half inputs: FUSED_TAIL_HALF_DEFAULT), the blocks where that was measured to be faster —
     lists that may be empty; names select those blocks in both precisions.
+    fused_decoder_precision (None; never a default): the ``precision`` of ``up_pooling_conv5x5`` for the blocks fused_decoder names, on
+    fp32 inputs — None / "exact", or "bf16x3": the products split into bf16 terms on the bf16 matrix cores, fp32-class results with
+    other bits (include/cspn_upconv.h).  It selects no block, half inputs ignore it, and train or grad mode run the stock blocks.
     The three switches together: fused_heads covers gud_up_proj_layer5 / 6, fused_decoder the head and fused_tail the tail of
     gud_up_proj_layer1 .. 4; each is forward-only, changes no module, parameter or state_dict key, and none changes what another does."""
 
     def __init__(self, block, layers, up_proj_block=UpProj_Block, decoder_sizes=DECODER_SIZES_NYU, prop_time=24,
                  prop_kernel=3, reference_state_dict=True, cspn_plan=None, affinity_channels=8, fused_heads=False,
-                 fused_decoder=False, fused_tail=False):
+                 fused_decoder=False, fused_tail=False,
+                 fused_decoder_precision=None):
         super(ResNet, self).__init__()
         self.inplanes = 64
         e = block.expansion
@@ -217,6 +221,7 @@ class ResNet(nn.Module):
         self.fused_heads = bool(fused_heads)
         self.fused_decoder = select_fused_decoder(self, fused_decoder)
         self.fused_tail = select_fused_tail(self, fused_tail)
+        self.fused_decoder_precision = select_fused_precision(self, fused_decoder_precision)
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None

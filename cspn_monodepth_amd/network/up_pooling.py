@@ -26,7 +26,9 @@ opt-in — ``fused_heads=True`` of the models — and differs from the two-block
 norms in eval mode and the ReLU of the first, as one implicit GEMM per output phase on the fp32 matrix cores
 (include/cspn_upconv.h).  Forward only and opt-in — ``fused_decoder`` of the models; the filters are reordered once by
 ``pack_upconv5x5``.  A half ``x`` (``torch.autocast``, ``model.half()``) takes a pack of ``dtype=torch.float16`` and runs on the fp16
-matrix cores with fp32 accumulation and one rounding of the result (include/cspn_uphalf.h).
+matrix cores with fp32 accumulation and one rounding of the result (include/cspn_uphalf.h).  ``precision="bf16x3"`` — the models'
+``fused_decoder_precision`` — keeps fp32 tensors and the fp32 pack and runs the products on the bf16 matrix cores, every operand split
+into three bf16 terms: fp32-class, other bits, measured slower than the exact path and so selected by nothing but the keyword.
 
 ``conv3x3_bn_act`` is the rest of such a block — the 3x3 convolutions ``conv1_1`` (over the head's output and the encoder skip, without
 the ``cat``) and ``conv2``, their eval-mode batch norms, the shortcut add and the ReLUs — one call per convolution on the same matrix
@@ -307,7 +309,10 @@ def pack_upconv5x5(weights, batchnorms=None, relu=(True, False), dtype=torch.flo
     return UpconvPack(packed, scale, shift, out_channels, C, sum(o for o, r in zip(out_channels, relu) if r), sources, dtype)
 
 
-def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=None, relu_channels=0):
+UPCONV_PRECISIONS = (None, "exact", "bf16x3")
+
+
+def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=None, relu_channels=0, precision=None):
     """Un-pooling by 2 to (oheight, owidth), the one or two bias-free 5x5 convolutions (padding 2) of a decoder block over it, a
     per-channel affine map and a ReLU on the leading channels, in one kernel:
 
@@ -325,6 +330,13 @@ def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=No
     gives fp16 outputs — fp16 products accumulated in fp32 on the fp16 matrix cores, the affine map and the ReLU in fp32, one
     rounding to fp16 at the end (include/cspn_uphalf.h); the same contract otherwise.  The filters themselves are taken in fp32 only.
 
+    ``precision``: None or ``"exact"`` — the above — or ``"bf16x3"``: fp32 ``x``, fp32 outputs and the same fp32 pack (switching costs
+    no repack), but every value of ``x`` and of the filters is split into three bf16 terms that sum to it exactly, and the six
+    leading cross products of a product run on the bf16 matrix cores with fp32 accumulation (include/cspn_upconv.h: the order, the
+    bound (2^-23 + 2^-32) |x w| on what a product drops, and what an Inf or a value outside bf16's range does).  fp32-class results
+    with other bits than the exact path — hence never a default — and the same contract otherwise: bits independent of the batch,
+    runs repeat, capturable.  Refused with a half ``x`` or a fp16 pack.
+
     ``pack_or_weights``: an ``UpconvPack`` (its scale, shift and ReLU count apply; the arguments of that name must be left alone),
     or the filters themselves — packed for this one call — with ``scale`` / ``shift`` (fp32 [O_0 + O_1], both or neither) and
     ``relu_channels`` as given.
@@ -339,6 +351,11 @@ def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=No
     if x.dim() != 4:
         raise ValueError("%s: x must be [N,C,H,W], got %s" % (who, tuple(x.shape)))
     pack = pack_or_weights if isinstance(pack_or_weights, UpconvPack) else None
+    if precision not in UPCONV_PRECISIONS:
+        raise ValueError("%s: precision must be None, \"exact\" or \"bf16x3\", got %r" % (who, precision))
+    if precision == "bf16x3" and (x.dtype == torch.float16 or (pack is not None and pack.dtype == torch.float16)):
+        raise ValueError("%s: precision=\"bf16x3\" splits fp32 values: it takes a fp32 x and a fp32 pack, got x %s%s (a half x runs on the "
+                         "fp16 matrix cores as it is)" % (who, x.dtype, "" if pack is None else " and a pack of %s" % pack.dtype))
     if pack is not None:
         if scale is not None or shift is not None or relu_channels:
             raise ValueError("%s: scale, shift and relu_channels come with the pack" % who)
@@ -385,7 +402,8 @@ def up_pooling_conv5x5(x, pack_or_weights, oheight, owidth, scale=None, shift=No
     tail = (_p(pack.packed), _p(None if scale is None else scale.contiguous()), _p(None if shift is None else shift.contiguous()),
             relu_channels, _ptrs(outs), (ctypes.c_int * len(outs))(*out_channels), len(outs), N, C, H, W, oheight, owidth)
     _, _, forward_fn, takes_dtype, _ = _UPCONV_KERNELS[pack.dtype]
-    launch(dev, forward_fn, _p(xc), *((_dt(xc),) if takes_dtype else ()), *tail)
+    dtype = _lib.UPCONV_F32_BF16X3 if precision == "bf16x3" else _dt(xc)       # the arithmetic; the tensors are fp32 either way
+    launch(dev, forward_fn, _p(xc), *((dtype,) if takes_dtype else ()), *tail)
     return outs
 
 
@@ -528,6 +546,17 @@ def select_fused_decoder(model, fused_decoder):
     return _select(model, "fused_decoder", fused_decoder, FUSED_DECODER_DEFAULT, FUSED_DECODER_HALF_DEFAULT, "fused_head")
 
 
+def select_fused_precision(model, precision):
+    """The `fused_decoder_precision` keyword of the models: None, "exact" or "bf16x3" (``up_pooling_conv5x5``'s ``precision``), set
+    on every decoder block as `fused_precision`.  It selects no block — `fused_decoder` does — and is never a default: "bf16x3"
+    changes bits.  What the model keeps as `fused_decoder_precision`."""
+    if precision not in UPCONV_PRECISIONS:
+        raise ValueError("fused_decoder_precision: must be None, \"exact\" or \"bf16x3\", got %r" % (precision,))
+    for n in DECODER_BLOCKS:
+        getattr(model, n).fused_precision = precision
+    return precision
+
+
 def select_fused_tail(model, fused_tail):
     """The `fused_tail` switch of the models, as `select_fused_decoder`: True selects FUSED_TAIL_DEFAULT (half inputs:
     FUSED_TAIL_HALF_DEFAULT), names select those blocks for both precisions.  What the model keeps as `fused_tail`."""
@@ -540,9 +569,11 @@ class FusedHead(object):
     with grad mode off.  The pack is made at the first such call, made again when a source changed (``load_state_dict``, an
     in-place update, a parameter replaced by ``.to()``) and dropped by ``train()``; it is no parameter, buffer or module.  It is made
     for the dtype of the block's input, fp32 or fp16, and made again when that changes (one pack at a time: a model run in both
-    precisions in turn repacks at every change)."""
+    precisions in turn repacks at every change).  `fused_precision` (the models' `fused_decoder_precision`) is handed to
+    ``up_pooling_conv5x5`` as its ``precision`` for fp32 inputs; half inputs ignore it, and the fp32 pack is the same for every value."""
     fused_head = False
     fused_head_half = None               # None: as fused_head (a block marked by hand)
+    fused_precision = None               # the `precision` of up_pooling_conv5x5 for fp32 inputs (the models' fused_decoder_precision)
     _upconv_pack = None
 
     def _fuse_head(self, x=None):
@@ -566,7 +597,10 @@ class FusedHead(object):
         pack = self._upconv_pack
         if pack is None or pack.dtype != x.dtype or pack.stale() or not pack.made_from(weights + [t for bn in bns for t in _bn_sources(bn)]):
             pack = self._upconv_pack = pack_upconv5x5(weights, bns, (True, False)[:len(convs)], dtype=x.dtype)
-        outs = up_pooling_conv5x5(x, pack, self.oheight, self.owidth)
+        if self.fused_precision is not None and x.dtype == torch.float32:       # half inputs run the fp16 kernel whatever it says
+            outs = up_pooling_conv5x5(x, pack, self.oheight, self.owidth, precision=self.fused_precision)
+        else:
+            outs = up_pooling_conv5x5(x, pack, self.oheight, self.owidth)
         return outs[0], (outs[1] if len(outs) > 1 else None)
 
     # The tail of the block — conv1_1 -> bn1_1 -> ReLU over (out, side_input) where the block has them, then conv2 -> bn2, + shortcut,

@@ -7,7 +7,7 @@ replace, on one GPU in one process:
   stage 3  gud_up_proj_layer3  Gudi_UpProj_Block_Cat   512 -> 2 x 256    29 x 38 -> 57 x 76
   stage 4  gud_up_proj_layer4  Gudi_UpProj_Block_Cat   256 -> 2 x 64     57 x 76 -> 114 x 152
 
-    python tools/decoder_bench.py {upconv,uphalf,uptail} [--iters 40] [--warmup 5] [--stages 1,2,3,4] [--out profiles/NAME.json]
+    python tools/decoder_bench.py {upconv,uphalf,upsplit,uptail} [--iters 40] [--warmup 5] [--stages 1,2,3,4] [--out profiles/NAME.json]
 
 upconv, the fp32 head (include/cspn_upconv.h):
   fused       network.up_pooling.up_pooling_conv5x5 on a pack made once: both outputs in one kernel
@@ -16,6 +16,12 @@ uphalf, the fp16 head (include/cspn_uphalf.h):
   half        up_pooling_conv5x5 on a half x and a pack of dtype fp16 made once
   stock_half  the stock sub-graph on the modules of ``block.half()``, as model.half() runs it
   fused_fp32  the fp32 kernel on the same values in fp32: what `fused_decoder` gives without the half kernel
+upsplit, the fp32 head with split products (include/cspn_upconv.h, CSPN_UPCONV_F32_BF16X3):
+  split       up_pooling_conv5x5(..., precision="bf16x3") on the fp32 x and the fp32 pack of `fused`
+  fused       the exact fp32 head on the same pack: what it has to be ahead of
+  stock       the stock fp32 sub-graph, as under upconv
+  The matrix floor is the split's own: 6 x 25 C (O1 + O2) B H W multiply-adds at the bf16 peak (2.5 PFLOP/s).  Before anything is
+  timed the split must agree with the exact head to 1e-5 of the largest element; the figure is recorded.
 uptail, the 3x3 tail in fp32 and in fp16 (include/cspn_uptail.h), over O channels at the stage's output size:
   fused       network.up_pooling.conv3x3_bn_act per convolution on packs made once: conv2 alone at stage 1 (one launch), conv1_1 over
               2 O channels and conv2 at the others (two launches), no ``cat``
@@ -45,6 +51,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 HBM_PEAK = 8e12
 MATRIX_PEAK_FLOPS = {"float32": 157.3e12, "float16": 2.5e15}
+PEAK_FLOPS = dict(MATRIX_PEAK_FLOPS, bfloat16=2.5e15)      # ... and the bf16 matrix cores the split products of upsplit run on
 ROUNDS = 4
 BATCH = 24
 STAGES = {1: ("gud_up_proj_layer1", 2048, 1024, (8, 10), (15, 19)), 2: ("gud_up_proj_layer2", 1024, 512, (15, 19), (29, 38)),
@@ -193,10 +200,32 @@ def uphalf_cases(s, r, dev, note):
     yield (r, name, variants) + counted(r, pack16, 2) + ("float16",)
 
 
+def upsplit_cases(s, r, dev, note):
+    name, block, x, counted, stock, fused = head(s, dev)
+    _, _, _, _, (oh, ow) = STAGES[s]
+    pack = up.pack_upconv5x5((block.conv1.weight, block.sc_conv1.weight), (block.bn1, block.sc_bn1))      # one pack for both precisions
+
+    def split():
+        with torch.no_grad():
+            return list(up.up_pooling_conv5x5(x, pack, oh, ow, precision="bf16x3"))
+
+    variants = dict(split=split, fused=lambda: fused(x, pack), stock=lambda: stock(block, x))
+    got, exact, want = (fn() for fn in variants.values())
+    agree, agree_stock, exact_stock = ([off(p, q) for p, q in zip(*pair)] for pair in ((got, exact), (got, want), (exact, want)))
+    assert max(agree) <= 1e-5 and max(agree_stock) <= 1e-4, (name, agree, agree_stock)
+    note("%s: bf16x3 against the exact fused head, largest difference over largest element: %s; against stock: bf16x3 %s, exact %s"
+         % (name, " ".join("%.2e" % v for v in agree), " ".join("%.2e" % v for v in agree_stock), " ".join("%.2e" % v for v in exact_stock)))
+    del got, exact, want
+    r.update(split_vs_fused_max_diff_over_max=agree, split_vs_stock_max_diff_over_max=agree_stock, fused_vs_stock_max_diff_over_max=exact_stock)
+    flops, nbytes = counted(r, pack, 4)
+    r["split_flops"] = 6 * flops                                          # six bf16 products per fp32 one
+    yield r, name, variants, r["split_flops"], nbytes, "bfloat16"
+
+
 def head_line(kernel, key):
     def line(results):
         return {"dtype": key, kernel + "_ahead": [n for n, r in results.items() if r[kernel + "_ahead"]],
-                "matrix_peak_flops_per_s": MATRIX_PEAK_FLOPS[key]}
+                "matrix_peak_flops_per_s": PEAK_FLOPS[key]}
     return line
 
 
@@ -250,7 +279,7 @@ def uptail_line(results):
 
 # cases, the family's keys of the line, whether a case records which floor binds
 FAMILIES = {"upconv": (upconv_cases, head_line("fused", "float32"), False), "uphalf": (uphalf_cases, head_line("half", "float16"), True),
-            "uptail": (uptail_cases, uptail_line, True)}
+            "uptail": (uptail_cases, uptail_line, True), "upsplit": (upsplit_cases, head_line("split", "bfloat16"), True)}
 
 
 def main():
@@ -285,7 +314,7 @@ def main():
         r = results[STAGES[s][0]] = {}
         for d, label, variants, flops, nbytes, key in cases(s, r, dev, note):
             times = replay_times(variants, a.iters, a.warmup, flush)
-            matrix_floor_us, hbm_floor_us = flops / MATRIX_PEAK_FLOPS[key] * 1e6, nbytes / HBM_PEAK * 1e6
+            matrix_floor_us, hbm_floor_us = flops / PEAK_FLOPS[key] * 1e6, nbytes / HBM_PEAK * 1e6
             d.update(matrix_floor_us=round(matrix_floor_us, 2), hbm_floor_us=round(hbm_floor_us, 2))
             if floor_bound:
                 d["floor_bound"] = "matrix" if matrix_floor_us > hbm_floor_us else "hbm"

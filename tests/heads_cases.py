@@ -39,6 +39,45 @@ GOLDEN_CASES = {
 }
 
 
+# The tiling constants of csrc/cspn_heads.hip, restated: a weight-gradient workgroup takes one 64-pixel segment of a compact row at a
+# time and 64 channels (its grid is capped at 1024 workgroups, each walking segments s, s + 1024, ...), the input gradient holds 32
+# channels per pass, and the kernels exist for 1 .. 16 flat output channels.
+GW_PX, GW_CB, GX_CB, GW_MAX_GROUPS, MAX_OUT = 64, 64, 32, 1024, 16
+
+
+def segments(N, oh, ow):
+    """Row segments of the weight gradient: frames x compact rows that take part x 64-pixel pieces of such a row."""
+    return N * ((oh + 1) // 2) * -(-((ow + 1) // 2) // GW_PX)
+
+
+def _coverage_cases():
+    """name -> ((N, C, H, W), (oh, ow), heads): integer-valued cases named for the branch of the kernels each is there for."""
+    rows = {}
+    # every instantiation of heads_fwd / heads_gx / heads_gw (a workgroup of 16 OT threads): two width segments (64 + 6), two channel
+    # blocks (64 + 1), three 32-channel passes of gx with one channel in the last, odd ow
+    for ot in range(1, MAX_OUT + 1):
+        rows["ot%d" % ot] = ((1, 65, 2, 70), (3, 139), (ot,))
+    # several heads flattened to OT = 3, 10, 11, 14, 15: the frame strides of the heads differ
+    for heads in ((2, 1), (3, 4, 3), (5, 6), (2, 3, 5, 4), (7, 8)):
+        rows["split_" + "x".join(map(str, heads))] = ((2, 5, 4, 6), (7, 11), heads)
+    # ragged and exact ends of the 32- and 64-channel blocks
+    for C in (31, 32, 33, 63, 65, 97, 128, 130):
+        rows["c%d" % C] = ((2, C, 3, 5), (5, 9), (1, 8))
+    # a last segment of 63, 64 and 1 pixels, `left` of a later segment from real data, even and odd ow
+    for Wc in (63, 64, 65, 128, 129):
+        rows["w%d_even" % Wc] = ((1, 3, 2, Wc), (4, 2 * Wc), (1, 4))
+        rows["w%d_odd" % Wc] = ((1, 3, 2, Wc), (3, 2 * Wc - 1), (1, 4))
+    # more segments than workgroups: workgroups with 3 and with 2 trips, crossing frames; and with two segments per row, where only
+    # workgroups 0 .. 15 take a second trip
+    rows["segs_2560"] = ((5, 3, 512, 2), (1023, 3), (1, 8))
+    rows["segs_1040_w65"] = ((2, 3, 260, 65), (519, 130), (3,))
+    return rows
+
+
+COVERAGE_CASES = _coverage_cases()
+SPLIT_TOTALS = (3, 10, 11, 14, 15)
+
+
 def make_inputs(seed, shape, out_hw, heads, integer):
     """x, weights, output gradients as fp32 arrays (what the device gets); a fixed function of its arguments."""
     rng = np.random.RandomState(seed)

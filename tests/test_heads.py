@@ -14,8 +14,9 @@ import pytest
 import torch
 
 import heads_cases as hc
-from conftest import ROOT, golden_names, load_golden
+from conftest import ROOT, golden_names, lds_poison, load_golden
 from cspn_monodepth_amd import _lib
+from cspn_monodepth_amd._host import launch
 from cspn_monodepth_amd.network import unet_cspn_nyu, unet_ours
 from cspn_monodepth_amd.network.up_pooling import up_pooling, up_pooling_conv3x3
 
@@ -176,6 +177,52 @@ def test_heads_family_contract():
     assert not lib.cspn_heads_backward_weights(8, one, one, o1, 1, None, 1, 1, 2, 2, 4, 4, None) and b"null" in lib.cspn_last_error()
 
 
+def test_coverage_table_reaches_what_it_names():
+    """heads_cases.COVERAGE_CASES from the formulas alone: every row has the property it is named for, the library's workspace
+    agrees on the cap of the weight gradient's grid, and every row keeps the precondition of a bit-for-bit comparison."""
+    cases = hc.COVERAGE_CASES
+    assert (hc.GW_PX, hc.GW_CB, hc.GX_CB, hc.GW_MAX_GROUPS, hc.MAX_OUT) == (64, 64, 32, 1024, 16) and hc.MAX_OUT == _lib.HEADS_MAX_OUT_CHANNELS
+    group = lambda stem: {k: v for k, v in cases.items() if re.fullmatch(stem, k)}          # noqa: E731
+    ot, split, chan, width, segs = group(r"ot\d+"), group(r"split_.*"), group(r"c\d+"), group(r"w\d+_(even|odd)"), group(r"segs_.*")
+    assert len(ot) + len(split) + len(chan) + len(width) + len(segs) == len(cases) == 16 + 5 + 8 + 10 + 2
+    # every instantiation exactly once, as one head; the split rows flatten several heads to the totals named
+    assert sorted(sum(v[2]) for v in ot.values()) == list(range(1, 17)) and all(len(v[2]) == 1 and k == "ot%d" % v[2][0] for k, v in ot.items())
+    assert tuple(sum(v[2]) for v in split.values()) == hc.SPLIT_TOTALS and all(len(v[2]) > 1 for v in split.values())
+    assert len({v[2][0] for v in split.values()}) > 1                         # the first head's frame stride differs from row to row
+    for (N, C, H, W), (oh, ow), heads in ot.values():
+        Wc = (ow + 1) // 2
+        assert Wc > hc.GW_PX and Wc % hc.GW_PX == 6 and ow % 2 == 1           # two width segments, 64 + 6; the scalar stores
+        assert C // hc.GW_CB == 1 and C % hc.GW_CB == 1                       # two channel blocks, 64 + 1
+        assert -(-C // hc.GX_CB) == 3 and C % hc.GX_CB == 1                   # three passes of gx, one channel in the last
+    # the segments: two rows above the cap, with workgroups of different trip counts; every other row below it
+    for name, ((N, C, H, W), (oh, ow), heads) in cases.items():
+        n = hc.segments(N, oh, ow)
+        assert (n == {"segs_2560": 2560, "segs_1040_w65": 1040}[name]) if name in segs else n < hc.GW_MAX_GROUPS, name
+    assert 2 * hc.GW_MAX_GROUPS < 2560 < 3 * hc.GW_MAX_GROUPS                 # workgroups with 3 and with 2 trips ...
+    assert hc.segments(1, *segs["segs_2560"][1]) == 512 < hc.GW_MAX_GROUPS    # ... a frame has 512: every trip lies two frames on
+    assert 1040 - hc.GW_MAX_GROUPS == 16 and (segs["segs_1040_w65"][1][1] + 1) // 2 == 65     # only workgroups 0 .. 15 come back; nJ = 2
+    # ragged and exact ends of the channel blocks
+    assert [v[0][1] % hc.GX_CB for v in chan.values()] == [31, 0, 1, 31, 1, 1, 0, 2]
+    assert [v[0][1] % hc.GW_CB for v in chan.values()] == [31, 32, 33, 63, 1, 33, 0, 2]
+    assert [v[0][1] // hc.GW_CB for v in chan.values()] == [0, 0, 0, 0, 1, 1, 2, 2]
+    # the last width segment: 63, 64 (exact), 1, 64 (exact, the second), 1 (the third), each with even and odd ow
+    for name, ((N, C, H, W), (oh, ow), heads) in width.items():
+        Wc = (ow + 1) // 2
+        assert name == "w%d_%s" % (Wc, "odd" if ow % 2 else "even") and W == Wc
+    assert sorted({((v[1][1] + 1) // 2) % hc.GW_PX for v in width.values()}) == [0, 1, 63]
+    assert sorted({-(-((v[1][1] + 1) // 2) // hc.GW_PX) for v in width.values()}) == [1, 2, 3]
+    # the library's own count of partial sums, through the entry point that needs no device
+    ws = _lib.lib().cspn_heads_workspace_bytes
+    for name, (shape, (oh, ow), heads) in cases.items():
+        assert ws(_lib.HEADS_BACKWARD_WEIGHTS, sum(heads), *shape, oh, ow) == \
+            min(hc.segments(shape[0], oh, ow), hc.GW_MAX_GROUPS) * sum(heads) * shape[1] * 9 * 4, name
+    # the precondition of the bit-for-bit comparison: every sum is an integer below 2^24, and no result is identically zero
+    for name, key in cases.items():
+        x, ws_, gys, ys_w, gx_w, gws_w = restated(*key)
+        for a in ys_w + [gx_w] + gws_w:
+            assert 0 < np.abs(a).max() < 2 ** 24 and np.array_equal(a, np.rint(a)), name
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # GPU
 # ------------------------------------------------------------------------------------------------------------------------
@@ -228,6 +275,121 @@ def test_integer_cases_bit_equal_to_the_restatement(shape, out_hw, heads):
     ys, gx, gws = run(x, ws, gys, *out_hw)
     for got, want in zip(ys + [gx] + gws, ys_w + [gx_w] + gws_w):
         assert same_bits(got, want + 0.0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(hc.COVERAGE_CASES))
+def test_coverage_cases_bit_equal_to_the_restatement(name):
+    """Every instantiation (OT = 1 .. 16), ragged channel blocks, later width segments and several trips of the weight gradient's
+    segment loop (heads_cases.COVERAGE_CASES; the CPU test above holds each row to what it is named for)."""
+    shape, out_hw, heads = hc.COVERAGE_CASES[name]
+    x, ws, gys, ys_w, gx_w, gws_w = restated(shape, out_hw, heads)
+    assert max(np.abs(a).max() for a in ys_w + [gx_w] + gws_w) < 2 ** 24
+    ys, gx, gws = run(x, ws, gys, *out_hw)
+    for what, got, want in zip(["y"] * len(ys) + ["gx"] + ["gw"] * len(gws), ys + [gx] + gws, ys_w + [gx_w] + gws_w):
+        assert same_bits(got, want + 0.0), (name, what)
+    if name.startswith("segs_"):                             # the finish adds the partial sums in a fixed order: the same bits again
+        again = run(x, ws, gys, *out_hw)
+        assert all(torch.equal(a, b) for a, b in zip(ys + [gx] + gws, again[0] + [again[1]] + again[2]))
+
+
+@pytest.mark.gpu
+def test_real_case_over_several_trips_within_the_a_priori_bound():
+    """segs_2560 on real values: a workgroup of the weight gradient adds two or three segments into its accumulators, and the finish
+    adds 1024 partial sums in sixteen chains of 64.  The bound is the file's own, n * 2^-24 * A with A the restatement on absolute
+    values; n = N H W = 5120 for a weight gradient."""
+    shape, (oh, ow), heads = hc.COVERAGE_CASES["segs_2560"]
+    x, ws, gys = hc.make_inputs(81, shape, (oh, ow), heads, False)
+    want = hc.restate(x, ws, gys, oh, ow)
+    ays, agx, agws = hc.restate(np.abs(x), [np.abs(w) for w in ws], [np.abs(g) for g in gys], oh, ow)
+    by = [hc.terms_forward(shape[1]) * hc.U * a for a in ays]
+    bgx = hc.terms_grad_x(heads) * hc.U * agx
+    bgw = [hc.terms_grad_w(shape) * hc.U * a for a in agws]
+    assert hc.terms_grad_w(shape) == 5120 and hc.segments(shape[0], oh, ow) == 2560
+    ys, gx, gws = run(x, ws, gys, oh, ow)
+    ratios = []
+    for what, got, w, bound in zip(["y"] * len(ys) + ["gx"] + ["gw"] * len(gws), ys + [gx] + gws, want[0] + [want[1]] + want[2], by + [bgx] + bgw):
+        err = np.abs(got.cpu().numpy().astype(np.float64) - w)
+        ratios.append((what, float((err[bound > 0] / bound[bound > 0]).max())))
+        print("segs_2560 real %s: error / bound = %.3g" % ratios[-1])
+        assert (err <= bound).all(), ratios
+    assert all(r > 0 for _, r in ratios)                    # fp32 results, not a copy of the fp64 ones
+
+
+def carve(buf, sizes, pad, align=4):
+    """Views of `sizes` elements inside `buf`, `pad` elements apart and from both ends, each starting on a multiple of `align`
+    elements (16 bytes of fp32, as an allocation does); and the mask of the elements of buf that belong to no view."""
+    views, keep, at = [], torch.ones_like(buf, dtype=torch.bool), pad
+    for s in sizes:
+        views.append(buf[at:at + s])
+        keep[at:at + s] = False
+        at += -(-s // align) * align + pad
+    assert at <= buf.numel()
+    return views, keep
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["ot7", "c65", "w65_odd", "w64_even", "segs_2560", "deep_crop"])
+def test_nothing_outside_outputs_gradients_and_workspace_is_written(name):
+    """The three entry points called directly: outputs, gx, every gw and the three workspaces (each exactly as long as
+    cspn_heads_workspace_bytes says) are views inside one buffer of sentinels.  For the deep crop (2, 3, 6, 7) -> (4, 5), NaN in the
+    compact pixels that take no part changes nothing in the outputs and the weight gradients, and the input gradient is exactly 0
+    there."""
+    shape, (oh, ow), heads = hc.COVERAGE_CASES[name] if name != "deep_crop" else ((2, 3, 6, 7), (4, 5), (1, 8))
+    N, C, H, W = shape
+    x, ws, gys, *_ = restated(shape, (oh, ow), heads)
+    want = run(x, ws, gys, oh, ow)
+    lib, total = _lib.lib(), sum(heads)
+    work = [lib.cspn_heads_workspace_bytes(p, total, N, C, H, W, oh, ow) for p in (_lib.HEADS_FORWARD, _lib.HEADS_BACKWARD_INPUT,
+                                                                                   _lib.HEADS_BACKWARD_WEIGHTS)]
+    assert all(b > 0 and b % 4 == 0 for b in work)
+    assert work[2] == min(hc.segments(N, oh, ow), hc.GW_MAX_GROUPS) * total * C * 9 * 4
+    pad, sentinel = 4096, -12345.0
+    sizes = [N * o * oh * ow for o in heads] + [N * C * H * W] + [o * C * 9 for o in heads] + [b // 4 for b in work]
+    buf = torch.full((pad + sum(-(-s // 4) * 4 + pad for s in sizes),), sentinel, device=DEV)
+    views, keep = carve(buf, sizes, pad)
+    nh = len(heads)
+    ys = [v.view(N, o, oh, ow) for v, o in zip(views[:nh], heads)]
+    gx = views[nh].view(shape)
+    gws = [v.view(o, C, 3, 3) for v, o in zip(views[nh + 1:2 * nh + 1], heads)]
+    wf, wx, ww = views[2 * nh + 1:]
+    assert all(v.data_ptr() % 16 == 0 for v in views) and ow % 2 == (name != "w64_even")      # the float2 stores at w64_even alone
+    xd, wd, gd = dev(x), [dev(w) for w in ws], [dev(g) for g in gys]
+    ptrs = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])                # noqa: E731
+    oc = (ctypes.c_int * nh)(*heads)
+    device = torch.device(DEV)
+    launch(device, "cspn_heads_forward", xd.data_ptr(), ptrs(wd), ptrs(ys), oc, nh, wf.data_ptr(), N, C, H, W, oh, ow)
+    launch(device, "cspn_heads_backward_input", ptrs(gd), ptrs(wd), oc, nh, gx.data_ptr(), wx.data_ptr(), N, C, H, W, oh, ow)
+    launch(device, "cspn_heads_backward_weights", xd.data_ptr(), ptrs(gd), ptrs(gws), oc, nh, ww.data_ptr(), N, C, H, W, oh, ow)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(ys + [gx] + gws, want[0] + [want[1]] + want[2]))
+    assert int(keep.sum()) >= pad * (len(sizes) + 1) and bool((buf[keep] == sentinel).all())
+    assert not any(bool((v == sentinel).any()) for v in (wf, wx, ww))      # the packed filters and every partial sum were written
+    if name != "deep_crop":
+        return
+    xn = x.copy()
+    xn[:, :, (oh + 1) // 2:, :] = np.nan
+    xn[:, :, :, (ow + 1) // 2:] = np.nan
+    assert np.isnan(xn).sum() == 2 * 3 * (6 * 7 - 2 * 3)
+    ys, gx, gws = run(xn, ws, gys, oh, ow)
+    assert all(torch.equal(a, b) for a, b in zip(ys + [gx] + gws, want[0] + [want[1]] + want[2]))
+    removed = torch.from_numpy(np.isnan(xn)).to(DEV)
+    assert bool((gx[removed] == 0).all()) and bool((gx[~removed] != 0).any())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["ot3", "ot16", "c65", "w65_odd", "w65_even", "segs_1040_w65"])
+def test_ragged_tiles_under_poisoned_lds(name):
+    """heads_gw zero-fills the ragged ends of its two LDS tiles itself: with NaN in the whole LDS of every CU in front of every
+    launch, the bits of the plain run."""
+    shape, out_hw, heads = hc.COVERAGE_CASES[name]
+    x, ws, gys, *_ = restated(shape, out_hw, heads)
+    plain = run(x, ws, gys, *out_hw)
+    with lds_poison():
+        ys, gx, gws = run(x, ws, gys, *out_hw)
+        torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(ys + [gx] + gws, plain[0] + [plain[1]] + plain[2]))
+    assert not any(bool(torch.isnan(t).any()) for t in ys + [gx] + gws)
 
 
 @pytest.mark.gpu

@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import upconv_cases as uc
-from conftest import ROOT, golden_names, load_golden
+from conftest import ROOT, golden_names, lds_poison, load_golden
 from cspn_monodepth_amd import _lib
 from cspn_monodepth_amd._host import launch
 from cspn_monodepth_amd.network import unet_cspn_nyu, unet_ours
@@ -79,6 +79,25 @@ def test_restatement_equals_the_dense_form(hw, out_hw):
         dense = dense * scale.astype(np.float64)[None, :, None, None] + shift.astype(np.float64)[None, :, None, None]
         dense[:, :relu] = np.maximum(dense[:, :relu], 0)
         assert np.array_equal(np.concatenate(got, 1) + 0.0, dense + 0.0)
+
+
+def test_m_tile_table_reaches_what_it_names():
+    """upconv_cases.M_TILE_FILTER_SETS from the sizes alone, and the exactness precondition of every case of the three precisions'
+    test_integer_cases_over_several_m_tiles (fp32 sums below 2^24; results inside the fp16 range for the half family)."""
+    tiles = [-(-sum(f) // 128) for f in uc.M_TILE_FILTER_SETS]
+    assert tiles == [2, 2, 3, 2] and all(sum(f) > max(sum(g) for g in uc.FILTER_SETS + (uc.BIG["filters"],)) for f in uc.M_TILE_FILTER_SETS)
+    (a, _), (b, c), (d, e), (f, g) = uc.M_TILE_FILTER_SETS
+    assert a - 128 == 1                                                      # one live row in tile 1
+    assert 128 < b < b + c < 256                                             # the filter and ReLU boundary, and the end, inside tile 1
+    assert d == 128 and 256 < d + e                                          # the boundary on the tile edge, a third tile
+    assert f < 128 < f + g                                                   # the boundary in tile 0, live rows in tile 1
+    cases = list(uc.m_tile_shapes())
+    assert len(cases) == 16 and uc.M_TILE_POISON_CASE in cases and {s[1] for s, _, _ in cases} == {3, 33}
+    for shape, out_hw, filters in cases:
+        x, ws, scale, shift = uc.make_inputs(uc.case_seed(shape, out_hw, filters), shape, filters, True)
+        acc = uc.accumulate(np.abs(x.astype(np.float64)), [np.abs(w.astype(np.float64)) for w in ws], *out_hw)
+        assert 0 < 4 * acc.max() + 5 < 65504 < 2 ** 24
+        assert all(np.array_equal(t.astype(np.float16).astype(np.float32), t) for t in [x] + ws)
 
 
 def test_refusals():
@@ -302,6 +321,25 @@ def test_integer_case_over_several_chunks_and_tiles():
     shape, out_hw, filters = uc.BIG["shape"], uc.BIG["out_hw"], uc.BIG["filters"]
     assert shape[1] > 32 and all(shape[0] * ((out_hw[0] + 1 - a) // 2) * ((out_hw[1] + 1 - b) // 2) > 128 for a, b in uc.PHASES)
     integer_case(shape, out_hw, filters)
+
+
+@pytest.mark.gpu
+def test_integer_cases_over_several_m_tiles():
+    """mt > 0 in fwd<F32>: the filter tile's offset, the tap stride with Mp > 128, the m >= M cut, the y0 / y1 switch and the ReLU
+    boundary in a tile that is not the first (upconv_cases.M_TILE_FILTER_SETS says what each row is there for)."""
+    for shape, out_hw, filters in uc.m_tile_shapes():
+        integer_case(shape, out_hw, filters)
+
+
+@pytest.mark.gpu
+def test_ragged_m_tile_under_poisoned_lds():
+    shape, out_hw, filters = uc.M_TILE_POISON_CASE
+    x, ws, scale, shift = uc.make_inputs(uc.case_seed(shape, out_hw, filters), shape, filters, True)
+    plain = run(x, ws, *out_hw, scale, shift, filters[0])
+    with lds_poison():
+        got = run(x, ws, *out_hw, scale, shift, filters[0])
+        torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(got, plain)) and not any(bool(torch.isnan(g).any()) for g in got)
 
 
 @pytest.mark.gpu

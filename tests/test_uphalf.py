@@ -17,7 +17,7 @@ import torch
 
 import upconv_cases as uc
 import uphalf_cases as hc
-from conftest import ROOT, golden_names, load_golden
+from conftest import ROOT, golden_names, lds_poison, load_golden
 from cspn_monodepth_amd import _lib
 from cspn_monodepth_amd._host import launch
 from cspn_monodepth_amd.network import unet_cspn_nyu, unet_ours
@@ -275,6 +275,27 @@ def test_integer_case_over_several_chunks_and_tiles():
     shape, out_hw, filters = uc.BIG["shape"], uc.BIG["out_hw"], uc.BIG["filters"]
     assert shape[1] > 32 and all(shape[0] * ((out_hw[0] + 1 - a) // 2) * ((out_hw[1] + 1 - b) // 2) > 128 for a, b in uc.PHASES)
     integer_case(shape, out_hw, filters)
+
+
+@pytest.mark.gpu
+def test_integer_cases_over_several_m_tiles():
+    """mt > 0 in fwd<F16>, whose filter tile is found by a row index times Cp: upconv_cases.M_TILE_FILTER_SETS, bit for bit
+    (tests/test_upconv.py holds every case inside the fp16 range without a GPU)."""
+    for shape, out_hw, filters in uc.m_tile_shapes():
+        assert 4 * hc.integer_case(shape, out_hw, filters)[4] + 5 < hc.HALF_MAX
+        integer_case(shape, out_hw, filters)
+
+
+@pytest.mark.gpu
+def test_ragged_m_tile_under_poisoned_lds():
+    shape, out_hw, filters = uc.M_TILE_POISON_CASE
+    x, ws, scale, shift, _ = hc.integer_case(shape, out_hw, filters)
+    pack = packed_for(ws, torch.float32)
+    plain = run(x, pack, *out_hw, scale, shift, filters[0])
+    with lds_poison(0x7fc07fc0):                                             # NaN in both fp16 halves of every word
+        got = run(x, pack, *out_hw, scale, shift, filters[0])
+        torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(got, plain)) and not any(bool(torch.isnan(g).any()) for g in got)
 
 
 @pytest.mark.gpu

@@ -19,7 +19,7 @@ import torch
 
 import upconv_cases as uc
 import upsplit_cases as us
-from conftest import ROOT
+from conftest import ROOT, lds_poison
 from cspn_monodepth_amd import _host, _lib
 from cspn_monodepth_amd._host import launch
 from cspn_monodepth_amd.network import unet_cspn_nyu, unet_ours
@@ -167,6 +167,24 @@ def test_integer_cases_bit_equal_to_the_restatement(hw, out_hw):
 @pytest.mark.gpu
 def test_integer_case_over_several_chunks_and_tiles():
     integer_case(uc.BIG["shape"], uc.BIG["out_hw"], uc.BIG["filters"])
+
+
+@pytest.mark.gpu
+def test_integer_cases_over_several_m_tiles():
+    """mt > 0 in fwd<F32X3>, whose filter tile is found two flat channels per thread: upconv_cases.M_TILE_FILTER_SETS, bit for bit."""
+    for shape, out_hw, filters in uc.m_tile_shapes():
+        integer_case(shape, out_hw, filters)
+
+
+@pytest.mark.gpu
+def test_ragged_m_tile_under_poisoned_lds():
+    shape, out_hw, filters = uc.M_TILE_POISON_CASE
+    x, ws, scale, shift = uc.make_inputs(uc.case_seed(shape, out_hw, filters), shape, filters, True)
+    plain = run(x, ws, *out_hw, scale, shift, filters[0])
+    with lds_poison(0x7fc07fc0):                                             # NaN in both bf16 halves of every word
+        got = run(x, ws, *out_hw, scale, shift, filters[0])
+        torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(got, plain)) and not any(bool(torch.isnan(g).any()) for g in got)
 
 
 def dyadic_case(kind, seed, shape, out_hw, filters, live=None):

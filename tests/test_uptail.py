@@ -16,7 +16,7 @@ import pytest
 import torch
 
 import uptail_cases as tc
-from conftest import ROOT, golden_names, load_golden
+from conftest import ROOT, golden_names, lds_poison, load_golden
 from cspn_monodepth_amd import _lib
 from cspn_monodepth_amd._host import launch
 from cspn_monodepth_amd.network import unet_cspn_nyu, unet_ours
@@ -471,6 +471,21 @@ def test_nothing_outside_the_output_is_written(channels, O, shape):
         torch.cuda.synchronize()
         assert torch.equal(out, want)
         assert bool((buf[:pad] == sentinel).all()) and bool((buf[pad + size:] == sentinel).all())
+
+
+@pytest.mark.gpu
+def test_ragged_case_under_poisoned_lds():
+    """The ragged case above — two maps of 33 and 40 channels, a second M tile with one live row — with NaN in the whole LDS of
+    every CU in front of every launch: the bits of the plain run, in both precisions."""
+    channels, O, shape = (33, 40), 129, (3, 7, 9)
+    a, b, w, scale, shift, r = tc.make_inputs(channels, O, shape, True)
+    for dtype, pattern in ((torch.float32, 0x7fc00000), (torch.float16, 0x7fc07fc0)):      # NaN as fp32, and in both fp16 halves
+        pack = packed_for(w, torch.float32, dtype, channels[0])
+        plain = run(pack, a, b, scale, shift, r)
+        with lds_poison(pattern):
+            got = run(pack, a, b, scale, shift, r)
+            torch.cuda.synchronize()
+        assert torch.equal(got, plain) and not bool(torch.isnan(got).any())
 
 
 @pytest.mark.gpu

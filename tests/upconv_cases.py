@@ -27,6 +27,27 @@ BATCHES = (1, 3)
 # K spans several LDS chunks of 32 channels per tap, and the pixels of every phase span several tiles of 128
 BIG = dict(shape=(2, 40, 9, 11), out_hw=(18, 22), filters=(40, 40))
 
+# More than one 128-row tile of flat output channels (mt > 0 in fwd<P>; every case above has at most 80): a second tile with one live
+# row; the filter boundary and the ReLU boundary inside tile 1; the boundary on the tile edge, and three tiles; the boundary in tile 0
+# with live rows in tile 1.  Run at C = 3 and 33 (one chunk, and a second one partly filled), B = 2, bit for bit, by the three
+# precisions' test_integer_cases_over_several_m_tiles.
+M_TILE_FILTER_SETS = ((129, 0), (130, 31), (128, 129), (100, 60))
+M_TILE_GEOMETRIES = (((3, 4), (6, 8)), ((5, 7), (9, 13)))
+M_TILE_CHANNELS = (3, 33)
+M_TILE_BATCH = 2
+
+
+def m_tile_shapes():
+    """shape, out_hw, filters of every case over several M tiles."""
+    for hw, out_hw in M_TILE_GEOMETRIES:
+        for C in M_TILE_CHANNELS:
+            for both in M_TILE_FILTER_SETS:
+                yield (M_TILE_BATCH, C) + hw, out_hw, filters_of(both)
+
+
+# the case the poisoned-LDS runs take: ragged in M (130 + 31 = 161 = 128 + 33), in K (33 = 32 + 1) and in the pixels of every phase
+M_TILE_POISON_CASE = ((M_TILE_BATCH, 33, 5, 7), (9, 13), (130, 31))
+
 # The integer-valued test runs the whole product of the four lists (a test per geometry), and BIG.
 # The real-valued cases that are no golden: the odd crop at C = 67 (three 32-channel chunks per tap, the last one partly filled)
 # with two filters, the widest single filter, and the big one.

@@ -215,19 +215,31 @@ def _families():
             "cspn_uptail_packed_bytes": (cs, [ci, ci, ci, ci]),
             "cspn_uptail_pack": [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp],
             "cspn_uptail_forward": [vp, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp]}, opt_in=True),
+    ), (
+        family("convbn", "cspn_convbn.h", 1, {"cspn_convbn.hip": False}, {
+            "cspn_convbn_abi_version": None,
+            "cspn_convbn_packed_bytes": (cs, [ci, ci, ci, ci]),
+            "cspn_convbn_pack": [vp, ci, ci, ci, ci, ci, ci, vp, vp],
+            "cspn_convbn_forward": [vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]}, opt_in=True),
     )
 
 
 # A family with `opt_in` set sits behind a switch of the models that is off by default (`fused_heads`, `fused_decoder`, `fused_tail`,
 # network/up_pooling.py); the others are what a default call of the package can reach.  All are built, declared and version-checked
 # alike, and no file of an opt-in family is part of code_digest().
-ALL_FAMILIES = _families()
+#
+# LATER_FAMILIES is a further part of the table: opt-in families added after those thirteen, which the older tests count and whose
+# tuples and digests they restate (convbn: `fused_encoder`, network/conv_bn.py).  They are built, declared and version-checked as
+# the opt-in ones and found by family(); their sources and headers are LATER_SOURCES / LATER_HEADERS, part of the build's staleness
+# stamp (_later_digest) and of no tuple or digest above.
+ALL_FAMILIES, LATER_FAMILIES = _families()
 FAMILIES = tuple(f for f in ALL_FAMILIES if not f.opt_in)
 OPT_IN_FAMILIES = tuple(f for f in ALL_FAMILIES if f.opt_in)
+EVERY_FAMILY = ALL_FAMILIES + LATER_FAMILIES
 
 
 def family(name):
-    return next(f for f in ALL_FAMILIES if f.name == name)
+    return next(f for f in EVERY_FAMILY if f.name == name)
 
 
 def _files(suffix, benchmarked=None, families=FAMILIES):
@@ -241,6 +253,8 @@ HEADERS = tuple(os.path.join(CSRC, f) for f in _files(".hpp", True)) + tuple(f.h
 BUILD_HEADERS = HEADERS + tuple(os.path.join(CSRC, f) for f in _files(".hpp", False, ALL_FAMILIES)) + \
     tuple(f.header for f in ALL_FAMILIES if not any(f.files.values()))
 EXPORTS = tuple(family("core").functions)      # every symbol include/cspn_hip.h declares
+LATER_SOURCES = _files(".hip", families=LATER_FAMILIES)
+LATER_HEADERS = tuple(os.path.join(CSRC, f) for f in _files(".hpp", families=LATER_FAMILIES)) + tuple(f.header for f in LATER_FAMILIES)
 
 
 def _source_digest(flags, code_only=False):
@@ -266,18 +280,28 @@ def code_digest():
     return _source_digest([], code_only=True)
 
 
+def _later_digest(digest):
+    """The build's staleness stamp: `digest` (_source_digest of the flags) carried on over the sources and headers of LATER_FAMILIES."""
+    import hashlib
+    h = hashlib.sha256(digest.encode())
+    for path in [os.path.join(CSRC, f) for f in LATER_SOURCES] + list(LATER_HEADERS):
+        with open(path, "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
 def build(force=False, verbose=False):
     """hipcc cross-compiles for gfx950 without a GPU: the translation units are compiled in parallel to
     csrc/_build/*.o and linked into the in-tree .so (which travels with gpurun snapshots).  Staleness is decided by
     a content hash of the sources + flags stored next to the library (file times do not survive every copy)."""
     from concurrent.futures import ThreadPoolExecutor
-    srcs = [os.path.join(CSRC, f) for f in SOURCES + OPT_IN_SOURCES]
+    srcs = [os.path.join(CSRC, f) for f in SOURCES + OPT_IN_SOURCES + LATER_SOURCES]
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     # -fno-slp-vectorize: the SLP pass pairs the stencil FMAs into v_pk_fma_f32 and pays for it with ~50 v_mov
     # per step to build operand pairs; scalar v_fma_f32 measured 4 % faster (profiles/).  No fast-math: 0/0 = NaN.
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-fno-slp-vectorize"] + \
         os.environ.get("CSPN_HIPCC_FLAGS", "").split() + ["-I", INCLUDE]
-    digest = _source_digest(flags[:-2])
+    digest = _later_digest(_source_digest(flags[:-2]))
     stamp = SO_PATH + ".hash"
     if not force and os.path.exists(SO_PATH) and os.path.exists(stamp) and open(stamp).read().strip() == digest:
         return SO_PATH
@@ -286,7 +310,7 @@ def build(force=False, verbose=False):
 
     import hashlib
     hdr = hashlib.sha256(" ".join(flags[:-2]).encode())
-    for path in BUILD_HEADERS:
+    for path in BUILD_HEADERS + LATER_HEADERS:
         with open(path, "rb") as fh:
             hdr.update(fh.read())
 
@@ -324,7 +348,7 @@ _lock = threading.Lock()
 
 
 def _declare(lib):
-    for fam in ALL_FAMILIES:
+    for fam in EVERY_FAMILY:
         for name, (restype, argtypes) in fam.functions.items():
             fn = getattr(lib, name)
             if restype is not ctypes.c_int:           # ctypes' default
@@ -345,7 +369,7 @@ def lib():
                         "cspn_monodepth_amd: %s is missing — build it with `python -c 'import __graft_entry__ as g; "
                         "g.build()'` (hipcc --offload-arch=gfx950).  There is no CPU fallback." % SO_PATH)
                 _lib = _declare(ctypes.CDLL(SO_PATH))
-                for fam in ALL_FAMILIES:
+                for fam in EVERY_FAMILY:
                     sub = "" if fam.name == "core" else fam.name      # cspn_abi_version, cspn_<family>_abi_version
                     if getattr(_lib, "cspn_%sabi_version" % (sub and sub + "_"))() != fam.abi_version:
                         raise RuntimeError("cspn_monodepth_amd: %sABI version mismatch" % (sub and sub + " "))

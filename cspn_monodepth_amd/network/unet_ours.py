@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from ..post_process import CSPN_ours as post_process
 from .unet_cspn_nyu import DECODER_SIZES_NYU, BasicBlock, Bottleneck, _conv
+from .conv_bn import FusedBridge, select_fused_encoder
 from .up_pooling import MyBlock, select_fused_decoder, select_fused_precision, select_fused_tail, up_pooling_conv3x3
 
 __all__ = ["ResNet", "resnet50", "resnet18", "Bottleneck", "BasicBlock", "UpProj_Block", "Gudi_UpProj_Block",
@@ -99,7 +100,7 @@ class Gudi_UpProj_Block_Cat(MyBlock):                            # unet_ours.py:
         return self.relu(out + self.sc_bn1(self.sc_conv1(x)))
 
 
-class ResNet(nn.Module):
+class ResNet(FusedBridge, nn.Module):
     """unet_ours.py:251-335.  input [B,4,H,W] (RGB + sparse depth) -> [refined depth [B,1,H,W], guidance [B,8,H,W]].
 
     `up_proj_block` is accepted and ignored, as in the reference (:253; it builds no up_proj_layer).  decoder_sizes: the five
@@ -124,11 +125,19 @@ class ResNet(nn.Module):
     fused_decoder_precision (None; never a default): the ``precision`` of ``up_pooling_conv5x5`` for the blocks fused_decoder names, on
     fp32 inputs — None / "exact", or "bf16x3": the products split into bf16 terms on the bf16 matrix cores, fp32-class results with
     other bits (include/cspn_upconv.h).  It selects no block, half inputs ignore it, and train or grad mode run the stock blocks.
-    The three switches together: fused_heads covers gud_up_proj_layer5 / 6, fused_decoder the head and fused_tail the tail of
-    gud_up_proj_layer1 .. 4; each is forward-only, changes no module, parameter or state_dict key, and none changes what another does."""
+    fused_encoder (off by default; independent of the other three): True, or a collection of names out of "layer1" .. "layer4" and
+    "conv2" (the bridge bn2(conv2(x)) between encoder and decoder).  In eval mode with grad mode off and on a fp32 or fp16 input, every
+    residual block of a named stage runs each of its convolutions with its batch norm, and where they follow the shortcut add and the
+    ReLU, as one ``conv_bn_act`` call (network/conv_bn.py, include/cspn_convbn.h), and the bridge runs as one call without a ReLU;
+    anything else runs exactly the default code.  True selects conv_bn.FUSED_ENCODER_DEFAULT (half inputs:
+    FUSED_ENCODER_HALF_DEFAULT), the stages where that was measured to be faster — lists that may be empty; names select those stages
+    in both precisions.  The 7x7 stem and the max-pool stay on stock ops.
+    The four switches together: fused_heads covers gud_up_proj_layer5 / 6, fused_decoder the head and fused_tail the tail of
+    gud_up_proj_layer1 .. 4, fused_encoder layer1 .. 4 and the bridge; each is forward-only, changes no module, parameter or state_dict
+    key, and none changes what another does."""
 
     def __init__(self, block, layers, up_proj_block=None, decoder_sizes=DECODER_SIZES_NYU, prop_time=24, cspn_plan=None,
-                 fused_heads=False, fused_decoder=False, fused_tail=False,
+                 fused_heads=False, fused_decoder=False, fused_tail=False, fused_encoder=False,
                  fused_decoder_precision=None):
         super(ResNet, self).__init__()
         self.inplanes = 64
@@ -156,6 +165,7 @@ class ResNet(nn.Module):
         self.fused_heads = bool(fused_heads)
         self.fused_decoder = select_fused_decoder(self, fused_decoder)
         self.fused_tail = select_fused_tail(self, fused_tail)
+        self.fused_encoder = select_fused_encoder(self, fused_encoder)
         self.fused_decoder_precision = select_fused_precision(self, fused_decoder_precision)
 
     def _make_layer(self, block, planes, blocks, stride=1):
@@ -181,7 +191,7 @@ class ResNet(nn.Module):
         skip3 = x                                                      # 64e ch at H/4 (:316)
         x = self.layer2(x)
         skip2 = x                                                      # 128e ch at H/8 (:319)
-        x = self.bn2(self.conv2(self.layer4(self.layer3(x))))
+        x = self._bridge(self.layer4(self.layer3(x)))
         x = self.gud_up_proj_layer1(x)
         x = self.gud_up_proj_layer2(x, skip2)
         x = self.gud_up_proj_layer3(x, skip3)

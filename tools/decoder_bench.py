@@ -7,7 +7,7 @@ replace, on one GPU in one process:
   stage 3  gud_up_proj_layer3  Gudi_UpProj_Block_Cat   512 -> 2 x 256    29 x 38 -> 57 x 76
   stage 4  gud_up_proj_layer4  Gudi_UpProj_Block_Cat   256 -> 2 x 64     57 x 76 -> 114 x 152
 
-    python tools/decoder_bench.py {upconv,uphalf,upsplit,uptail} [--iters 40] [--warmup 5] [--stages 1,2,3,4] [--out profiles/NAME.json]
+    python tools/decoder_bench.py {upconv,uphalf,upsplit,uptail,encoder} [--iters 40] [--warmup 5] [--stages 1,2,3,4] [--out profiles/NAME.json]
 
 upconv, the fp32 head (include/cspn_upconv.h):
   fused       network.up_pooling.up_pooling_conv5x5 on a pack made once: both outputs in one kernel
@@ -26,6 +26,11 @@ uptail, the 3x3 tail in fp32 and in fp16 (include/cspn_uptail.h), over O channel
   fused       network.up_pooling.conv3x3_bn_act per convolution on packs made once: conv2 alone at stage 1 (one launch), conv1_1 over
               2 O channels and conv2 at the others (two launches), no ``cat``
   stock       ``cat``, conv1_1, bn1_1, ReLU, conv2, bn2, the shortcut add and the ReLU on stock ops (half: of ``block.half()``)
+encoder, the residual stages layer1 .. layer4 (57 x 76 -> 8 x 10) and the bridge bn2(conv2(x)) of the same model in fp32 and in fp16
+(include/cspn_convbn.h), stages 1 .. 5, and as stage 0 the whole of ``features`` (everything below the CSPN module):
+  fused       network.conv_bn.conv_bn_act per convolution on packs made once, as `fused_encoder` runs a stage (stage 0: every stage)
+  stock       the stage on stock ops: MIOpen convolutions, eval batch norms, adds and ReLUs (half: of ``.half()``)
+  The line carries the stages' sums and `encoder_share_of_features`: the stock stages' sum over the stock time of stage 0.
 The stock convolutions run with the package's MIOpen tuning database in place as bench.py puts it (network.conv_tuning).
 
 Method: every variant of a case is captured once in a graph under no_grad and timed as graph replays with HIP events around each
@@ -35,7 +40,7 @@ Infinity Cache holds the inputs.  Before anything is timed the family's kernel m
 largest element (fp32 head 1e-4: fp32 sums of the same terms; fp32 tail 1e-3; fp16 1e-2: a few fp16 roundings on either side); the
 figures are recorded.  `<kernel>_ahead`: the 90th percentile of the family's kernel (the first variant) is below the 10th percentile
 of the stock path (the second), warm and cold — the one rule behind up_pooling.FUSED_DECODER_DEFAULT, FUSED_DECODER_HALF_DEFAULT,
-FUSED_TAIL_DEFAULT and FUSED_TAIL_HALF_DEFAULT.  Beside the kernel's times the floors counted from the shapes: its multiply-adds (head:
+FUSED_TAIL_DEFAULT, FUSED_TAIL_HALF_DEFAULT and conv_bn.FUSED_ENCODER_DEFAULT / FUSED_ENCODER_HALF_DEFAULT.  Beside the kernel's times the floors counted from the shapes: its multiply-adds (head:
 25 C (O1 + O2) B H W, tail: 9 Cin O B H W per convolution) at the dense matrix peak of the precision (fp32 157.3 TFLOP/s, the vector
 peak as well; fp16 2.5 PFLOP/s), and every operand, the packed filters, the tail's intermediate (written and read) and the results
 moved once at the 8 TB/s HBM peak.  Prints one JSON line, with the keys and the `tool` name (`<family>_bench`) of the recorded
@@ -277,9 +282,141 @@ def uptail_line(results):
                 matrix_peak_flops_per_s=MATRIX_PEAK_FLOPS)
 
 
+# The encoder's stages: name, input channels and input size at 228 x 304 (the stem and the max-pool in front of layer1 leave 57 x 76).
+# Stage 0 is the whole of `features` — everything below the CSPN module — with the switch on every stage against the stock model: the
+# rest of a forward is its stock time less the stock stages'.
+ENCODER_STAGES = {0: ("features", 4, (228, 304)), 1: ("layer1", 64, (57, 76)), 2: ("layer2", 256, (57, 76)), 3: ("layer3", 512, (29, 38)),
+                  4: ("layer4", 1024, (15, 19)), 5: ("conv2", 2048, (8, 10))}
+_encoder_model = {}
+
+
+def encoder_convs(stage, C, H, W):
+    """(multiply-adds, elements moved once) of a stage's fused calls on one frame, from the shapes."""
+    macs = moved = 0
+    blocks = list(stage) if isinstance(stage, torch.nn.Sequential) else []
+    rows = []
+    for b in blocks:
+        convs = [getattr(b, n) for n in ("conv1", "conv2", "conv3") if hasattr(b, n)]
+        rows += [(c, False) for c in convs[:-1]] + ([(b.downsample[0], False)] if b.downsample is not None else []) + [(convs[-1], True)]
+    size = {}
+    for b in blocks:                                             # the input size of every convolution of the block
+        h, w = H, W
+        for n in ("conv1", "conv2", "conv3"):
+            if hasattr(b, n):
+                size[getattr(b, n)] = (h, w)
+                s = getattr(b, n).stride[0]
+                h, w = (h - 1) // s + 1, (w - 1) // s + 1
+        if b.downsample is not None:
+            size[b.downsample[0]] = (H, W)
+        H, W = h, w
+    for conv, residual in rows:
+        h, w = size[conv]
+        s, k = conv.stride[0], conv.kernel_size[0]
+        ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
+        macs += k * k * conv.in_channels * conv.out_channels * ho * wo
+        moved += conv.in_channels * h * w + conv.out_channels * ho * wo * (2 if residual else 1)
+    return macs, moved, sum(c.weight.numel() for c, _ in rows)
+
+
+def encoder_cases(s, r, dev, note):
+    """The residual stages and the bridge of unet_ours.resnet50 (include/cspn_convbn.h), in fp32 and in fp16:
+      fused   every convolution of the stage as one network.conv_bn.conv_bn_act call on packs made once (`fused_encoder`)
+      stock   the stage as the model runs it by default: MIOpen convolutions, eval batch norms, adds and ReLUs (half: of ``.half()``)"""
+    from cspn_monodepth_amd.network import conv_bn
+    name, C, (H, W) = ENCODER_STAGES[s]
+    if "net" not in _encoder_model:
+        torch.manual_seed(41)
+        net = unet_ours.resnet50(prop_time=24).to(dev).eval()
+        gen = torch.Generator(device=dev).manual_seed(41)
+        with torch.no_grad():
+            for m in net.modules():
+                if isinstance(m, torch.nn.BatchNorm2d):
+                    m.running_mean.normal_(0, 0.1, generator=gen)
+                    m.running_var.uniform_(0.5, 1.5, generator=gen)
+                    m.weight.normal_(1.0, 0.2, generator=gen)
+                    m.bias.normal_(0, 0.1, generator=gen)
+        _encoder_model["net"] = net
+    net = _encoder_model["net"]
+    gen = torch.Generator(device=dev).manual_seed(43 + s)
+    x32 = torch.rand((BATCH, C, H, W), generator=gen, device=dev) if s == 0 else torch.randn((BATCH, C, H, W), generator=gen, device=dev).relu_()
+    r.update(stage=name, x=[BATCH, C, H, W])
+    for dtype, key, tol in ((torch.float32, "float32", 1e-3), (torch.float16, "float16", 1e-1 if s == 0 else 2e-2)):      # features: ~160 roundings deep
+        x = x32.to(dtype)
+        if s == 0:
+            stock_m = net if dtype == torch.float32 else copy.deepcopy(net).half()
+            fused_m = copy.deepcopy(stock_m)
+            conv_bn.select_fused_encoder(fused_m, conv_bn.ENCODER_STAGES)
+            macs = moved = packed = 0
+            for t in range(1, 6):
+                _, c, (h, w) = ENCODER_STAGES[t]
+                m, v, p = encoder_convs(getattr(net, ENCODER_STAGES[t][0]), c, h, w) if t < 5 else (9 * c * c * h * w, 2 * c * h * w, 9 * c * c)
+                macs, moved, packed = macs + m, moved + v, packed + p
+
+            def fused(m=fused_m, x=x):
+                with torch.no_grad():
+                    return list(m.features(x)[:2])
+
+            def stock(m=stock_m, x=x):
+                with torch.no_grad():
+                    return list(m.features(x)[:2])
+            launches = sum(len(list(getattr(net, ENCODER_STAGES[t][0]))) for t in range(1, 5))      # blocks; the calls are counted per stage
+        elif s == 5:
+            conv, bn = (net.conv2, net.bn2) if dtype == torch.float32 else (copy.deepcopy(net.conv2).half(), copy.deepcopy(net.bn2).half())
+            pack = conv_bn.pack_conv_bn(conv.weight, bn, 1, dtype)
+            macs, moved, packed, launches = 9 * C * C * H * W, 2 * C * H * W, 9 * C * C, 1
+
+            def fused(pack=pack, x=x):
+                with torch.no_grad():
+                    return [conv_bn.conv_bn_act(x, pack, relu=False)]
+
+            def stock(conv=conv, bn=bn, x=x):
+                with torch.no_grad():
+                    return [bn(conv(x))]
+        else:
+            stock_m = getattr(net, name) if dtype == torch.float32 else copy.deepcopy(getattr(net, name)).half()
+            fused_m = copy.deepcopy(stock_m)
+            for b in fused_m:
+                b.fused_encoder = b.fused_encoder_half = True
+            macs, moved, packed = encoder_convs(stock_m, C, H, W)
+            launches = sum(3 + (b.downsample is not None) for b in stock_m)
+
+            def fused(m=fused_m, x=x):
+                with torch.no_grad():
+                    return [m(x)]
+
+            def stock(m=stock_m, x=x):
+                with torch.no_grad():
+                    return [m(x)]
+
+        got, want = fused(), stock()
+        assert all(g.dtype == w.dtype == dtype and g.shape == w.shape for g, w in zip(got, want))
+        agree = max(off(g, w) for g, w in zip(got, want))
+        assert agree <= tol, (name, key, agree)
+        note("%s %s: fused against stock, largest difference over largest element: %.2e" % (name, key, agree))
+        del got, want
+        esize = 4 if dtype == torch.float32 else 2
+        nbytes = (BATCH * moved + packed) * esize
+        r[key] = dict(multiply_adds=BATCH * macs, bytes=nbytes, fused_vs_stock_max_diff_over_max=agree, launches_fused=launches)
+        yield r[key], "%s %s" % (name, key), dict(fused=fused, stock=stock), 2 * BATCH * macs, nbytes, key
+
+
+def encoder_line(results):
+    whats = ("fused_warm_us", "fused_cold_us", "stock_warm_us", "stock_cold_us", "matrix_floor_us")
+    stages = dict((n, r) for n, r in results.items() if n != "features")
+    line = dict(sums=dict((key, dict((what, round(sum(r[key][what] for r in stages.values()), 2)) for what in whats)) for key in MATRIX_PEAK_FLOPS),
+                fused_ahead=dict((key, [n for n, r in stages.items() if r[key]["fused_ahead"]]) for key in MATRIX_PEAK_FLOPS),
+                matrix_peak_flops_per_s=MATRIX_PEAK_FLOPS)
+    if "features" in results:                                    # the encoder's share of everything below the CSPN module, stock ops
+        line["encoder_share_of_features"] = dict(
+            (key, dict((mode, round(line["sums"][key]["stock_%s_us" % mode] / results["features"][key]["stock_%s_us" % mode], 3)) for mode in ("warm", "cold")))
+            for key in MATRIX_PEAK_FLOPS)
+    return line
+
+
 # cases, the family's keys of the line, whether a case records which floor binds
 FAMILIES = {"upconv": (upconv_cases, head_line("fused", "float32"), False), "uphalf": (uphalf_cases, head_line("half", "float16"), True),
-            "uptail": (uptail_cases, uptail_line, True), "upsplit": (upsplit_cases, head_line("split", "bfloat16"), True)}
+            "uptail": (uptail_cases, uptail_line, True), "upsplit": (upsplit_cases, head_line("split", "bfloat16"), True),
+            "encoder": (encoder_cases, encoder_line, True)}
 
 
 def main():
@@ -288,12 +425,13 @@ def main():
     ap.add_argument("family", choices=sorted(FAMILIES))
     ap.add_argument("--iters", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--stages", default="1,2,3,4")
+    ap.add_argument("--stages", default=None, help="default: 1,2,3,4; encoder: 0,1,2,3,4,5 (0: the whole of features)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.iters < 20 or a.iters % ROUNDS:
         ap.error("--iters must be at least 20 and a multiple of %d" % ROUNDS)
-    stages = [int(s) for s in a.stages.split(",")]
+    names = dict((s, row[0]) for s, row in (ENCODER_STAGES if a.family == "encoder" else STAGES).items())
+    stages = [int(s) for s in a.stages.split(",")] if a.stages else sorted(names)
     tool = a.family + "_bench"
     cases, line, floor_bound = FAMILIES[a.family]
     from cspn_monodepth_amd.network import conv_tuning
@@ -311,7 +449,7 @@ def main():
     flush = torch.empty(128 << 20, dtype=torch.float32, device=dev)
     results = {}
     for s in stages:
-        r = results[STAGES[s][0]] = {}
+        r = results[names[s]] = {}
         for d, label, variants, flops, nbytes, key in cases(s, r, dev, note):
             times = replay_times(variants, a.iters, a.warmup, flush)
             matrix_floor_us, hbm_floor_us = flops / PEAK_FLOPS[key] * 1e6, nbytes / HBM_PEAK * 1e6

@@ -42,6 +42,8 @@ HEADS_FORWARD, HEADS_BACKWARD_INPUT, HEADS_BACKWARD_WEIGHTS = 0, 1, 2      # the
 UPCONV_MAX_FILTERS = 2                                       # CSPN_UPCONV_MAX_FILTERS (include/cspn_upconv.h)
 UPCONV_F32_BF16X3 = 2                                        # CSPN_UPCONV_F32_BF16X3: a `dtype` of cspn_upconv_forward alone
 UPHALF_MAX_FILTERS = 2                                       # CSPN_UPHALF_MAX_FILTERS (include/cspn_uphalf.h)
+HEAD16_MAX_HEADS, HEAD16_MAX_OUT_CHANNELS = 4, 16            # CSPN_HEAD16_MAX_* (include/cspn_head16.h)
+HEAD16_TILE_H, HEAD16_TILE_W, HEAD16_CHANNEL_BLOCK = 8, 32, 32      # CSPN_HEAD16_TILE_*, CSPN_HEAD16_CHANNEL_BLOCK: the kernel's tiling
 
 
 class cspn_plan(ctypes.Structure):
@@ -221,6 +223,11 @@ def _families():
             "cspn_convbn_packed_bytes": (cs, [ci, ci, ci, ci]),
             "cspn_convbn_pack": [vp, ci, ci, ci, ci, ci, ci, vp, vp],
             "cspn_convbn_forward": [vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]}, opt_in=True),
+    ), (
+        family("head16", "cspn_head16.h", 1, {"cspn_head16.hip": False}, {
+            "cspn_head16_abi_version": None,
+            "cspn_head16_workspace_bytes": (cs, [ci, ci]),
+            "cspn_head16_forward": [vp, ptr(vp), ci, ptr(vp), ptr(ci), ci, vp, ci, ci, ci, ci, ci, ci, vp]}, opt_in=True),
     )
 
 
@@ -232,14 +239,19 @@ def _families():
 # tuples and digests they restate (convbn: `fused_encoder`, network/conv_bn.py).  They are built, declared and version-checked as
 # the opt-in ones and found by family(); their sources and headers are LATER_SOURCES / LATER_HEADERS, part of the build's staleness
 # stamp (_later_digest) and of no tuple or digest above.
-ALL_FAMILIES, LATER_FAMILIES = _families()
+#
+# LATEST_FAMILIES is a third part, for the families added after those tests were written in turn (head16: the half path of
+# `fused_heads`, network/up_pooling.py).  Built, declared, version-checked and found by family() as the others; their sources and
+# headers are LATEST_SOURCES / LATEST_HEADERS and carry a stamp of their own (_latest_digest) in a second file next to the library,
+# so that the first stamp is what it was.  No tuple or digest above contains them.
+ALL_FAMILIES, LATER_FAMILIES, LATEST_FAMILIES = _families()
 FAMILIES = tuple(f for f in ALL_FAMILIES if not f.opt_in)
 OPT_IN_FAMILIES = tuple(f for f in ALL_FAMILIES if f.opt_in)
 EVERY_FAMILY = ALL_FAMILIES + LATER_FAMILIES
 
 
 def family(name):
-    return next(f for f in EVERY_FAMILY if f.name == name)
+    return next(f for f in EVERY_FAMILY + LATEST_FAMILIES if f.name == name)
 
 
 def _files(suffix, benchmarked=None, families=FAMILIES):
@@ -255,6 +267,8 @@ BUILD_HEADERS = HEADERS + tuple(os.path.join(CSRC, f) for f in _files(".hpp", Fa
 EXPORTS = tuple(family("core").functions)      # every symbol include/cspn_hip.h declares
 LATER_SOURCES = _files(".hip", families=LATER_FAMILIES)
 LATER_HEADERS = tuple(os.path.join(CSRC, f) for f in _files(".hpp", families=LATER_FAMILIES)) + tuple(f.header for f in LATER_FAMILIES)
+LATEST_SOURCES = _files(".hip", families=LATEST_FAMILIES)
+LATEST_HEADERS = tuple(os.path.join(CSRC, f) for f in _files(".hpp", families=LATEST_FAMILIES)) + tuple(f.header for f in LATEST_FAMILIES)
 
 
 def _source_digest(flags, code_only=False):
@@ -290,20 +304,36 @@ def _later_digest(digest):
     return h.hexdigest()
 
 
+def _latest_digest(flags):
+    """The second stamp: the flags, then the sources and headers of LATEST_FAMILIES."""
+    import hashlib
+    h = hashlib.sha256(" ".join(flags).encode())
+    for path in [os.path.join(CSRC, f) for f in LATEST_SOURCES] + list(LATEST_HEADERS):
+        with open(path, "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()
+
+
+def _stamped(path, digest):
+    return os.path.exists(path) and open(path).read().strip() == digest
+
+
 def build(force=False, verbose=False):
     """hipcc cross-compiles for gfx950 without a GPU: the translation units are compiled in parallel to
     csrc/_build/*.o and linked into the in-tree .so (which travels with gpurun snapshots).  Staleness is decided by
-    a content hash of the sources + flags stored next to the library (file times do not survive every copy)."""
+    a content hash of the sources + flags stored next to the library (file times do not survive every copy), and for the
+    LATEST_FAMILIES by a second one in a file of its own: the build is current only if both match."""
     from concurrent.futures import ThreadPoolExecutor
-    srcs = [os.path.join(CSRC, f) for f in SOURCES + OPT_IN_SOURCES + LATER_SOURCES]
+    srcs = [os.path.join(CSRC, f) for f in SOURCES + OPT_IN_SOURCES + LATER_SOURCES + LATEST_SOURCES]
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     # -fno-slp-vectorize: the SLP pass pairs the stencil FMAs into v_pk_fma_f32 and pays for it with ~50 v_mov
     # per step to build operand pairs; scalar v_fma_f32 measured 4 % faster (profiles/).  No fast-math: 0/0 = NaN.
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-fno-slp-vectorize"] + \
         os.environ.get("CSPN_HIPCC_FLAGS", "").split() + ["-I", INCLUDE]
     digest = _later_digest(_source_digest(flags[:-2]))
-    stamp = SO_PATH + ".hash"
-    if not force and os.path.exists(SO_PATH) and os.path.exists(stamp) and open(stamp).read().strip() == digest:
+    latest = _latest_digest(flags[:-2])
+    stamp, stamp2 = SO_PATH + ".hash", SO_PATH + ".hash2"
+    if not force and os.path.exists(SO_PATH) and _stamped(stamp, digest) and _stamped(stamp2, latest):
         return SO_PATH
     bdir = os.path.join(CSRC, "_build")
     os.makedirs(bdir, exist_ok=True)
@@ -313,11 +343,15 @@ def build(force=False, verbose=False):
     for path in BUILD_HEADERS + LATER_HEADERS:
         with open(path, "rb") as fh:
             hdr.update(fh.read())
+    hdr2 = hdr.copy()                         # the translation units of LATEST_FAMILIES see their headers too; the others do not
+    for path in LATEST_HEADERS:
+        with open(path, "rb") as fh:
+            hdr2.update(fh.read())
 
     def compile_one(src):
         # per-object staleness: flags + headers + this translation unit (an edit to one kernel recompiles one file)
         obj = os.path.join(bdir, os.path.basename(src)[:-4] + ".o")
-        h = hdr.copy()
+        h = (hdr2 if os.path.basename(src) in LATEST_SOURCES else hdr).copy()
         with open(src, "rb") as fh:
             h.update(fh.read())
         want = h.hexdigest()
@@ -338,8 +372,9 @@ def build(force=False, verbose=False):
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
     os.replace(SO_PATH + ".tmp", SO_PATH)
-    with open(stamp, "w") as fh:
-        fh.write(digest + "\n")
+    for path, value in ((stamp, digest), (stamp2, latest)):
+        with open(path, "w") as fh:
+            fh.write(value + "\n")
     return SO_PATH
 
 
@@ -348,7 +383,7 @@ _lock = threading.Lock()
 
 
 def _declare(lib):
-    for fam in EVERY_FAMILY:
+    for fam in EVERY_FAMILY + LATEST_FAMILIES:
         for name, (restype, argtypes) in fam.functions.items():
             fn = getattr(lib, name)
             if restype is not ctypes.c_int:           # ctypes' default
@@ -369,7 +404,7 @@ def lib():
                         "cspn_monodepth_amd: %s is missing — build it with `python -c 'import __graft_entry__ as g; "
                         "g.build()'` (hipcc --offload-arch=gfx950).  There is no CPU fallback." % SO_PATH)
                 _lib = _declare(ctypes.CDLL(SO_PATH))
-                for fam in EVERY_FAMILY:
+                for fam in EVERY_FAMILY + LATEST_FAMILIES:
                     sub = "" if fam.name == "core" else fam.name      # cspn_abi_version, cspn_<family>_abi_version
                     if getattr(_lib, "cspn_%sabi_version" % (sub and sub + "_"))() != fam.abi_version:
                         raise RuntimeError("cspn_monodepth_amd: %sABI version mismatch" % (sub and sub + " "))

@@ -23,7 +23,8 @@ import torch.nn as nn
 
 from ..post_process import CSPN_new as post_process
 from .conv_bn import FusedBridge, FusedResidual, select_fused_encoder
-from .up_pooling import FusedHead, select_fused_decoder, select_fused_precision, select_fused_tail, up_pooling, up_pooling_conv3x3
+from . import up_pooling as _up
+from .up_pooling import FusedHead, select_fused_decoder, select_fused_precision, select_fused_tail, up_pooling
 
 __all__ = ["ResNet", "resnet50", "resnet18", "Bottleneck", "BasicBlock", "Gudi_UpProj_Block", "Gudi_UpProj_Block_Cat",
            "Simple_Gudi_UpConv_Block_Last_Layer", "UpProj_Block", "DECODER_SIZES_NYU"]
@@ -171,7 +172,9 @@ class ResNet(FusedBridge, nn.Module):
     and the state_dict keep the reference's [12,64,3,3] shape.  12 reproduces the reference's tensor (guidance [B,12,H,W]).
     fused_heads (off by default): both heads run as one ``up_pooling_conv3x3`` call on gud_up_proj_layer5's weight and the first
     `affinity_channels` filters of gud_up_proj_layer6's, without the un-pooled [B,64,H,W] map; blocks, parameters and state_dict
-    stay as they are (the one difference in values: up_pooling_conv3x3's docstring).
+    stay as they are (the one difference in values: up_pooling_conv3x3's docstring).  A half map (autocast, ``half()``) runs
+    ``up_pooling_conv3x3_half`` on the same weights — forward only, on the fp16 matrix cores (include/cspn_head16.h) — when no gradient
+    is needed (grad mode off, or nothing involved requires one), and the two stock blocks when one is.
     fused_decoder (off by default; independent of fused_heads): True, or a collection of block names out of "gud_up_proj_layer1" ..
     "gud_up_proj_layer4" — in eval mode with grad mode off a named block runs its head (un-pool, conv1 -> bn1 -> ReLU, sc_conv1 ->
     sc_bn1) as one ``up_pooling_conv5x5`` call and the rest of itself on stock ops; otherwise exactly the default code.  True selects
@@ -269,8 +272,9 @@ class ResNet(FusedBridge, nn.Module):
         x = self.gud_up_proj_layer4(x, skip4)
         if self.fused_heads:
             l5, l6 = self.gud_up_proj_layer5, self.gud_up_proj_layer6
-            coarse, guidance = up_pooling_conv3x3(x, (l5.conv1.weight, l6.conv1.weight[:self.affinity_channels]), l5.oheight, l5.owidth)
-            return guidance, coarse, sparse_depth
+            outs = _up.fused_heads_forward(x, (l5.conv1.weight, l6.conv1.weight[:self.affinity_channels]), l5.oheight, l5.owidth)
+            if outs is not None:                                       # None: a half x that needs a gradient, the stock blocks below
+                return outs[1], outs[0], sparse_depth
         return self.gud_up_proj_layer6(x, self.affinity_channels), self.gud_up_proj_layer5(x), sparse_depth
 
     def forward(self, x):

@@ -21,7 +21,8 @@ import torch.nn as nn
 from ..post_process import CSPN_ours as post_process
 from .unet_cspn_nyu import DECODER_SIZES_NYU, BasicBlock, Bottleneck, _conv
 from .conv_bn import FusedBridge, select_fused_encoder
-from .up_pooling import MyBlock, select_fused_decoder, select_fused_precision, select_fused_tail, up_pooling_conv3x3
+from . import up_pooling as _up
+from .up_pooling import MyBlock, select_fused_decoder, select_fused_precision, select_fused_tail
 
 __all__ = ["ResNet", "resnet50", "resnet18", "Bottleneck", "BasicBlock", "UpProj_Block", "Gudi_UpProj_Block",
            "Gudi_UpProj_Block_Cat", "Simple_Gudi_UpConv_Block", "Simple_Gudi_UpConv_Block_Last_Layer", "DECODER_SIZES_NYU", "decoder_sizes_for"]
@@ -110,7 +111,9 @@ class ResNet(FusedBridge, nn.Module):
     fused_heads (off by default): the two output heads run as one ``up_pooling_conv3x3`` call on the weights of
     gud_up_proj_layer5 / 6 instead of the two blocks — the [B,64,H,W] un-pooled map is neither written nor saved for the backward.
     The blocks and their parameters stay where they are (the same state_dict either way); the sums are the same terms in another
-    order, and a NaN in the decoder's last map spreads less far (up_pooling_conv3x3's docstring).
+    order, and a NaN in the decoder's last map spreads less far (up_pooling_conv3x3's docstring).  A half map (autocast,
+    ``half()``) runs ``up_pooling_conv3x3_half`` on the same weights — forward only, on the fp16 matrix cores (include/cspn_head16.h) —
+    when no gradient is needed (grad mode off, or nothing involved requires one), and the two stock blocks when one is.
     fused_decoder (off by default; independent of fused_heads): True, or a collection of block names out of "gud_up_proj_layer1" ..
     "gud_up_proj_layer4".  In eval mode with grad mode off a named block computes relu(bn1(conv1(up(x)))) and sc_bn1(sc_conv1(up(x)))
     with one ``up_pooling_conv5x5`` call on the compact map and runs the rest of itself on stock ops; in train mode or with grad mode
@@ -198,8 +201,9 @@ class ResNet(FusedBridge, nn.Module):
         x = self.gud_up_proj_layer4(x, skip4)
         if self.fused_heads:
             l5, l6 = self.gud_up_proj_layer5, self.gud_up_proj_layer6
-            blur_depth, guidance = up_pooling_conv3x3(x, (l5.conv1.weight, l6.conv1.weight), l5.oheight, l5.owidth)
-            return blur_depth, guidance, sparse_depth
+            outs = _up.fused_heads_forward(x, (l5.conv1.weight, l6.conv1.weight), l5.oheight, l5.owidth)
+            if outs is not None:                                       # None: a half x that needs a gradient, the stock blocks below
+                return outs[0], outs[1], sparse_depth
         return self.gud_up_proj_layer5(x), self.gud_up_proj_layer6(x), sparse_depth
 
     def forward(self, x):

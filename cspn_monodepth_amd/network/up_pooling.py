@@ -20,6 +20,8 @@ empty tensor (unet_ours.py:147-148) or an all-zero one (the mask loop never runs
 ``up_pooling_conv3x3`` is the un-pooling by 2 fused with the bias-free 3x3 convolutions that follow it in the two output heads
 (``Simple_Gudi_UpConv_Block_Last_Layer``, unet_ours.py:194-202): the un-pooled map is never written (include/cspn_heads.h).  It is
 opt-in — ``fused_heads=True`` of the models — and differs from the two-block path in one stated way, see its docstring.
+``up_pooling_conv3x3_half`` is its forward for a half ``x`` (``torch.autocast``, ``model.half()``) on the fp16 matrix cores
+(include/cspn_head16.h), and ``fused_heads_forward`` is how the models choose between the two and the stock blocks.
 
 ``up_pooling_conv5x5`` is the same for the head of a decoder block (``Gudi_UpProj_Block``, ``Gudi_UpProj_Block_Cat``, ``UpProj_Block``,
 ``Simple_Gudi_UpConv_Block``, unet_ours.py:160-248): un-pooling by 2, the one or two bias-free 5x5 convolutions over it, their batch
@@ -43,7 +45,7 @@ from torch.autograd.function import Function, once_differentiable
 from .. import _lib
 from .._host import _dt, _p, _require_device, launch
 
-__all__ = ["up_pooling", "up_pooling_conv3x3", "up_pooling_conv5x5", "pack_upconv5x5", "UpconvPack", "pack_conv3x3", "conv3x3_bn_act", "MyBlock"]
+__all__ = ["up_pooling", "up_pooling_conv3x3", "up_pooling_conv3x3_half", "fused_heads_forward", "up_pooling_conv5x5", "pack_upconv5x5", "UpconvPack", "pack_conv3x3", "conv3x3_bn_act", "MyBlock"]
 _UPCONV_KERNELS = {torch.float32: ("cspn_upconv_workspace_bytes", "cspn_upconv_pack", "cspn_upconv_forward", True, 4),      # by pack dtype: bytes, pack, forward,
                    torch.float16: ("cspn_uphalf_packed_bytes", "cspn_uphalf_pack", "cspn_uphalf_forward", False, 2)}       # forward takes a dtype, element size
 
@@ -198,6 +200,79 @@ def up_pooling_conv3x3(x, weights, oheight, owidth):
     if torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in weights)):
         return _UpPoolingConv3x3.apply(x, oheight, owidth, *weights)
     return _heads_forward(x.contiguous(), tuple(w.contiguous() for w in weights), oheight, owidth)
+
+
+def up_pooling_conv3x3_half(x, weights, oheight, owidth):
+    """``up_pooling_conv3x3`` for a half ``x``, forward only, on the fp16 matrix cores (include/cspn_head16.h):
+
+        x [N,C,H,W] fp16, weights (w_0 [O_0,C,3,3], ...)  ->  (y_0 [N,O_0,oheight,owidth], ...) fp16
+        y_h == conv2d(up_pooling(x, 2, oheight, owidth), w_h, padding=1)
+
+    without the un-pooled map.  The weights are all fp32 (autocast: rounded to fp16 once, to nearest even) or all fp16
+    (``model.half()``: taken as they are); fp16 products accumulated in fp32, one rounding of the result to fp16, beyond the fp16
+    range +-Inf.  At most 4 heads with at most 16 output channels together; 1 <= oheight <= 2H, 1 <= owidth <= 2W; every tensor
+    below 2^31 elements.  Every output element is one fixed chain (the header says which), so a frame's bits do not depend on the
+    batch, runs repeat, and the call can be captured in a graph.  Non-contiguous inputs are made contiguous.
+
+    Forward only.  With grad mode on and ``x`` or a weight requiring a gradient it raises: training runs the stock blocks
+    (``up_pooling`` and the 3x3 convolutions, as the models do by default).
+
+    The difference from the two-block path is ``up_pooling_conv3x3``'s: a NaN or Inf in ``x[n,c,i,j]`` reaches only the outputs whose
+    3x3 window covers (2i, 2j)."""
+    who = "up_pooling_conv3x3_half"
+    if not isinstance(weights, (tuple, list)):
+        raise ValueError("%s: weights must be a tuple of [O,C,3,3] tensors" % who)
+    weights = tuple(weights)
+    if x.dim() != 4:
+        raise ValueError("%s: x must be [N,C,H,W], got %s" % (who, tuple(x.shape)))
+    if not 1 <= len(weights) <= _lib.HEAD16_MAX_HEADS:
+        raise ValueError("%s: between 1 and %d heads, got %d" % (who, _lib.HEAD16_MAX_HEADS, len(weights)))
+    N, C, H, W = x.shape
+    for h, w in enumerate(weights):
+        if w.dim() != 4 or w.shape[0] < 1 or tuple(w.shape[1:]) != (C, 3, 3):
+            raise ValueError("%s: weight %d must be [O,%d,3,3], got %s" % (who, h, C, tuple(w.shape)))
+    total = sum(w.shape[0] for w in weights)
+    if total > _lib.HEAD16_MAX_OUT_CHANNELS:
+        raise ValueError("%s: %d output channels over all heads, at most %d" % (who, total, _lib.HEAD16_MAX_OUT_CHANNELS))
+    if x.dtype != torch.float16:
+        raise ValueError("%s: x must be fp16 (a fp32 x takes up_pooling_conv3x3), got %s" % (who, x.dtype))
+    for w in weights:
+        if w.dtype not in (torch.float32, torch.float16):
+            raise ValueError("%s: the weights are fp32 or fp16, got %s" % (who, w.dtype))
+        if w.dtype != weights[0].dtype:
+            raise ValueError("%s: the weights of one call have one dtype, got %s and %s" % (who, weights[0].dtype, w.dtype))
+    oheight, owidth = int(oheight), int(owidth)
+    if not (1 <= oheight <= 2 * H and 1 <= owidth <= 2 * W):
+        raise ValueError("%s: output %dx%d must lie within [1, %d] x [1, %d] (scale 2 of a %dx%d input)"
+                         % (who, oheight, owidth, 2 * H, 2 * W, H, W))
+    if N < 1 or C < 1 or H < 1 or W < 1:
+        raise ValueError("%s: empty input %s" % (who, tuple(x.shape)))
+    if x.numel() >= 2 ** 31 or N * max(w.shape[0] for w in weights) * oheight * owidth >= 2 ** 31:
+        raise ValueError("%s: a tensor of 2^31 elements or more; split the batch" % who)
+    if torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in weights)):
+        raise RuntimeError("%s is forward-only: with grad mode on, run the stock blocks (up_pooling and the 3x3 convolutions, the "
+                           "models' default and their training path), or call it under torch.no_grad()" % who)
+    dev = _require_device(x, *weights)
+    xc, wc = x.contiguous(), tuple(w.detach().contiguous() for w in weights)
+    nbytes = _lib.lib().cspn_head16_workspace_bytes(total, C)
+    if not nbytes:
+        raise RuntimeError("cspn_head16_workspace_bytes: no workspace for %d output channels over %d channels" % (total, C))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    outs = tuple(torch.empty((N, w.shape[0], oheight, owidth), dtype=torch.float16, device=dev) for w in wc)
+    launch(dev, "cspn_head16_forward", _p(xc), _ptrs(wc), _dt(wc[0]), _ptrs(outs), _channels(wc), len(wc), _p(work), N, C, H, W, oheight, owidth)
+    return outs
+
+
+def fused_heads_forward(x, weights, oheight, owidth):
+    """What the models' `fused_heads` runs on the decoder's last map: a fp16 ``x`` with no gradient needed — grad mode off, or neither
+    ``x`` nor a weight requiring one — takes ``up_pooling_conv3x3_half``; everything else ``up_pooling_conv3x3`` (fp32: its
+    kernels and its autograd node; any other dtype: its refusal).  None: a fp16 ``x`` that needs a gradient — the caller runs the two
+    stock blocks, the training path in half."""
+    if x.dtype == torch.float16:
+        if torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in weights)):
+            return None
+        return up_pooling_conv3x3_half(x, weights, oheight, owidth)
+    return up_pooling_conv3x3(x, weights, oheight, owidth)
 
 
 class UpconvPack(object):
